@@ -7,8 +7,14 @@ One step = the reference training step (run_pde_observers.py:185-193): zero_grad
 forward -> LpLoss(sum) -> backward -> [N>1: one RCCL all-reduce(SUM) of the flat gradient
 bucket] -> Adam.  All arithmetic of forward/backward runs in the HIP engine.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`)
+
+A plain run sets up, runs W warm-up steps, times ONE block of exactly K steps (`ms_per_step` = that block / K) and prints
+the result line.  --full adds everything else the line can carry: 15 timed blocks (median, min, max; --repeats), the
+exact-fp32 and matrix-core contraction arms, the per-kernel roofline from profiled steps, the exchange timing for N > 1 and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step computed (loss, parameters after Adam, gradients) as
+DIR/<name>.npy, float32, at most 64 MB (see dump_outputs).
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md section "Measurement").
 """
@@ -347,15 +353,52 @@ def spawn_ranks(n, cmd, extra_env=None):
     return out0, max(abs(rc) for rc in rcs)
 
 
+DUMP_LIMIT_FLOATS = 15 * 2 ** 20      # 60 MB of float32 over all files of --dump-outputs (the promise is at most 64 MB)
+
+
+def dump_outputs(out_dir, loss, named_params):
+    """--dump-outputs: what a caller of the timed step holds after its last step - `loss.npy`, and per parameter
+    `param.<name>.npy` (its value after the Adam update) and `grad.<name>.npy` (the gradient that update used), float32,
+    complex parameters as (..., 2) real / imaginary pairs.  When all of it is larger than DUMP_LIMIT_FLOATS every tensor is
+    cut to the same fraction: one element drawn from each of k equal strata of its flattened values by a generator seeded with
+    its name, so the same elements are picked in every run and by every build; such a file holds that 1-D sample."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = [("loss", loss.detach().reshape(1))]
+    for name, p in named_params:
+        items.append(("param." + name, p.detach()))
+        if p.grad is not None:
+            items.append(("grad." + name, p.grad.detach()))
+    items = [(n, torch.view_as_real(t) if t.is_complex() else t) for n, t in items]
+    frac = min(1.0, DUMP_LIMIT_FLOATS / sum(t.numel() for _, t in items))
+    for name, t in items:
+        if frac < 1.0 and t.numel() > 1:
+            n = t.numel()
+            k = max(1, int(n * frac))
+            edges = np.arange(k + 1, dtype=np.int64) * n // k
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = edges[:-1] + (rng.random(k) * (edges[1:] - edges[:-1])).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="fno2d_128x128_w64_m12_b64", choices=sorted(CONFIGS))
-    ap.add_argument("--repeats", type=int, default=15,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed block of --steps steps is run this many times (each bracketed by barrier + synchronize, "
-                         "MAX over ranks); ms_per_step / value are the MEDIAN block, value_min / value_max the extremes")
+                         "MAX over ranks); ms_per_step / value are the MEDIAN block, value_min / value_max the extremes "
+                         "(default: 1, with --full 15)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: 15 timed blocks unless --repeats says otherwise, the exact-fp32 and matrix-core "
+                         "contraction arms, per-kernel roofline from profiled steps, exchange timing (N > 1), CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's loss, updated parameters and gradients as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-child", default=None, help=argparse.SUPPRESS)     # internal: the pinned CPU-baseline process
     ap.add_argument("--profile-steps", type=int, default=5)
@@ -373,6 +416,10 @@ def main():
     args = ap.parse_args()
     if args.cpu_child:
         return cpu_child(json.loads(args.cpu_child))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 15 if args.full else 1
     if CONFIGS[args.config].get("graph") and not args.eager:
         # (N > 1 too since round 6: the step replays as two graphs with the all-reduce of a plain bucket between them)
         args.graph = True
@@ -532,11 +579,13 @@ def main():
     srt = sorted(blocks)
     dt = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
     fields_per_s = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model.named_parameters())      # before any --full arm steps the model again
 
     # ---- the precision-matched arm: the same step with every channel GEMM on the exact-fp32 matrix instructions
     # (fno_set_gemm_mode(0): v_mfma_f32_32x32x2_f32, no split-precision products) - a short second timed block, same bracketing
     exact_fp32 = None
-    if not args.no_exact_fp32 and _lib.lib().fno_get_gemm_mode() == 1:
+    if args.full and not args.no_exact_fp32 and _lib.lib().fno_get_gemm_mode() == 1:
         # (every workload since round 6: the observers' modules take the unfused compositions where a fused path exists in
         # split precision only - loose rows, the regressor tails; eager steps: a captured graph holds the split-precision launches)
         Lb = _lib.lib()
@@ -574,7 +623,8 @@ def main():
     # sequence k_axis_fwd -> k_mode_gemm (v_mfma_f32_32x32x2_f32, exact fp32, one workgroup per mode x 64 batch rows) ->
     # k_axis_inv is the matrix-core arm: the same step timed with fno_set_fused_mid(0), its kernels profiled below.
     mode_contraction = None
-    if fused_model and not args.graph and not args.no_exact_fp32 and cfg["kind"] == "2d" and _lib.lib().fno_get_fused_mid() == 1:
+    if (args.full and fused_model and not args.graph and not args.no_exact_fp32 and cfg["kind"] == "2d"
+            and _lib.lib().fno_get_fused_mid() == 1):
         Lb = _lib.lib()
         Lb.fno_set_fused_mid(0)
         try:
@@ -619,7 +669,7 @@ def main():
 
     # ---- N > 1: what the gradient exchange costs, and how much of it the overlap hides ----
     exchange = None
-    if dist_on:
+    if args.full and dist_on:
         bucket.time_exchange(True)
         for _ in range(max(5, args.profile_steps)):
             eager_step()
@@ -635,7 +685,7 @@ def main():
     roofline = None
     kernels = []
     # (every rank runs the profiled steps - for N > 1 they contain the collective of the gradient exchange; rank 0 reports)
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         L = _lib.lib()
         L.fno_profile_reset()
         L.fno_profile_enable(1)
@@ -743,7 +793,7 @@ def main():
     # host is full, so `value` is the best of an 8 / 16 / 32-thread sweep and `all_cores` the figure SURVEY section 8d asks
     # for: every physical core of the host, one field, bounded at 120 s.
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         kind = cfg["kind"]
         bs = min({"2d": 8, "rno2d": 2, "rno2d_shipped": 8, "pino_ff": 4, "pino_ff_pde": 4}.get(kind, 1), B)
         tshape = [bs] + list((tgt[0] if isinstance(tgt, tuple) else tgt).shape[1:])
@@ -798,6 +848,7 @@ def main():
                           "per kernel: kernels[].pipe")
                          if _lib.lib().fno_get_gemm_mode() == 1 else "f32 (v_mfma_f32_32x32x2_f32)",
             "data": "synthetic",
+            "full": args.full,      # False: the extra arms, roofline / kernels and cpu_baseline below were not run (null / [])
             "repeats": len(blocks),
             "value_min": round(B * world * args.steps / max(blocks), 2),
             "value_max": round(B * world * args.steps / min(blocks), 2),

@@ -375,6 +375,40 @@ def test_bench_self_launch_spawns_one_process_per_rank(tmp_path):
     assert rc != 0
 
 
+def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs): loss, parameters and gradients as float32 .npy files, complex
+    parameters as real / imaginary pairs, in full while they fit; above the size limit every tensor is cut to the same
+    fraction by a sample fixed by its name, so two runs (or two builds) pick the same elements.  CPU tensors stand in."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn(40, 30, generator=g, requires_grad=True)
+    z = torch.randn(6, 5, dtype=torch.complex64, generator=g).requires_grad_(True)
+    w.grad, z.grad = torch.randn(40, 30, generator=g), torch.randn(6, 5, dtype=torch.complex64, generator=g)
+    params = [("w", w), ("spec.z", z)]
+    loss = torch.tensor(1.5)
+    bench.dump_outputs(str(tmp_path / "a"), loss, params)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grad.spec.z.npy", "grad.w.npy", "loss.npy", "param.spec.z.npy", "param.w.npy"]
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "param.w.npy"), w.detach().numpy())
+    zz = np.load(tmp_path / "a" / "grad.spec.z.npy")
+    assert zz.dtype == np.float32 and zz.shape == (6, 5, 2) and np.array_equal(zz, torch.view_as_real(z.grad).numpy())
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_FLOATS", 600)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), loss, params)
+    total = 0
+    for f in files:
+        b, c = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
+        assert b.dtype == np.float32 and np.array_equal(b, c)
+        total += b.size
+    assert total <= 600 + len(files)
+    sw = np.load(tmp_path / "b" / "param.w.npy")
+    full = w.detach().numpy().reshape(-1)
+    assert 1 < sw.size < full.size and np.isin(sw, full).all() and len(np.unique(sw)) == sw.size
+
+
 def test_bucket_hooks_are_released_and_live_extent_growth_is_refused():
     """a segmented bucket registers parameter hooks and a direct-write hook; close() (or dropping the bucket)
     releases both, and a batch with a longer last dimension than the sample the exchange was planned on is refused."""

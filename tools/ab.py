@@ -13,7 +13,7 @@ for e in args:
         for kv in e.split():
             k, v = kv.split("=", 1)
             env[k] = v
-    cmd = [sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"] + (["--config", cfg] if cfg else [])
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"] + (["--config", cfg] if cfg else [])
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=200).stdout
         d = json.loads(out.strip().splitlines()[-1])

@@ -1,11 +1,12 @@
 # usage: tools/ab_kern.sh <rounds> <lib|default> ...   interleaved bench runs on one box; prints step time and the big kernels' event times
+out=${OUT_DIR:-bench_out}; mkdir -p $out
 n=$1; shift
 for i in $(seq $n); do for l in "$@"; do
   [ "$l" = default ] && lp="" || lp=$PWD/tools/_libs/$l
-  FNO_LIB_PATH=$lp timeout -k 10 300 python bench.py --no-cpu-baseline --repeats 5 --steps 20 --warmup 5 --no-exact-fp32 --profile-steps 20 > gpurun_out/ab_tmp.json 2>> gpurun_out/ab.err
+  FNO_LIB_PATH=$lp timeout -k 10 300 python bench.py --full --no-cpu-baseline --repeats 5 --steps 20 --warmup 5 --no-exact-fp32 --profile-steps 20 > $out/ab_tmp.json 2>> $out/ab.err
   python - "$l" <<PY
 import json,sys
-d=json.loads(open("gpurun_out/ab_tmp.json").read().strip().splitlines()[-1])
+d=json.loads(open("$out/ab_tmp.json").read().strip().splitlines()[-1])
 ks={k["name"]:k["avg_ms_events"] for k in d["kernels"]}
 print("%-16s %.4f"%(sys.argv[1], d["ms_per_step"]), " ".join("%s %.4f"%(n[2:],ks[n]) for n in ("k_proj_bwd","k_block_bwd","k_block_bwd0","k_pw_fwd_block","k_pw_fwd_block0","k_proj_fwd","k_spec_mid") if n in ks))
 PY

@@ -9,26 +9,26 @@ tag="$1"; quick="$2"; R=$PWD; out=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp; cd $R
 T="timeout -k 5 240"
 if [ "$quick" != "bench" ]; then
-$T python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+$T python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "headline done" >> $out/${tag}_progress.log
 fi
 if [ -z "$quick" ] || [ "$quick" = "bench" ]; then
-$T python3 bench.py --config fno2d_64x64_w32_m8_b4 --steps 50 > $out/${tag}_bench_cfg1.json 2>> $out/${tag}_bench.err
-$T python3 bench.py --config fno2d_64x64_w32_m8_b4 --no-cpu-baseline --steps 50 --eager > $out/${tag}_bench_cfg1_eager.json 2>> $out/${tag}_bench.err
-$T python3 bench.py --config fno3d_64_w32_m8_b16 --steps 10 > $out/${tag}_bench_fno3d.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config fno2d_64x64_w32_m8_b4 --steps 50 > $out/${tag}_bench_cfg1.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config fno2d_64x64_w32_m8_b4 --no-cpu-baseline --steps 50 --eager > $out/${tag}_bench_cfg1_eager.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config fno3d_64_w32_m8_b16 --steps 10 > $out/${tag}_bench_fno3d.json 2>> $out/${tag}_bench.err
 for c in rno2d_128x128_w64_m12_b32 rno2d_32x32_w34_m12_b32 pino_fullfield_32x32_w64_m12_b32 pino_fullfield_pde_32x130x32_w64_m12_b32 \
          pinobserver2d_128x128x65_w64_m8_b2 pino_finetune_128x128x65_w64_m8_b4 pino_finetune_256x256x65_w64_m20_b1; do
-  $T python3 bench.py --config $c --steps 10 --warmup 3 > $out/${tag}_bench_$c.json 2>> $out/${tag}_bench.err
+  $T python3 bench.py --full --config $c --steps 10 --warmup 3 > $out/${tag}_bench_$c.json 2>> $out/${tag}_bench.err
   echo "$c done" >> $out/${tag}_progress.log
 done
-$T python3 bench.py --config rno2d_128x128_w64_m12_b32 --steps 10 --warmup 3 --graph --no-cpu-baseline > $out/${tag}_bench_rno2d_128x128_w64_m12_b32_graph.json 2>> $out/${tag}_bench.err
-$T python3 bench.py --config pino_fullfield_32x32_w64_m12_b32 --steps 10 --warmup 3 --eager --no-cpu-baseline > $out/${tag}_bench_pino_fullfield_32x32_w64_m12_b32_eager.json 2>> $out/${tag}_bench.err
-$T python3 bench.py --config pino_fullfield_pde_32x130x32_w64_m12_b32 --steps 10 --warmup 3 --eager --no-cpu-baseline > $out/${tag}_bench_pino_fullfield_pde_32x130x32_w64_m12_b32_eager.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config rno2d_128x128_w64_m12_b32 --steps 10 --warmup 3 --graph --no-cpu-baseline > $out/${tag}_bench_rno2d_128x128_w64_m12_b32_graph.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config pino_fullfield_32x32_w64_m12_b32 --steps 10 --warmup 3 --eager --no-cpu-baseline > $out/${tag}_bench_pino_fullfield_32x32_w64_m12_b32_eager.json 2>> $out/${tag}_bench.err
+$T python3 bench.py --full --config pino_fullfield_pde_32x130x32_w64_m12_b32 --steps 10 --warmup 3 --eager --no-cpu-baseline > $out/${tag}_bench_pino_fullfield_pde_32x130x32_w64_m12_b32_eager.json 2>> $out/${tag}_bench.err
 fi
 [ "$quick" = "bench" ] && exit 0
 prof() {   # prof <name> <bench args...>: kernel-trace stats of one workload
   local name=$1; shift
-  $T rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats_$name -- python3 bench.py "$@" --no-cpu-baseline --no-exact-fp32 > $out/${tag}_stats_$name.log 2>&1
+  $T rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats_$name -- python3 bench.py --full "$@" --no-cpu-baseline --no-exact-fp32 > $out/${tag}_stats_$name.log 2>&1
   cp $(ls $out/${tag}_stats_$name/*/*kernel_stats.csv | head -1) $out/${tag}_kernel_stats_$name.csv
   echo "stats $name done" >> $out/${tag}_progress.log
 }
