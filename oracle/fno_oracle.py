@@ -156,11 +156,13 @@ def complex_weight(p, key):
 
 
 def fno_forward(p, x, n_modes, n_layers=4, fft_norm="forward",
-                weight_leaf="tensor", return_intermediates=False):
+                weight_leaf="tensor", return_intermediates=False, preact=False):
     """neuralop.models.FNO.forward (tfno.py:195-211) on the default path:
     lifting (tfno.py:11-20) -> n_layers x FNOBlocks.forward (fno_block.py:123-170,
     skip = bias-free 1x1 conv, skip_connections.py:31) -> projection (tfno.py:23-38,
-    F.gelu exact-erf).  `p` maps reference state_dict names to tensors."""
+    F.gelu exact-erf).  `p` maps reference state_dict names to tensors.
+    return_intermediates: also the lifting output and every block's output (after its GELU gate; preact=True: before it,
+    the u_l the fused engine stores)."""
     order = len(n_modes)
     half = [m // 2 for m in n_modes]
     nw = 2 ** (order - 1)
@@ -173,9 +175,10 @@ def fno_forward(p, x, n_modes, n_layers=4, fft_norm="forward",
         bias = p.get("fno_blocks.convs.bias")
         spec = spectral_conv_A(h, ws, None if bias is None else bias[l], half, fft_norm)
         h = spec + skip
+        pre = h
         if fno_gelu_gate(l, n_layers):
             h = F.gelu(h)
-        inter.append(h)
+        inter.append(pre if preact else h)
     h = conv1x1(h, p["projection.fc1.weight"], p["projection.fc1.bias"])
     h = F.gelu(h)
     y = conv1x1(h, p["projection.fc2.weight"], p["projection.fc2.bias"])

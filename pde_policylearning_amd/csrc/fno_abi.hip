@@ -950,9 +950,12 @@ struct FnoModelPlan {
 };
 
 static const int kHID = 256;
-// magnitude bounds kept at the end of the forward's `saved` buffer (fno_dev.h "h2"): [0] max |u_L| (projection input), [1] max |dy|
+// magnitude bounds kept at the end of the forward's `saved` buffer (fno_dev.h "h2"; tests/test_hostile_ranges_gpu.py checks each):
+// [7] max |x| of the model input (k_lift_rowdft), [8] the bound of |u_0| block 0's forward derives from it (fused lifting:
+// lift_u0_bound), [8 + l] max |u_l| as stored (l >= 1), [32 + l] max |dL/du_l| (the backward's gradient chain, l >= 1),
+// [60] max |dy|, [61] max |W1|, [62] max |w2| (the projection backward's scalars, bwd_b = amax + 59); the others stay 0
 static_assert(8 + FNO_MAX_LAYERS + 1 <= 32 && 32 + FNO_MAX_LAYERS + 1 <= 59, "bound slots: [8, 32) forward |u_l|, [32, 59) backward |g_l|, [59, 63) projection scalars");
-static const int kNAmax = 64;      // [1] max |dy|, [2] max |W1|, [3] max |w2|, [6] max |g| (backward chain), [7] max |x| (model input), [8 + l] max |u_l|
+static const int kNAmax = 64;
 // persistent-grid size per CU of the forward kernels (= workgroups that fit: registers / LDS)
 #ifndef FNO_GRID_LIFT
 #define FNO_GRID_LIFT 3
@@ -1174,10 +1177,14 @@ static bool blk_fwd_s_ok(const FnoModelPlan* p, const PwFwdArgs& a) {
   if ((size_t)a.PW * 4 * 64 >= (size_t)1 << 31) return false;          // 32-bit offsets within one sample
   return true;
 }
+// *ub_published (if given): the launched kernel left the bound of |u_0| at a.ubound (the LIFT variants do when a.xmax is set:
+// lift_u0_bound, fno_dev.h) - the two-term block-0 backward splits u_0 by it, so the host hands it on only when it was written
 template <int C>
-static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a_in) {
+static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a_in, bool* ub_published = nullptr) {
   size_t lds2 = 0;
   const PwFwdArgs& a = a_in;
+  if (ub_published) *ub_published = false;
+  const bool ub = a_in.lw && a_in.ubound && a_in.xmax;      // what the LIFT variants below publish
   // profile label: block 0 with the lifting recomputed reads the <= 4-channel model input instead of u_0 (bench.py prices it so)
   const char* nm = a_in.lw ? "k_pw_fwd_block0" : "k_pw_fwd_block";
   // (64 channels only: blk_fwd_t_ok refuses 32, where k_pw_fwd_x3 measured faster - `if constexpr` so that the 33 instantiations
@@ -1198,6 +1205,7 @@ static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, cons
       a.share32 = ((int)g3.x == 2 * p->ncu) ? share_bf : 0;
 #define BF3(AIN_, EPI_) return GT(2), launch(nm, k_blk_fwd_s<AIN_, EPI_>, g3, dim3(256), lds3, st, a)
       if (a.lw) {
+        if (ub_published) *ub_published = ub;
         if (epi == 2) return GT(2), launch(nm, k_blk_fwd_s<false, 2, true>, g3, dim3(256), lds3, st, a);
         if (epi == 1) return GT(2), launch(nm, k_blk_fwd_s<false, 1, true>, g3, dim3(256), lds3, st, a);
         return GT(2), launch(nm, k_blk_fwd_s<false, 0, true>, g3, dim3(256), lds3, st, a);
@@ -1215,7 +1223,7 @@ static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, cons
 #define BF2(LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_) return GT(3), launch(nm, k_blk_fwd_t<C, LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_>, g2, blk, lds2, st, a)
     const bool plain = !a.lw && !a.relu_out && !a.add;
     if (kz == 1) {
-      if (a.lw && !a.relu_out && !a.add && epi == 2) BF2(true, false, false, 2, false, 1);
+      if (a.lw && !a.relu_out && !a.add && epi == 2) { if (ub_published) *ub_published = ub; BF2(true, false, false, 2, false, 1); }
       if (plain && a.act_in) { if (epi == 2) BF2(false, false, true, 2, false, 1); if (epi == 1) BF2(false, false, true, 1, false, 1); BF2(false, false, true, 0, false, 1); }
       if (plain) { if (epi == 2) BF2(false, false, false, 2, false, 1); if (epi == 1) BF2(false, false, false, 1, false, 1); BF2(false, false, false, 0, false, 1); }
       if (!a.lw && a.relu_out && !a.add && epi == 0 && !a.act_in) BF2(false, true, false, 0, false, 1);
@@ -1230,9 +1238,11 @@ static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, cons
   if (p->loose && !a.relu_out)
     return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, true>, dim3(grid), dim3((C / 32) * (4 / FNO_NTW_PWX) * 64),
                   lds, st, a);
-  if (a.lw && !a.relu_out)
+  if (a.lw && !a.relu_out) {
+    if (ub_published) *ub_published = ub;
     return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, false, true>, dim3(grid), dim3((C / 32) * (4 / FNO_NTW_PWX) * 64),
                   lds, st, a);
+  }
   if (a.relu_out) {
     if (p->NPX != 128 || p->loose || a.lw) return fail(FNO_EUNSUPPORTED, "ReLU output: 128-pixel tiles of whole rows, no fused lifting");
     return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, false, false, true>, dim3(grid),
@@ -1243,9 +1253,10 @@ static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, cons
                   lds, st, a);
   return GT(3), launch(nm, k_pw_fwd_x3<C, 256, 2>, dim3(grid), dim3((C / 32) * 4 * 64), lds, st, a);
 }
-static int launch_block(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a) {
+static int launch_block(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a, bool* ub_published = nullptr) {
+  if (ub_published) *ub_published = false;
   if (p->loose && !g_gemm_x3) return fail(FNO_EUNSUPPORTED, "block stacks on loose rows need the split-precision GEMM mode");
-  if (g_gemm_x3) return p->d.C == 32 ? launch_block_x3<32>(p, st, grid, a) : launch_block_x3<64>(p, st, grid, a);
+  if (g_gemm_x3) return p->d.C == 32 ? launch_block_x3<32>(p, st, grid, a, ub_published) : launch_block_x3<64>(p, st, grid, a, ub_published);
   if (p->d.C == 32) return launch_pw<32, 32>(p, st, grid, a, "k_pw_fwd_block");
   return launch_pw<64, 64>(p, st, grid, a, "k_pw_fwd_block");
 }
@@ -1487,6 +1498,7 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
 
   const bool has_lift = d.Cin > 0, has_proj = d.Cout > 0;
   bool lift_xmax = false;      // max |x| of the model input was published (k_lift_rowdft)
+  bool u0_bound = false;       // block 0's forward published the bound of |u_0| (amax[8])
   FnoModelPlan::CallState cs;
   cs.B = B;
   PwFwdArgs a;
@@ -1547,7 +1559,9 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
     // zigzag: every block walks its tiles in the opposite direction of its producer, so that it starts on the part of its
     // input the producer wrote last - what the 256 MB Infinity Cache still holds of it (kernels without the option walk forward)
     a.rev = g_zigzag ? (l & 1) : 0;
-    LAUNCHCHK(launch_block(p, st, std::min(s.ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p->ncu), a));
+    bool ub = false;
+    LAUNCHCHK(launch_block(p, st, std::min(s.ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p->ncu), a, &ub));
+    if (l == 0) u0_bound = ub;
   }
 
   if (!has_proj) { p->put_call(saved, cs); return FNO_OK; }
@@ -1560,7 +1574,7 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
   pa.xmax = (h2 && L > 0) ? amax + 8 + L : nullptr;
   cs.h2_fwd = pa.xmax != nullptr;
   cs.bwd_clean = h2;
-  cs.h2_u0 = h2 && lift_xmax && g_h2;
+  cs.h2_u0 = h2 && lift_xmax && g_h2 && u0_bound;      // (else the three-term block-0 backward, which needs no bound)
   p->put_call(saved, cs);
   const int pgrid = std::min(pa.ntiles, FNO_GRID_PF * p->ncu);
   if (C == 32) LAUNCHCHK(launch_pfwd_c<32>(p, st, pgrid, pa));

@@ -648,6 +648,24 @@ FNO_DEV void stage_lift_params(float* lws, const float* lw, const float* lb, int
   for (int i = tid; i < 4 * C; i += nt) lws[i] = (i & 3) < CL ? lw[(i >> 2) * CL + (i & 3)] : 0.f;
   for (int i = tid; i < C; i += nt) lws[4 * C + i] = lb[i];
 }
+// Bound of channel c of u_0 = W_l x + b_l from a bound xmax of |x| and the staged lifting parameters:
+// |u_0[c]| <= sum_k |lw[c][k]| xmax + |lb[c]|.  The maximum over c is what every block-0 forward with a fused lifting publishes
+// (PwFwdArgs.ubound) for the two-term block-0 backward, which splits u_0 by it; k_blk_fwd_s also scales its own operand by it.
+// One formula for every kernel: the published value is the same bits whichever kernel ran.
+template <int C>
+FNO_DEV float lift_u0_bound(const float* lws, int c, float xmax) {
+  const float4 wv = ld4(lws + 4 * c);
+  return (fabsf(wv.x) + fabsf(wv.y) + fabsf(wv.z) + fabsf(wv.w)) * xmax + fabsf(lws[4 * C + c]);
+}
+// ... published by thread 0 of workgroup 0 alone (kernels that do not scale by it; lws must be visible: after a barrier)
+template <int C>
+FNO_DEV void lift_u0_bound_publish(const float* lws, const float* xmax, float* ubound) {
+  if (!ubound || !xmax || blockIdx.x != 0 || threadIdx.x != 0) return;
+  const float bx = *xmax;
+  float m = 0.f;
+  for (int c = 0; c < C; ++c) m = fmaxf(m, lift_u0_bound<C>(lws, c, bx));
+  *ubound = m;
+}
 // The same LDS image for block 0 of a model with a lifting layer, computed instead of loaded: the tile is
 // u_0 = W_l x + b_l of the <= 4-channel model input (tfno.py:11-20), so the 64-channel u_0 is never written to or read from
 // HBM.  px = idx % NPX with NT a multiple of NPX: a thread's items all sit on ONE pixel, whose CL input values are loaded

@@ -180,12 +180,10 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
 #pragma unroll
       for (int j = 0; j < 8; ++j) mw = fmaxf(mw, fabsf(wraw[kb][j]));
     sw = h2_scale(wg_max(mw));
-    if constexpr (LIFT) {                                  // |u_0[c]| <= sum_k |lw[c][k]| bx + |lb[c]|
+    if constexpr (LIFT) {                                  // |u_0[c]| <= sum_k |lw[c][k]| bx + |lb[c]|  (lift_u0_bound, fno_dev.h)
       float m = 0.f;
-      for (int c = tid; c < C; c += NT) {
-        const float4 wv = ld4(lws + 4 * c);                // (staged above; the first wg_max barrier made it visible)
-        m = fmaxf(m, (fabsf(wv.x) + fabsf(wv.y) + fabsf(wv.z) + fabsf(wv.w)) * bx + fabsf(lws[4 * C + c]));
-      }
+      for (int c = tid; c < C; c += NT)
+        m = fmaxf(m, lift_u0_bound<C>(lws, c, bx));       // (staged above; the first wg_max barrier made it visible)
       (void)wg_max(0.f);
       bx = wg_max(m);
       if (a.ubound && blockIdx.x == 0 && tid == 0) *a.ubound = bx;      // (the same value in every workgroup) for the backward pass
@@ -208,6 +206,8 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
   }
 
   __syncthreads();
+  // three-term LIFT variants: the bound of |u_0| for the two-term block-0 backward, as the strip kernel derives it (lws is visible)
+  if constexpr (LIFT && NT3 != 2) lift_u0_bound_publish<C>(lws, a.xmax, a.ubound);
 
   // one float4 of spectral rows = (o, re), (o, im), (o + 1, re), (o + 1, im) of row-mode rs -> k = 2 s, 2 s + 1 of two channels
   auto put_z = [&](int f, const float4& zq) {

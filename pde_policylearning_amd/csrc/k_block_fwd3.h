@@ -160,12 +160,10 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
     }
   }
   const float sw = h2_scale(wg_max(mw));
-  if constexpr (LIFT) {                                       // |u_0[c]| <= sum_k |lw[c][k]| bx + |lb[c]|  (as k_blk_fwd_t: the same bound, bit for bit)
+  if constexpr (LIFT) {                                       // |u_0[c]| <= sum_k |lw[c][k]| bx + |lb[c]|  (lift_u0_bound, fno_dev.h)
     float m = 0.f;
-    for (int c = tid; c < C; c += NT) {
-      const float4 wv = ld4(lws + 4 * c);                     // (staged above; wg_max's barriers made it visible)
-      m = fmaxf(m, (fabsf(wv.x) + fabsf(wv.y) + fabsf(wv.z) + fabsf(wv.w)) * bx + fabsf(lws[4 * C + c]));
-    }
+    for (int c = tid; c < C; c += NT)
+      m = fmaxf(m, lift_u0_bound<C>(lws, c, bx));             // (staged above; wg_max's barriers made it visible)
     bx = wg_max(m);
     if (a.ubound && blockIdx.x == 0 && tid == 0) *a.ubound = bx;      // (the same value in every workgroup) for the backward pass
   }

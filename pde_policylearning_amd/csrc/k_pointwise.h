@@ -49,8 +49,9 @@ struct PwFwdArgs {
   const float* lb;    // ... and bias (C); x is then the (B, CL, PW) model input
   int CL;
   int tiles_per_plane, ntiles;
-  const float* xmax;  // k_blk_fwd_t<.., NT3 = 2>: device scalar, a bound of |x| (of the model input with a fused lifting)
-  float* ubound;      // k_blk_fwd_t<LIFT, NT3 = 2>: the bound of |u_0| it derived from xmax and the lifting parameters is left here
+  const float* xmax;  // device scalar, a bound of |x| (of the model input with a fused lifting): the two-term block forwards scale by it
+  float* ubound;      // block-0 forwards with a fused lifting (LIFT variants of k_blk_fwd_s, k_blk_fwd_t, k_pw_fwd_x3), when xmax is
+                      // set: the bound of |u_0| derived from xmax and the lifting parameters is left here (lift_u0_bound, fno_dev.h)
   float* umax;        // if set: max |u| of what this launch stores is published here (atomic max of the float pattern; the
                       // two-term fp16 GEMMs of the consumer scale their operand by it: fno_dev.h, "h2")
   int share32 = 0;    // k_blk_fwd_t with two workgroups per CU: 32nds of a CU's tiles that go to the workgroup dispatched FIRST
@@ -313,6 +314,7 @@ __global__ void __launch_bounds__((C / 32) * (NPX / 32 / NTW) * 64, FNO_OCC_PWX)
   __shared__ __attribute__((aligned(16))) float lws[LIFT ? 5 * C : 4];
   if constexpr (LIFT) stage_lift_params<C>(lws, a.lw, a.lb, a.CL, tid, NT);     // visible after the first tile's barrier? no: sync here
   if constexpr (LIFT) __syncthreads();
+  if constexpr (LIFT) lift_u0_bound_publish<C>(lws, a.xmax, a.ubound);     // the bound of |u_0| for the two-term block-0 backward
   float4 zpf = make_float4(0.f, 0.f, 0.f, 0.f);
   auto issue = [&](int tile_) {
     const int tile = a.rev ? a.ntiles - 1 - tile_ : tile_;      // (zigzag along the kernel chain: k_blk_fwd_s)
