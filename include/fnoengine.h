@@ -41,6 +41,9 @@ const char* fno_last_error(void);
  *     operand is split into THREE bf16 terms instead and six products are kept (v_mfma_f32_32x32x16_bf16).  Error of either
  *     form against float64 = the fp32 MFMA's own (1.5e-7 relative at K = 64; DESIGN.md sections 4, 4d).
  * 0 = every GEMM on the exact fp32 matrix instruction (v_mfma_f32_32x32x2_f32).
+ * Both modes cover the fused model (fno_model_*) on whole rows, the block tails (fno_model_*_tail), the fan-outs
+ * (fno_fanout_*), the pointwise layers (fno_pointwise_*) and the projection heads (fno_projection_*, GELU and ReLU, every
+ * output width); block stacks on loose rows (fno_model_plan_create) are split-precision only.
  * Environment FNO_GEMM_F32=1 selects 0 at load time. */
 void fno_set_gemm_mode(int split_precision);
 int fno_get_gemm_mode(void);
@@ -183,7 +186,7 @@ int fno_model_backward_dx(const FnoModelPlan* plan, int batch, const FnoModelPar
  * element index and the two 32-bit words at `drop_seed` (device memory; the caller draws them per call and passes the same
  * pointer to the backward, which regenerates s instead of reading a mask; fno_dropout_scale writes s out for tests).
  * drop_p = 0 disables the dropout (evaluation mode).  Plans: Cin = Cout = 0, n_layers = 1, 32 / 64 channels, rows of
- * 32 / 64 / 128 floats, split-precision GEMM mode; anything else returns FNO_EUNSUPPORTED. */
+ * 32 / 64 / 128 floats, either GEMM mode; anything else returns FNO_EUNSUPPORTED. */
 typedef struct FnoBlockTail {
   int relu_out;
   float drop_p;
@@ -344,7 +347,7 @@ int fno_pointwise_backward(int batch, int channels, size_t plane, const float* x
  * Cout = 1, PW % 128 == 0: the `fc1 -> act -> fc2` tail of the observer models
  * (libs/models/pino_models/pinobserver.py:231-233, 270-273; neuralop/models/tfno.py:23-38), with the FNO
  * projection kernels (hidden tensor never materialised; backward recomputes it).  w1 (hidden, C), w2 (1, hidden).
- * backward writes dx and all four parameter gradients.  Needs the split-precision GEMM mode (default).
+ * backward writes dx and all four parameter gradients.  Either GEMM mode (fno_set_gemm_mode).
  * ---------------------------------------------------------------------- */
 size_t fno_projection_workspace_bytes(int channels, int hidden);
 int fno_projection_forward(int batch, int channels, int hidden, int cout, size_t plane, const float* x, const float* w1,

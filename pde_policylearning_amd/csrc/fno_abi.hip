@@ -1257,8 +1257,21 @@ static int launch_block(const FnoModelPlan* p, hipStream_t st, int grid, const P
   if (ub_published) *ub_published = false;
   if (p->loose && !g_gemm_x3) return fail(FNO_EUNSUPPORTED, "block stacks on loose rows need the split-precision GEMM mode");
   if (g_gemm_x3) return p->d.C == 32 ? launch_block_x3<32>(p, st, grid, a, ub_published) : launch_block_x3<64>(p, st, grid, a, ub_published);
+  if (a.relu_out) {      // one-layer stacks with a ReLU tail: the exact-fp32 twin of k_pw_fwd_x3<.., RELU = true>
+    if (p->NPX != 128 || p->loose || a.lw) return fail(FNO_EUNSUPPORTED, "ReLU output: 128-pixel tiles of whole rows, no fused lifting");
+    const size_t lds = pw_fwd_lds_bytes(p->d.C, p->d.C, 128, a.W, a.K2in, a.NJ, a.z != nullptr, a.x1 != nullptr);
+    if (p->d.C == 32)
+      return GT(1), launch("k_pw_fwd_block", k_pw_fwd<32, 32, 128, true>, dim3(grid), dim3(1 * 4 * 64), lds, st, a);
+    return GT(1), launch("k_pw_fwd_block", k_pw_fwd<64, 64, 128, true>, dim3(grid), dim3(2 * 4 * 64), lds, st, a);
+  }
   if (p->d.C == 32) return launch_pw<32, 32>(p, st, grid, a, "k_pw_fwd_block");
   return launch_pw<64, 64>(p, st, grid, a, "k_pw_fwd_block");
+}
+// k_block_bwd (k_block_bwd.h, exact fp32): g and u tiles, lifting-input rows, the tile's spectral rows and tables
+static size_t bbwd_lds(int C, int npx, const BlkBwdArgs& a) {
+  return ((size_t)2 * C * (npx + 4) + (a.xin ? 8 * (npx + 4) : 0) +
+          (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(npx / a.W) * a.K2in * C * 2 : 0) +
+          (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
 }
 // k_block_bwd_t (k_block_bwd2.h): two swizzled [3][C][128] bf16 images, the fp32 gout tile, two lifting-input buffers, tables
 static size_t bbwd_t_lds(int C, const BlkBwdArgs& a) {
@@ -1283,14 +1296,15 @@ static int launch_bbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const 
   // profile labels: block 0 behind a lifting layer reads g and the model input and writes no gradient tile unless dx is asked for
   const char* nm = (a_in.xin && !a_in.gout) ? "k_block_bwd0" : "k_block_bwd";
   const char* nm_kch = "k_block_bwd_kch";
-  const size_t pitch = p->NPX + 4;
   const bool h2 = g_h2 && g_h2_blocks && a.gmax_in && a.umax;      // two-term fp16 variants (operand bounds known)
   const int g2_terms = h2 ? 2 : 3;
   a.kx16 = (C == 64 && a.zg && a.K2in <= 8) ? 1 : 0;
   if (a.kx16 && bbwd_g2_lds(a, g2_terms) > 160 * 1024) a.kx16 = 0;
   if (a.drop_seed) {      // dropout of the spectral branch (one-layer stacks with a tail, fno_model_*_tail)
-    if (p->loose || a.lw || a.xin || !g_gemm_x3 || p->NPX != 128 || bbwd_t_lds(C, a) > 160 * 1024)
-      return fail(FNO_EUNSUPPORTED, "spectral-branch dropout: split-precision GEMM mode, 128-pixel tiles of whole rows, no lifting");
+    if (p->loose || a.lw || a.xin || p->NPX != 128 || (g_gemm_x3 ? bbwd_t_lds(C, a) : bbwd_lds(C, 128, a)) > 160 * 1024)
+      return fail(FNO_EUNSUPPORTED, "spectral-branch dropout: 128-pixel tiles of whole rows, no lifting");
+    if (!g_gemm_x3)      // exact-fp32 mode: the first-generation kernel with the same regenerated mask
+      return GT(1), launch(nm, k_block_bwd<C, 128, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_lds(C, 128, a), st, a);
     return GT(3), launch(nm, k_block_bwd_t<C, 128, false, false, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64),
                   bbwd_t_lds(C, a), st, a);
   }
@@ -1347,9 +1361,7 @@ static int launch_bbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const 
       if (h2) return GT(2), launch(nm, k_block_bwd_t<C, 128, false, false, false, 2>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
     return GT(3), launch(nm, k_block_bwd_t<C, 128>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
   }
-  const size_t lds = ((size_t)2 * C * pitch + (a.xin ? 8 * pitch : 0) +
-                      (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(p->NPX / a.W) * a.K2in * C * 2 : 0) +
-                      (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
+  const size_t lds = bbwd_lds(C, p->NPX, a);
   if (p->NPX == 128)
     return GT(1), launch(nm, k_block_bwd<C, 128>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), lds, st, a);
   return GT(1), launch(nm, k_block_bwd<C, 256>, dim3(grid), dim3(BlkBwdCfg<C, 256>::NW * 64), lds, st, a);
@@ -1444,8 +1456,8 @@ static int tail_check(const FnoModelPlan* p, const FnoBlockTail* t, bool backwar
   if (!t) return FNO_OK;
   const FnoModelDesc& d = p->d;
   if (d.Cin != 0 || d.Cout != 0 || d.n_layers != 1) return fail(FNO_EUNSUPPORTED, "block tail: one-layer block stacks only");
-  if (!g_gemm_x3 || p->NPX != 128 || p->loose || !row_fast_ok(p->g, d.C))
-    return fail(FNO_EUNSUPPORTED, "block tail: split-precision GEMM mode, 32 / 64 channels, rows of 32 / 64 / 128 floats");
+  if (p->NPX != 128 || p->loose || !row_fast_ok(p->g, d.C))
+    return fail(FNO_EUNSUPPORTED, "block tail: 32 / 64 channels, rows of 32 / 64 / 128 floats");
   if (t->drop_p < 0.f || t->drop_p >= 1.f) return fail(FNO_EINVAL, "block tail: dropout rate %g outside [0, 1)", (double)t->drop_p);
   if (t->drop_p > 0.f && !t->drop_seed) return fail(FNO_EINVAL, "block tail: dropout needs the two seed words (device pointer)");
   if (backward && t->relu_out && !t->y) return fail(FNO_EINVAL, "block tail: the backward of a ReLU tail needs the forward's output");
@@ -2470,40 +2482,52 @@ static int proj_check(int B, int C, int HID, int CO, size_t PW) {
   LAUNCHCHK(pw_check(B, C, PW));
   if (HID != 128 && HID != 256) return fail(FNO_EUNSUPPORTED, "projection: hidden width 128 or 256 (got %d)", HID);
   if (CO < 1 || CO > PROJ_MAXCO) return fail(FNO_EUNSUPPORTED, "projection: 1..%d output channels (got %d)", PROJ_MAXCO, CO);
-  if (!g_gemm_x3) return fail(FNO_EUNSUPPORTED, "projection entry points need the split-precision GEMM mode");
   return FNO_OK;
 }
 extern "C" size_t fno_projection_workspace_bytes(int C, int hidden) {
   if ((C != 32 && C != 64) || (hidden != 128 && hidden != 256)) return 0;
   return carve_proj(C, hidden, nullptr, 0).total;
 }
+// exact-fp32 projection kernels (k_projection.h): LDS of k_proj_fwd / k_proj_bwd at 128-pixel tiles
+static size_t proj_fwd_f32_lds(int C, int HID, int NCO) {
+  return ((size_t)C * 132 + HID + NCO * HID + NCO * 128 + (size_t)HID * (C + 1)) * 4;
+}
+static size_t proj_bwd_f32_lds(int C, int HID, int NCO) {
+  const int pitch = 132;          // mirrors the constexpr W1LDS / DBUF choices of k_proj_bwd
+  const size_t small = ((size_t)NCO * 128 + HID + NCO * HID) * 4;
+  const size_t w1b = (size_t)HID * (C + 1) * 4;
+  const bool w1lds = (size_t)(C + 64) * pitch * 4 + small + w1b <= 160 * 1024;
+  const bool dbuf = (size_t)(C + 128) * pitch * 4 + small + (w1lds ? w1b : 0) <= 160 * 1024;
+  return (size_t)(C + (dbuf ? 128 : 64)) * pitch * 4 + small + (w1lds ? w1b : 0);
+}
 template <int C, int HID, bool RELU>
 static int proj_fwd_launch(hipStream_t st, int grid, const ProjFwdArgs& a) {
+  if (!g_gemm_x3)
+    return GT(1), launch("k_proj_fwd", k_proj_fwd<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), proj_fwd_f32_lds(C, HID, 1), st, a);
   const size_t lds = (size_t)3 * 128 * (C + 8) * 2 + (size_t)(HID / 32) * (C / 16) * 3 * 64 * 16 + (size_t)(HID + HID + 128) * 4;
   return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), lds, st, a);
 }
 template <int C, int HID, bool RELU>
 static int proj_bwd_launch(hipStream_t st, int grid, const ProjBwdArgs& a) {
-  // (the standalone head is split-precision in both GEMM modes: its exact-fp32 form is k_proj_bwd of the model path)
+  if (!g_gemm_x3)      // exact-fp32 mode: the first-generation kernel
+    return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), proj_bwd_f32_lds(C, HID, 1), st, a);
   return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, HID, RELU>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
 }
 // 2..PROJ_MAXCO output channels (PlanePredHead, pinobserver.py:257-273: fc2 -> out_dim * plane_num): the forward kernel with
-// PROJ_MAXCO output rows, the backward on the exact-fp32 first-generation kernel (the split-precision ones are built for one)
+// PROJ_MAXCO output rows (split-precision or exact fp32 by the GEMM mode), the backward on the exact-fp32 first-generation
+// kernel in both modes (the split-precision ones are built for one)
 template <int C, int HID>
 static int proj_fwd_launch_mo(hipStream_t st, int grid, const ProjFwdArgs& a) {
   constexpr int NCO = PROJ_MAXCO;
+  if (!g_gemm_x3)
+    return GT(1), launch("k_proj_fwd", k_proj_fwd<C, HID, 128, NCO>, dim3(grid), dim3(512), proj_fwd_f32_lds(C, HID, NCO), st, a);
   const size_t lds = (size_t)3 * 128 * (C + 8) * 2 + (size_t)(HID / 32) * (C / 16) * 3 * 64 * 16 + (size_t)(HID + NCO * HID + NCO * 128) * 4;
   return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, HID, 128, NCO, false>, dim3(grid), dim3(512), lds, st, a);
 }
 template <int C, int HID>
 static int proj_bwd_launch_mo(hipStream_t st, int grid, const ProjBwdArgs& a) {
-  constexpr int NCO = PROJ_MAXCO, pitch = 132;          // mirrors the constexpr W1LDS / DBUF choices of k_proj_bwd
-  const size_t small = ((size_t)NCO * 128 + HID + NCO * HID) * 4;
-  const size_t w1b = (size_t)HID * (C + 1) * 4;
-  const bool w1lds = (size_t)(C + 64) * pitch * 4 + small + w1b <= 160 * 1024;
-  const bool dbuf = (size_t)(C + 128) * pitch * 4 + small + (w1lds ? w1b : 0) <= 160 * 1024;
-  const size_t lds = (size_t)(C + (dbuf ? 128 : 64)) * pitch * 4 + small + (w1lds ? w1b : 0);
-  return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, NCO>, dim3(grid), dim3(512), lds, st, a);
+  constexpr int NCO = PROJ_MAXCO;
+  return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, NCO>, dim3(grid), dim3(512), proj_bwd_f32_lds(C, HID, NCO), st, a);
 }
 static int proj_act_check(int hidden, int act) {
   if (act != FNO_ACT_GELU && act != FNO_ACT_RELU) return fail(FNO_EINVAL, "projection: hidden_act %d (FNO_ACT_GELU or FNO_ACT_RELU)", act);
@@ -2546,11 +2570,12 @@ extern "C" int fno_projection_backward_act(int B, int C, int hidden, int Cout, s
   ProjWs w = carve_proj(C, hidden, ws, ws_bytes);
   if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
   hipStream_t st = (hipStream_t)stream;
-  if (Cout == 1) LAUNCHCHK(pack_w1_x3(st, w1, w.wa1, w.wa3, hidden, C, true));
+  const bool split = Cout == 1 && g_gemm_x3;      // k_proj_bwd_t reads W1 as split-precision fragments
+  if (split) LAUNCHCHK(pack_w1_x3(st, w1, w.wa1, w.wa3, hidden, C, true));
   ProjBwdArgs pb;
   memset(&pb, 0, sizeof(pb));
   pb.x = x; pb.dy = dy; pb.w1 = w1; pb.b1 = b1; pb.w2 = w2; pb.gout = dx;
-  if (Cout == 1) { pb.wa1 = w.wa1; pb.wa3 = w.wa3; }
+  if (split) { pb.wa1 = w.wa1; pb.wa3 = w.wa3; }
   pb.dw1_part = w.dw1_part; pb.db1_part = w.db1_part; pb.dw2_part = w.dw2_part;
   pb.PW = (int)PW; pb.W = 128; pb.P = (int)(PW / 128); pb.CO = Cout;
   pb.tiles_per_plane = (int)(PW / 128); pb.ntiles = B * pb.tiles_per_plane;

@@ -70,7 +70,10 @@ struct BlkBwdCfg {
   static_assert(NW % TILES == 0 && KSPLIT >= 1, "C <= NPX required");
 };
 
-template <int C, int NPX>
+// DROPK: the spectral branch saw drop(x) in the forward pass (rno.py:98): the K-extension part of dx is accumulated first and
+// multiplied by the regenerated dropout scale (the same drop_cfg hash as the forward's row pass and k_block_bwd_t<.., DROPK>),
+// then W^T g is accumulated on top of it.
+template <int C, int NPX, bool DROPK = false>
 __global__ void __launch_bounds__((C / 32) * (NPX / 32) * 64, FNO_OCC_BB) k_block_bwd(BlkBwdArgs a) {
   using Cfg = BlkBwdCfg<C, NPX>;
   constexpr int NTN = Cfg::NTN, MT = Cfg::MT, NW = Cfg::NW, TILES = Cfg::TILES, KSPLIT = Cfg::KSPLIT;
@@ -161,9 +164,21 @@ __global__ void __launch_bounds__((C / 32) * (NPX / 32) * 64, FNO_OCC_BB) k_bloc
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    if constexpr (DROPK) {
+      if (a.zg) {
+        const float* zr = zs + (((n0 / a.W) * a.K2in) * C + mt * 32 + l31) * 2 + half;
+        const float* tv = tinv_s + half * a.W + n0 % a.W + l31;
+#pragma unroll 2
+        for (int s = 0; s < a.K2in; ++s) acc = mfma32(zr[s * C * 2], tv[2 * s * a.W], acc);
+        const DropCfg dc = drop_cfg(a.drop_seed, a.drop_p);
+        const size_t e0 = ((size_t)b * C + mt * 32 + 4 * half) * a.PW + px0 + n0 + l31;      // acc[r] <-> row acc_row32(r, half)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] *= drop_scale(dc, e0 + (size_t)((r & 3) + 8 * (r >> 2)) * a.PW);
+      }
+    }
 #pragma unroll
     for (int s = 0; s < KS; ++s) acc = mfma32(afrag[s], gs[(2 * s + half) * PITCH + n0 + l31], acc);
-    if (a.zg) {
+    if (a.zg && !DROPK) {
       const float* zr = zs + (((n0 / a.W) * a.K2in) * C + mt * 32 + l31) * 2 + half;
       const float* tv = tinv_s + half * a.W + n0 % a.W + l31;
 #pragma unroll 2

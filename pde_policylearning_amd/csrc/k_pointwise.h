@@ -69,8 +69,11 @@ static inline size_t pw_fwd_lds_bytes(int cin, int cout, int npx, int W, int K2i
   return fl * 4;
 }
 
-template <int CIN, int COUT, int NPX>
-__global__ void __launch_bounds__((COUT / 32) * (NPX / 32) * 64, CIN <= 4 ? (COUT * NPX >= 64 * 128 ? 2 : 4) : FNO_OCC_PW) k_pw_fwd(PwFwdArgs a) {
+// RELU: the stored tensor is max(u, 0) (the exact-fp32 form of k_pw_fwd_x3<.., RELU = true>: one-layer stacks with a ReLU tail);
+// those ask for 2 waves per SIMD (256 VGPRs): at FNO_OCC_PW the 64-channel tile spills 48 bytes per lane
+template <int CIN, int COUT, int NPX, bool RELU = false>
+__global__ void __launch_bounds__((COUT / 32) * (NPX / 32) * 64, CIN <= 4 ? (COUT * NPX >= 64 * 128 ? 2 : 4) : RELU ? 2 : FNO_OCC_PW)
+k_pw_fwd(PwFwdArgs a) {
   constexpr int NTN = NPX / 32;          // pixel sub-tiles
   constexpr int MT = COUT / 32;          // channel sub-tiles
   constexpr int NW = MT * NTN;
@@ -157,6 +160,10 @@ __global__ void __launch_bounds__((COUT / 32) * (NPX / 32) * 64, CIN <= 4 ? (COU
         const float* ap = a.add + ((size_t)b * COUT + mt * 32 + 4 * half) * a.PW + px0 + n0 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] += ap[(size_t)((r & 3) + 8 * (r >> 2)) * a.PW];
+      }
+      if constexpr (RELU) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = acc[r] < 0.f ? 0.f : acc[r];      // (NaN stays NaN, as torch's relu)
       }
       if (up) {
 #pragma unroll

@@ -26,11 +26,12 @@ struct ProjFwdArgs {
 
 constexpr int PROJ_MAXCO = 4;   // largest supported projection output width
 
+// RELU: hidden activation max(h, 0) instead of GELU (RNO2d's regressor head, rno.py:171-175), as k_proj_fwd_x3<.., RELU>.
 // wave (hm, nt): hidden rows [64*ch + 32*hm, +32) of every chunk ch, pixels [32*nt, +32).
 // W1 stays in LDS for the lifetime of the (persistent) workgroup, rows padded to C+1 floats so
 // that both the row-per-lane fragment reads here and the channel-per-lane reads of the backward
 // kernel are bank-conflict-free; the next tile's activations are prefetched into registers.
-template <int C, int HID, int NPX, int NCO>
+template <int C, int HID, int NPX, int NCO, bool RELU = false>
 __global__ void __launch_bounds__(NPX * 4, FNO_OCC_PF) k_proj_fwd(ProjFwdArgs a) {
   constexpr int NTN = NPX / 32;
   constexpr int NW = 2 * NTN;
@@ -88,7 +89,7 @@ __global__ void __launch_bounds__(NPX * 4, FNO_OCC_PF) k_proj_fwd(ProjFwdArgs a)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int ro = (r & 3) + 8 * (r >> 2);
-        const float gl = gelu_f(acc[r] + b1p[ro]);
+        const float gl = RELU ? fmaxf(acc[r] + b1p[ro], 0.f) : gelu_f(acc[r] + b1p[ro]);
 #pragma unroll
         for (int co = 0; co < NCO; ++co) ysum[co] = fmaf(w2p[co * HID + ro], gl, ysum[co]);
       }
@@ -154,7 +155,8 @@ struct ProjBwdCfg {
 //   --- barrier ---
 //   B   dW1[chunk] += dP1 . a^T  (MFMA, K = pixels) by the wave group that owns this chunk,
 //       while the other group already recomputes the next chunk
-template <int C, int HID, int NPX, int NCO>
+// RELU: the hidden activation is max(h, 0), derivative (h > 0) (as k_proj_bwd_t<.., RELU>)
+template <int C, int HID, int NPX, int NCO, bool RELU = false>
 __global__ void __launch_bounds__(NPX * 4, FNO_OCC_PB) k_proj_bwd(ProjBwdArgs a) {
   // W1 is resident in LDS (rows padded to C+1 floats: conflict-free both for the row-per-lane
   // fragments of the recompute and the channel-per-lane fragments of the dx product); the dP1
@@ -268,7 +270,11 @@ __global__ void __launch_bounds__(NPX * 4, FNO_OCC_PB) k_proj_bwd(ProjBwdArgs a)
 #pragma unroll
           for (int co = 0; co < NCO; ++co) t = fmaf(w2p[co * HID + ro], dyl[co], t);
           float gl, dg;
-          gelu_both(acc[r] + b1p[ro], gl, dg);
+          if constexpr (RELU) {
+            const float h = acc[r] + b1p[ro];
+            gl = fmaxf(h, 0.f);
+            dg = h > 0.f ? 1.f : 0.f;
+          } else gelu_both(acc[r] + b1p[ro], gl, dg);
           const float dp = dg * t;
           acc[r] = dp;
           dpp[ro * PITCH] = dp;

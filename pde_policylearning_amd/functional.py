@@ -681,8 +681,8 @@ def blocks_supported(x, n_layers=1, modes=None, norm="backward", gelu_mask=0):
 
 def block_tail_supported(x, modes, norm):
     """Shapes fno_block_tail covers: what one fused block covers on whole rows (32 / 64 channels, rows of 32 / 64 / 128
-    floats tiling 128-pixel tiles), split-precision GEMM mode."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _lib.lib().fno_get_gemm_mode() == 1):
+    floats tiling 128-pixel tiles), in either GEMM mode."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     w, pw = x.shape[-1], x.shape[-1] * x.shape[-2]
     if not (x.shape[1] in (32, 64) and w in (32, 64, 128) and pw % 128 == 0):
@@ -1343,7 +1343,7 @@ PROJ_MAXCO = 4        # k_projection.h
 def projection_supported(x, hidden, cout, act="gelu"):
     return (pointwise_supported(x) and hidden in ((128, 256) if act == "gelu" else (256,))
             and (cout == 1 or (act == "gelu" and 1 <= cout <= PROJ_MAXCO))
-            and act in _ACT_CODES and _lib.lib().fno_get_gemm_mode() == 1)
+            and act in _ACT_CODES)
 
 
 _ACT_CODES = {"gelu": 0, "relu": 1}      # FNO_ACT_* (include/fnoengine.h)
