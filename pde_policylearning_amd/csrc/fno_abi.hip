@@ -1435,7 +1435,9 @@ template <int C>
 static int launch_pbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const ProjBwdArgs& a) {
   if (a.wa1 && a.amax && use_pbwd_t(C, a.CO, p->NPX))      // two fp16 terms: same LDS carve with two planes per image
     return GT(2), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false, 2>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
-  if (a.wa1 && use_pbwd_t(C, a.CO, p->NPX))
+  // three bf16 terms take a third plane per image: with the gradient's row DFT fused (x1g, more than 16 kept last-dim bins at
+  // 64 channels) that carve outgrows LDS, and the first-generation kernel (same x1g epilogue, same partial slabs) serves instead
+  if (a.wa1 && use_pbwd_t(C, a.CO, p->NPX) && pbwd_t_lds(C, a) <= 160 * 1024)
     return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
   return a.CO == 1 ? launch_pbwd_cn<C, 1>(p, st, grid, a) : launch_pbwd_cn<C, PROJ_MAXCO>(p, st, grid, a);
 }
