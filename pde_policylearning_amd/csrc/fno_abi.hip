@@ -53,17 +53,15 @@ extern "C" int fno_version(void) { return FNO_VERSION; }
 // GEMM arithmetic of the fused model path: 1 = 3-term bf16 split on the matrix cores (fp32-grade,
 // default), 0 = fp32 MFMA.  FNO_GEMM_F32=1 in the environment selects 0 at load time.
 static int g_gemm_x3 = []() { const char* e = getenv("FNO_GEMM_F32"); return (e && e[0] == '1') ? 0 : 1; }();
-// Two-term fp16 channel GEMMs (fno_dev.h "h2": half the matrix-pipe work of the three-term bf16 split) wherever a kernel has
-// the variant and its operands' magnitude bounds are known (the A/B switches of rounds 3-5 - FNO_NO_H2, FNO_NO_H2_BLOCKS,
-// FNO_NO_H2_FWD_BLOCKS - are retired: the three-term kernels remain as what runs when no bound is known)
-static constexpr int g_h2 = 1, g_h2_blocks = 1, g_h2_fwd_blocks = 1;
+// In the split mode, two-term fp16 channel GEMMs (fno_dev.h "h2": half the matrix-pipe work of the three-term bf16 split) run
+// wherever a kernel has the variant and its operands' magnitude bounds are known; the three-term kernels are what runs when
+// no bound is known.
 extern "C" void fno_set_gemm_mode(int x3) { g_gemm_x3 = x3 ? 1 : 0; }
 extern "C" int fno_get_gemm_mode(void) { return g_gemm_x3; }
 extern "C" const char* fno_last_error(void) { return g_err.c_str(); }
 // mode contraction on the fp32 matrix cores (default) or the VALU kernels (FNO_MODE_GEMM_VALU=1 / fno_set_mode_gemm(0)):
 // an A/B switch for profiling and for the parity tests, which run both
 static int g_mode_mfma = []() { const char* e = getenv("FNO_MODE_GEMM_VALU"); return (e && e[0] == '1') ? 0 : 1; }();
-static constexpr int g_mode_gemv = 1;      // weight-streaming kernels for tiny batches (config 5 as named: 59.5 -> 52.3 ms, round 1)
 extern "C" void fno_set_mode_gemm(int mfma) { g_mode_mfma = mfma ? 1 : 0; }
 extern "C" int fno_get_mode_gemm(void) { return g_mode_mfma; }
 
@@ -153,7 +151,7 @@ static int launch(const char* name, void (*kern)(KArgs...), dim3 grid, dim3 bloc
   g_terms_next = 0;
   if (grid.x == 0 || grid.y == 0 || grid.z == 0) return FNO_OK;
   if (lds > 64 * 1024) {
-    if (lds > 160 * 1024) return fail(FNO_EUNSUPPORTED, "%s needs %zu bytes of LDS (160 KB per CU)", name, lds);
+    if (lds > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "%s needs %zu bytes of LDS (160 KB per CU)", name, lds);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
@@ -471,7 +469,7 @@ static int mode_gemm(hipStream_t st, const float* x, const float* w, float* out,
                      int conj_w, int nm = 1, size_t x_ms = 0, size_t w_ms = 0, size_t o_ms = 0, int trans_w = 0) {
   if (Cout > 256) return fail(FNO_EUNSUPPORTED, "channels > 256");
   if (trans_w && !mode_gemm_members_ok(Cin, Cout)) return fail(FNO_EUNSUPPORTED, "transposed-weight contraction needs the matrix-core kernels");
-  if (g_mode_mfma && g_mode_gemv && nm == 1 && B <= 4 && Cin <= 64 && Cout <= 64 && (long)Ktot * Cin * Cout >= (1L << 21)) {
+  if (g_mode_mfma && nm == 1 && B <= 4 && Cin <= 64 && Cout <= 64 && (long)Ktot * Cin * Cout >= (1L << 21)) {
     // tiny batch, many modes: a stream over the weights (k_mode_gemv*); x / out hold B samples back to back
     const float2 *xx = (const float2*)x, *ww = (const float2*)w;
     float2* oo = (float2*)out;
@@ -525,7 +523,7 @@ static int mode_gemm_dw(hipStream_t st, const float* x, const float* g, float* d
                         int nm = 1, size_t x_ms = 0, size_t g_ms = 0, size_t d_ms = 0) {
   if (Cout > 256) return fail(FNO_EUNSUPPORTED, "channels > 256");
   if (nm > 1 && !mode_gemm_members_ok(Cin, Cout)) return fail(FNO_EUNSUPPORTED, "batched mode contraction needs the matrix-core kernels");
-  if (g_mode_mfma && g_mode_gemv && nm == 1 && B <= 4 && Cin <= 64 && Cout <= 64 && (long)Ktot * Cin * Cout >= (1L << 21)) {
+  if (g_mode_mfma && nm == 1 && B <= 4 && Cin <= 64 && Cout <= 64 && (long)Ktot * Cin * Cout >= (1L << 21)) {
     const dim3 grid((Ktot + 3) / 4), blk(256);
     const float2 *xx = (const float2*)x, *gg = (const float2*)g;
     float2* dd = (float2*)dw;
@@ -652,7 +650,7 @@ extern "C" int fno_spec_plan_create(const FnoSpecDesc* d, FnoSpecPlan** out) {
     rc = fail(FNO_EUNSUPPORTED, "channels must be in [1, 256]");
   if (rc == FNO_OK) {
     const size_t lds1 = (size_t)std::max(d->Cin, d->Cout) * (p->g.W + 1) * 4;
-    if (lds1 > 160 * 1024) rc = fail(FNO_EUNSUPPORTED, "row tile C*(W+1)*4=%zu exceeds LDS", lds1);
+    if (lds1 > FNO_LDS_MAX) rc = fail(FNO_EUNSUPPORTED, "row tile C*(W+1)*4=%zu exceeds LDS", lds1);
   }
   if (rc == FNO_OK) rc = make_tables(p->g, p->t);
   if (rc == FNO_OK && d->input_gelu && !row_chan_ok(p->g, p->t.K2P, d->Cin))
@@ -754,7 +752,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
       if (rb >= q && rb * g.W >= 256) {
         const size_t lds = ((size_t)8 * rowdft4_pitch(rb * g.W) + 4 + (size_t)2 * K2P * rowdft4_pitch((g.W + 3) & ~3)) * 4;
         const int ntiles = B * (C / 8) * (g.P / rb);
-        const int per_cu = std::max(1, (int)std::min<size_t>(4, (160 * 1024) / lds));
+        const int per_cu = std::max(1, (int)std::min<size_t>(4, FNO_LDS_MAX / lds));
         const dim3 grid(std::min(ntiles, per_cu * dev_ncu())), blk(256);
 #define ROWDFT_CHAN4(K) launch("k_rowdft_chan4", k_rowdft_chan4<K>, grid, blk, lds, st, x, (float2*)x1, tfwd, C, g.P, g.W, g.Klast, rb, ntiles, act_in, 16 * g.NJ)
         if (K2P == 8) return ROWDFT_CHAN4(8);
@@ -771,7 +769,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
       while (rb > 1 && (long)B * ((g.P + rb - 1) / rb) < 4L * dev_ncu()) rb >>= 1;
       const size_t lds = (size_t)C * (rb * g.W + 1) * 4;
       const int ntiles = B * ((g.P + rb - 1) / rb);
-      const int per_cu = std::max(1, (int)std::min<size_t>(4, (160 * 1024) / lds));
+      const int per_cu = std::max(1, (int)std::min<size_t>(4, FNO_LDS_MAX / lds));
       const dim3 grid(std::min(ntiles, per_cu * dev_ncu())), blk(256);
       (void)cg;
 #define ROWDFT_CHAN(K) launch("k_rowdft_chan", k_rowdft_chan<K, 16>, grid, blk, lds, st, x, (float2*)x1, tT, C, g.P, g.W, g.Klast, rb, ntiles, act_in)
@@ -786,7 +784,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
   int rb = 8;
   while (rb > 1 && ((size_t)C * (rb * g.W + 1) + (size_t)g.W * 2 * k2e) * 4 > 64 * 1024) rb >>= 1;
   const size_t lds = ((size_t)C * (rb * g.W + 1) + (size_t)g.W * 2 * k2e) * 4;
-  if (lds > 160 * 1024) return fail(FNO_EUNSUPPORTED, "row tile of %d channels x %d floats exceeds LDS", C, g.W);
+  if (lds > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "row tile of %d channels x %d floats exceeds LDS", C, g.W);
   return launch("k_rowdft_generic", k_rowdft_generic, dim3(B * ((g.P + rb - 1) / rb)), dim3(256), lds, st, x, (float2*)x1,
                 tfwd, C, g.P, g.W, g.Klast, rb);
 }
@@ -813,7 +811,7 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
     if (C % 32 == 0 && g.W >= 32 && g.W <= 128) {   // truncated inverse DFT on the fp32 matrix cores (short rows would waste the 32-column tiles)
       const size_t tabb = (size_t)2 * g.Klast * (((g.W + 31) / 32) * 32 + 4) * 4;
       const size_t ldsf = (size_t)C * (ROWFLAT_CH + 4) * 4 + tabb;
-      if (g.PW % 4 == 0 && g.W < ROWFLAT_CH && ldsf <= 160 * 1024 && B <= 65535) {     // whole-line tiles of the flattened planes
+      if (g.PW % 4 == 0 && g.W < ROWFLAT_CH && ldsf <= FNO_LDS_MAX && B <= 65535) {     // whole-line tiles of the flattened planes
         const dim3 gridf((g.PW + ROWFLAT_CH - 1) / ROWFLAT_CH, B);
         constexpr int flat_threads = 512;
         if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_flat_mfma<8>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
@@ -824,13 +822,13 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
       while (rbm > 1 && (size_t)C * (rbm * g.W + 1) * 4 + tabb > 80 * 1024) rbm >>= 1;
       const size_t lds3 = (size_t)C * (rbm * g.W + 1) * 4 + tabb;
       const dim3 gridm(B * ((g.P + rbm - 1) / rbm));
-      if (lds3 <= 160 * 1024) {
+      if (lds3 <= FNO_LDS_MAX) {
         if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_chan_mfma<8>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
         if (K2P == 16) return launch("k_rowidft_chan", k_rowidft_chan_mfma<16>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
         return launch("k_rowidft_chan", k_rowidft_chan_mfma<32>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
       }
     }
-    if (lds2 <= 160 * 1024) {
+    if (lds2 <= FNO_LDS_MAX) {
       const dim3 grid(B * ((g.P + rb - 1) / rb));
       const dim3 blk(std::min(256, ((rb * C + 63) / 64) * 64));
       if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_chan<8>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
@@ -841,7 +839,7 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
   int rb = 8;
   auto need = [&](int r) { return (((size_t)2 * g.Klast * g.W + 1) & ~(size_t)1) * 4 + (size_t)r * g.Klast * C * 8; };
   while (rb > 1 && need(rb) > 64 * 1024) rb >>= 1;
-  if (need(rb) > 160 * 1024) return fail(FNO_EUNSUPPORTED, "row spectra of %d channels x %d bins exceed LDS", C, g.Klast);
+  if (need(rb) > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "row spectra of %d channels x %d bins exceed LDS", C, g.Klast);
   const dim3 grid(B * ((g.P + rb - 1) / rb));
   // (<= 32 kept bins always fit one of the tile / lanes-as-channels kernels above: plan creation refuses rows whose channel tile
   // exceeds LDS; what is left for the generic kernel is more than 32 bins, its run-time-bound form)
@@ -950,12 +948,17 @@ struct FnoModelPlan {
 };
 
 static const int kHID = 256;
-// magnitude bounds kept at the end of the forward's `saved` buffer (fno_dev.h "h2"; tests/test_hostile_ranges_gpu.py checks each):
-// [7] max |x| of the model input (k_lift_rowdft), [8] the bound of |u_0| block 0's forward derives from it (fused lifting:
-// lift_u0_bound), [8 + l] max |u_l| as stored (l >= 1), [32 + l] max |dL/du_l| (the backward's gradient chain, l >= 1),
-// [60] max |dy|, [61] max |W1|, [62] max |w2| (the projection backward's scalars, bwd_b = amax + 59); the others stay 0
-static_assert(8 + FNO_MAX_LAYERS + 1 <= 32 && 32 + FNO_MAX_LAYERS + 1 <= 59, "bound slots: [8, 32) forward |u_l|, [32, 59) backward |g_l|, [59, 63) projection scalars");
+// Magnitude bounds kept at the end of the forward's `saved` buffer (fno_dev.h "h2"): kNAmax floats, the slots not named here
+// stay 0.  tests/test_hostile_ranges_gpu.py checks every slot by its NUMBER - the independent statement of this map.
 static const int kNAmax = 64;
+static const int kBndX = 7;                                    // max |x| of the model input (k_lift_rowdft)
+// max |u_l| as stored (l >= 1); l = 0: the bound of |u_0| block 0's forward derives from max |x| (fused lifting: lift_u0_bound)
+static constexpr int bnd_u(int l) { return 8 + l; }
+static constexpr int bnd_g(int l) { return 32 + l; }           // max |dL/du_l| (the backward's gradient chain, l >= 1)
+// the projection backward's scalars: max |dy|, max |W1|, max |w2| (the kernels read them as amax[1..3] behind kBndProj)
+static const int kBndProj = 59, kBndDy = kBndProj + 1, kBndW1 = kBndProj + 2, kBndW2 = kBndProj + 3;
+static_assert(kBndX < bnd_u(0) && bnd_u(FNO_MAX_LAYERS) < bnd_g(0) && bnd_g(FNO_MAX_LAYERS) < kBndProj && kBndW2 < kNAmax,
+              "bound slots: [8, 32) forward |u_l|, [32, 59) backward |g_l|, [59, 63) projection scalars");
 // persistent-grid size per CU of the forward kernels (= workgroups that fit: registers / LDS)
 #ifndef FNO_GRID_LIFT
 #define FNO_GRID_LIFT 3
@@ -966,9 +969,6 @@ static const int kNAmax = 64;
 #ifndef FNO_GRID_BWD
 #define FNO_GRID_BWD 1   // persistent workgroups per CU of the backward kernels: their LDS footprint allows one resident
                          // workgroup, and every extra one adds a partial slab to reduce
-#endif
-#ifndef FNO_BBWD_X3
-#define FNO_BBWD_X3 1
 #endif
 #ifndef FNO_GRID_PWX
 #define FNO_GRID_PWX 4
@@ -1014,8 +1014,10 @@ extern "C" int fno_model_plan_create(const FnoModelDesc* d, FnoModelPlan** out) 
     }
     if (rc == FNO_OK && p->g.NJ > 4) rc = fail(FNO_EUNSUPPORTED, "too many last-dim modes (%d)", p->g.Klast);
     if (rc == FNO_OK) {
-      // every kernel of the plan must fit its tile + twiddle tables in 160 KB of LDS (256-pixel tiles with many
-      // kept last-dim modes do not: such shapes take the unfused composition)
+      // every kernel of the plan must fit its tile + twiddle tables in FNO_LDS_MAX (256-pixel tiles with many kept last-dim
+      // modes do not: such shapes take the unfused composition).  The sums below approximate blk_bwd_lds_bytes,
+      // blk_bwd_t_lds_bytes (and its loose form), pw_fwd_x3_lds_bytes and pw_fwd_lds_bytes of the kernel headers; they are kept
+      // as they are because which plans are accepted is ABI behaviour.
       const Geom& g = p->g;
       const int npx = p->NPX, C = d->C;
       const size_t tz = ((size_t)2 * g.Klast * g.W + (size_t)(npx / g.W + (p->loose ? 2 : 0)) * g.Klast * C * 2) * 4;   // inverse table + Z rows
@@ -1024,16 +1026,16 @@ extern "C" int fno_model_plan_create(const FnoModelDesc* d, FnoModelPlan** out) 
       const size_t xin = d->Cin > 0 ? (size_t)8 * (npx + 4) * 4 : 0;                                // block 0: lifting rows
       const size_t bbwd_f32 = (size_t)2 * C * (npx + 4) * 4 + tz + std::max(xin, many ? tf : (size_t)0);
       const size_t bbwd_x3 = (size_t)6 * C * (npx + 8) * 2 + (size_t)C * (npx + 4) * 4 + tz + std::max(xin, many ? tf : (size_t)0);
-      const size_t bbwd = (npx == 128 && bbwd_x3 <= 160 * 1024) ? bbwd_x3 : bbwd_f32;
+      const size_t bbwd = (npx == 128 && bbwd_x3 <= FNO_LDS_MAX) ? bbwd_x3 : bbwd_f32;
       const size_t pwx3 = (size_t)3 * npx * (C + 8) * 2 + tz + (many ? tf : 0), pwf32 = (size_t)C * (npx + 4) * 4 + tz + (many ? tf : 0);
       // loose rows exist for the split-precision kernels only; their backward kernel can apply the K-extension in chunks
       // of kept modes, so one mode's rows + table column must fit next to the GEMM images
       const size_t bbwd_x3_1 = (size_t)6 * C * (npx + 8) * 2 + (size_t)C * (npx + 4) * 4 +
                                ((size_t)2 * g.W + (size_t)(npx / g.W + 2) * C * 2) * 4;
-      if (p->loose && (bbwd_x3_1 > 160 * 1024 || pwx3 > 160 * 1024))
+      if (p->loose && (bbwd_x3_1 > FNO_LDS_MAX || pwx3 > FNO_LDS_MAX))
         rc = fail(FNO_EUNSUPPORTED, "loose-row tile of %d channels with %d kept last-dim modes exceeds LDS", C, g.Klast);
       else if (p->loose) { /* fits */ }
-      else if (bbwd > 160 * 1024 || pwx3 > 160 * 1024 || pwf32 > 160 * 1024)
+      else if (bbwd > FNO_LDS_MAX || pwx3 > FNO_LDS_MAX || pwf32 > FNO_LDS_MAX)
         rc = fail(FNO_EUNSUPPORTED, "tile of %d pixels x %d channels with %d kept last-dim modes exceeds LDS", npx, C,
                   g.Klast);
     }
@@ -1120,9 +1122,40 @@ static ModelWs carve_model(const FnoModelPlan* p, int B, void* ws, size_t cap, b
 extern "C" size_t fno_model_workspace_bytes(const FnoModelPlan* p, int B) {
   return carve_model(p, B, nullptr, 0, true, nullptr).total;
 }
-extern "C" size_t fno_model_saved_bytes(const FnoModelPlan* p, int B) {
+// the forward's `saved` buffer: u_0 .. u_L, every layer's truncated input spectrum and packed weights (kept for backward), the
+// magnitude bounds
+// (u[l] = u + l * n_act, hats[l] = hats + l * n_hat; wps [k][i][o] and wpts, the transposed copy [k][o][i]: n_wp floats per layer)
+struct ModelSaved { float *u, *hats, *wps, *wpts, *bounds; size_t total; };
+static ModelSaved carve_saved(const FnoModelPlan* p, int B, const void* saved) {
   const ModelSizes s = model_sizes(p, B);
-  return ((size_t)(p->d.n_layers + 1) * s.n_act + (size_t)p->d.n_layers * (s.n_hat + 2 * s.n_wp) + kNAmax) * sizeof(float);
+  const size_t nl = p->d.n_layers;
+  float* base = (float*)const_cast<void*>(saved);
+  size_t off = 0;
+  auto take = [&](size_t n) { float* q = base ? base + off : nullptr; off += n; return q; };
+  ModelSaved v;
+  v.u = take((nl + 1) * s.n_act);
+  v.hats = take(nl * s.n_hat);
+  v.wps = take(nl * s.n_wp);
+  v.wpts = take(nl * s.n_wp);
+  v.bounds = take(kNAmax);
+  v.total = off * sizeof(float);
+  return v;
+}
+extern "C" size_t fno_model_saved_bytes(const FnoModelPlan* p, int B) { return carve_saved(p, B, nullptr).total; }
+// the tile geometry PwFwdArgs and BlkBwdArgs carry
+template <typename A>
+static void set_tile_geom(A& a, const Geom& g, const ModelSizes& s, int K2in) {
+  a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = K2in; a.K2out = g.Klast; a.NJ = g.NJ;
+  a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
+}
+// corner tensors of layers lo .. hi -> slots 0 .. hi - lo of the pack / unpack kernels' pointer table
+template <typename CP, typename P>
+static CP corner_ptrs(const Geom& g, P spec_w, int lo, int hi) {
+  CP cp;
+  memset(&cp, 0, sizeof(cp));
+  for (int l = lo; l <= hi; ++l)
+    for (int c = 0; c < (1 << g.nlead); ++c) cp.p[l - lo][c] = (std::remove_reference_t<decltype(cp.p[0][0])>)spec_w[l][c];
+  return cp;
 }
 
 // ---- templated launch dispatch ---------------------------------------------
@@ -1150,7 +1183,7 @@ static int launch_lift(const FnoModelPlan* p, hipStream_t st, int grid, const Pw
 // block 0 of a model with a lifting layer computes u_0 = W_l x + b_l itself (forward on load, backward from the input rows it
 // stages anyway) when both of its kernels are the split-precision 128-pixel ones: u_0 then never travels through HBM
 static bool lift_fused(const FnoModelPlan* p) {
-  return p->d.Cin > 0 && g_gemm_x3 && FNO_BBWD_X3 && p->NPX == 128 && !p->loose;
+  return p->d.Cin > 0 && g_gemm_x3 && p->NPX == 128 && !p->loose;
 }
 // second-generation block forward (k_block_fwd2.h): whole rows in 128-pixel tiles, two workgroups per CU
 template <int C>
@@ -1162,7 +1195,7 @@ static bool blk_fwd_t_ok(const FnoModelPlan* p, const PwFwdArgs& a, size_t* lds)
   if (C == 32) return false;      // 32 channels: k_pw_fwd_x3 is faster with and without a row-DFT epilogue (FNO3d 64^3: 0.298 vs 0.329 ms per launch,
                                   // BASELINE config 1: 11.2 vs 11.7 us)
   *lds = blk_fwd_t_lds_bytes(C, a.W, a.K2in, a.NJ, a.z != nullptr, a.x1 != nullptr);
-  return *lds + 2048 <= 160 * 1024;
+  return *lds + 2048 <= FNO_LDS_MAX;
 }
 // third-generation block forward (k_block_fwd3.h): independent strip waves fed by LDS-DMA.  64 channels, rows of 128 pixels,
 // <= 8 kept last-dim modes either side, two-term fp16 mode, no lifting / ReLU / addend; everything else keeps k_blk_fwd_t.
@@ -1170,60 +1203,62 @@ static bool blk_fwd_t_ok(const FnoModelPlan* p, const PwFwdArgs& a, size_t* lds)
 // fp32 MFMAs).  FNO_BFWD_V2=1 keeps the second generation (A/B arm).
 static const int g_bfwd_v2 = getenv("FNO_BFWD_V2") ? 1 : 0;
 static const int g_zigzag = getenv("FNO_NO_ZIGZAG") ? 0 : 1;      // A/B switch: alternating tile order along the kernel chain
-static bool blk_fwd_s_ok(const FnoModelPlan* p, const PwFwdArgs& a) {
+static bool blk_fwd_s_ok(const FnoModelPlan* p, const PwFwdArgs& a, size_t* lds) {
   if (g_bfwd_v2 || p->NPX != 128 || p->loose || !a.x || !a.u || !a.z || !a.xmax) return false;
-  if (a.W != 128 || a.K2in > 8 || a.relu_out || a.add || (a.lw && a.CL > 4)) return false;
+  if (a.W != 128 || a.K2in < 1 || a.K2in > 8 || a.relu_out || a.add || (a.lw && a.CL > 4)) return false;
   if (a.x1 && (a.NJ != 1 || a.K2out > 8)) return false;
   if ((size_t)a.PW * 4 * 64 >= (size_t)1 << 31) return false;          // 32-bit offsets within one sample
-  return true;
+  *lds = blk_fwd_s_lds_bytes(a.K2out, a.x1 != nullptr);
+  return *lds <= FNO_LDS_MAX;      // (uniformity only: at most 82 KB with K2out <= 8)
 }
-// *ub_published (if given): the launched kernel left the bound of |u_0| at a.ubound (the LIFT variants do when a.xmax is set:
-// lift_u0_bound, fno_dev.h) - the two-term block-0 backward splits u_0 by it, so the host hands it on only when it was written
+// k_blk_fwd_s has every ACT_IN x EPI combination without lifting and every EPI with it (nine instantiations)
+template <bool ACT_IN, bool LIFT>
+static int launch_blk_fwd_s(const char* nm, hipStream_t st, dim3 grid, size_t lds, int epi, const PwFwdArgs& a) {
+  if (epi == 2) return launch(nm, k_blk_fwd_s<ACT_IN, 2, LIFT>, grid, dim3(256), lds, st, a);
+  if (epi == 1) return launch(nm, k_blk_fwd_s<ACT_IN, 1, LIFT>, grid, dim3(256), lds, st, a);
+  return launch(nm, k_blk_fwd_s<ACT_IN, 0, LIFT>, grid, dim3(256), lds, st, a);
+}
+// A block's forward in the split mode.  In this order:
+//   k_blk_fwd_s   two fp16 terms     where k_blk_fwd_t is eligible AND blk_fwd_s_ok (the bound of |x| is known, ...)
+//   k_blk_fwd_t   three bf16 terms   64 channels, whole rows in 128-pixel tiles (blk_fwd_t_ok), the listed flag combinations
+//   k_pw_fwd_x3   three bf16 terms   everything else (every option is a run-time argument)
+// *ub_published (if given): the launched kernel left the bound of |u_0| at a.ubound.  The LIFT variant of each family does when
+// a.xmax is set (lift_u0_bound, fno_dev.h) - the two-term block-0 backward splits u_0 by it, so the host hands it on only when it
+// was written.
 template <int C>
-static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a_in, bool* ub_published = nullptr) {
-  size_t lds2 = 0;
-  const PwFwdArgs& a = a_in;
-  if (ub_published) *ub_published = false;
-  const bool ub = a_in.lw && a_in.ubound && a_in.xmax;      // what the LIFT variants below publish
+static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a, bool* ub_published = nullptr) {
+  bool unused = false;
+  bool& published = ub_published ? *ub_published : unused;
+  published = false;
+  const bool lift_ub = a.lw && a.ubound && a.xmax;      // what a LIFT variant publishes
   // profile label: block 0 with the lifting recomputed reads the <= 4-channel model input instead of u_0 (bench.py prices it so)
-  const char* nm = a_in.lw ? "k_pw_fwd_block0" : "k_pw_fwd_block";
+  const char* nm = a.lw ? "k_pw_fwd_block0" : "k_pw_fwd_block";
   // (64 channels only: blk_fwd_t_ok refuses 32, where k_pw_fwd_x3 measured faster - `if constexpr` so that the 33 instantiations
   // nothing can launch are not compiled: tools/kernel_coverage.py, round 5)
-  if constexpr (C == 64) if (blk_fwd_t_ok<C>(p, a_in, &lds2)) {
+  size_t lds_t = 0, lds_s = 0;
+  if constexpr (C == 64) if (blk_fwd_t_ok<C>(p, a, &lds_t)) {
     const dim3 g2(std::min(a.ntiles, 2 * p->ncu)), blk((C / 32) * 2 * 64);
     const int epi = a.x1 ? (a.act_out ? 2 : 1) : 0;
     // two workgroups per CU: the one dispatched first gets the larger share of the CU's tiles (pair_share, fno_dev.h)
     constexpr int share_bf = 20;      // of 32 (16 = even): 2.111 / 2.114 / 2.103 / 2.110 ms per step at 18 / 16 / 20 / 22 (round 6, one box)
-    PwFwdArgs a = a_in;
-    a.share32 = ((int)g2.x == 2 * p->ncu) ? share_bf : 0;
-    // (template flags: LIFT, RELU, ACT_IN, EPI, ADD - k_block_fwd2.h; other combinations keep k_pw_fwd_x3)
-    const int kz = a.z ? (2 * a.K2in + 15) / 16 : 0;
-    const bool h2k = g_h2 && g_h2_blocks && g_h2_fwd_blocks && a.xmax && kz > 0 && !a.add && !a.relu_out;      // two-term fp16 variants: the model path's combinations
-    if (h2k && blk_fwd_s_ok(p, a)) {
-      const size_t lds3 = blk_fwd_s_lds_bytes(a.K2out, a.x1 != nullptr);
-      const dim3 g3(std::min(a.ntiles, 2 * p->ncu));
-      a.share32 = ((int)g3.x == 2 * p->ncu) ? share_bf : 0;
-#define BF3(AIN_, EPI_) return GT(2), launch(nm, k_blk_fwd_s<AIN_, EPI_>, g3, dim3(256), lds3, st, a)
-      if (a.lw) {
-        if (ub_published) *ub_published = ub;
-        if (epi == 2) return GT(2), launch(nm, k_blk_fwd_s<false, 2, true>, g3, dim3(256), lds3, st, a);
-        if (epi == 1) return GT(2), launch(nm, k_blk_fwd_s<false, 1, true>, g3, dim3(256), lds3, st, a);
-        return GT(2), launch(nm, k_blk_fwd_s<false, 0, true>, g3, dim3(256), lds3, st, a);
-      }
-      if (a.act_in) { if (epi == 2) BF3(true, 2); if (epi == 1) BF3(true, 1); BF3(true, 0); }
-      if (epi == 2) BF3(false, 2);
-      if (epi == 1) BF3(false, 1);
-      BF3(false, 0);
-#undef BF3
+    PwFwdArgs at = a;
+    at.share32 = ((int)g2.x == 2 * p->ncu) ? share_bf : 0;
+    if (blk_fwd_s_ok(p, a, &lds_s)) {      // the strip kernel: the model path's two-term combinations
+      published = lift_ub;
+      GT(2);
+      if (a.lw) return launch_blk_fwd_s<false, true>(nm, st, g2, lds_s, epi, at);
+      if (a.act_in) return launch_blk_fwd_s<true, false>(nm, st, g2, lds_s, epi, at);
+      return launch_blk_fwd_s<false, false>(nm, st, g2, lds_s, epi, at);
     }
     // k_blk_fwd_t (three-term variants: its two-term ones were replaced by the strip kernel above) for the flag combinations the
     // models and layer stacks of the reference produce - every instantiation below is launched by the GPU test suite
-    // (tools/kernel_coverage.py); anything else takes k_pw_fwd_x3, which has every option as a run-time argument.
-    // (template flags: LIFT, RELU, ACT_IN, EPI, ADD, KZ)
-#define BF2(LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_) return GT(3), launch(nm, k_blk_fwd_t<C, LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_>, g2, blk, lds2, st, a)
+    // (tools/kernel_coverage.py); anything else takes k_pw_fwd_x3.  Not a helper: the list does not enumerate every combination.
+    // (template flags: LIFT, RELU, ACT_IN, EPI, ADD, KZ - k_block_fwd2.h)
+#define BF2(LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_) return GT(3), launch(nm, k_blk_fwd_t<C, LIFT_, RELU_, AIN_, EPI_, ADD_, KZ_>, g2, blk, lds_t, st, at)
+    const int kz = a.z ? (2 * a.K2in + 15) / 16 : 0;
     const bool plain = !a.lw && !a.relu_out && !a.add;
     if (kz == 1) {
-      if (a.lw && !a.relu_out && !a.add && epi == 2) { if (ub_published) *ub_published = ub; BF2(true, false, false, 2, false, 1); }
+      if (a.lw && !a.relu_out && !a.add && epi == 2) { published = lift_ub; BF2(true, false, false, 2, false, 1); }
       if (plain && a.act_in) { if (epi == 2) BF2(false, false, true, 2, false, 1); if (epi == 1) BF2(false, false, true, 1, false, 1); BF2(false, false, true, 0, false, 1); }
       if (plain) { if (epi == 2) BF2(false, false, false, 2, false, 1); if (epi == 1) BF2(false, false, false, 1, false, 1); BF2(false, false, false, 0, false, 1); }
       if (!a.lw && a.relu_out && !a.add && epi == 0 && !a.act_in) BF2(false, true, false, 0, false, 1);
@@ -1233,24 +1268,19 @@ static int launch_block_x3(const FnoModelPlan* p, hipStream_t st, int grid, cons
     }
 #undef BF2
   }
+  // k_pw_fwd_x3 (template flags behind the tile shape: LOOSE, LIFT, RELU); no fallback behind it: launch() refuses what exceeds LDS
   const size_t lds = pw_fwd_x3_lds_bytes(C, p->NPX, a.W, a.K2in, a.NJ, a.z != nullptr, a.x1 != nullptr) +
                      (p->loose && a.z ? (size_t)2 * a.K2in * C * 2 * 4 : 0);      // two more spectral rows per tile
-  if (p->loose && !a.relu_out)
-    return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, true>, dim3(grid), dim3((C / 32) * (4 / FNO_NTW_PWX) * 64),
-                  lds, st, a);
-  if (a.lw && !a.relu_out) {
-    if (ub_published) *ub_published = ub;
-    return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, false, true>, dim3(grid), dim3((C / 32) * (4 / FNO_NTW_PWX) * 64),
-                  lds, st, a);
-  }
+  const dim3 blk((C / 32) * (4 / FNO_NTW_PWX) * 64);
+#define PWX(...) return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, ##__VA_ARGS__>, dim3(grid), blk, lds, st, a)
+  if (p->loose && !a.relu_out) PWX(true);
+  if (a.lw && !a.relu_out) { published = lift_ub; PWX(false, true); }
   if (a.relu_out) {
     if (p->NPX != 128 || p->loose || a.lw) return fail(FNO_EUNSUPPORTED, "ReLU output: 128-pixel tiles of whole rows, no fused lifting");
-    return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX, false, false, true>, dim3(grid),
-                  dim3((C / 32) * (4 / FNO_NTW_PWX) * 64), lds, st, a);
+    PWX(false, false, true);
   }
-  if (p->NPX == 128)
-    return GT(3), launch(nm, k_pw_fwd_x3<C, 128, FNO_NTW_PWX>, dim3(grid), dim3((C / 32) * (4 / FNO_NTW_PWX) * 64),
-                  lds, st, a);
+  if (p->NPX == 128) PWX();
+#undef PWX
   return GT(3), launch(nm, k_pw_fwd_x3<C, 256, 2>, dim3(grid), dim3((C / 32) * 4 * 64), lds, st, a);
 }
 static int launch_block(const FnoModelPlan* p, hipStream_t st, int grid, const PwFwdArgs& a, bool* ub_published = nullptr) {
@@ -1267,118 +1297,106 @@ static int launch_block(const FnoModelPlan* p, hipStream_t st, int grid, const P
   if (p->d.C == 32) return launch_pw<32, 32>(p, st, grid, a, "k_pw_fwd_block");
   return launch_pw<64, 64>(p, st, grid, a, "k_pw_fwd_block");
 }
-// k_block_bwd (k_block_bwd.h, exact fp32): g and u tiles, lifting-input rows, the tile's spectral rows and tables
-static size_t bbwd_lds(int C, int npx, const BlkBwdArgs& a) {
-  return ((size_t)2 * C * (npx + 4) + (a.xin ? 8 * (npx + 4) : 0) +
-          (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(npx / a.W) * a.K2in * C * 2 : 0) +
-          (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
+// k_block_bwd_g2 (k_block_bwd2.h; 64 channels, rows of 32 / 64 / 128 pixels: two independent 4-wave groups per workgroup): the
+// shape conditions, the two variants the register budget allows - block 0 with the lifting recomputed, and a block without
+// lifting input (gradient addends and two 16-output row-DFT blocks per wave: k_block_bwd_t takes those) - and the LDS check.
+// Decides a.kx16 and a.lines, which only this kernel reads.
+static bool blk_bwd_g2_ok(const FnoModelPlan* p, BlkBwdArgs& a, bool h2, size_t* lds) {
+  const int nterm = h2 ? 2 : 3;
+  // the K-extension as one 16-deep block on the matrix pipe where its images fit (judged before the whole-line staging is
+  // added: kept as it was, the other order could change what runs)
+  a.kx16 = (a.zg && a.K2in <= 8) ? 1 : 0;
+  if (a.kx16 && blk_bwd_g2_lds_bytes(a, nterm) > FNO_LDS_MAX) a.kx16 = 0;
+  a.lines = h2 ? 1 : 0;      // whole-line u loads / gout stores (round 6): the two-term variants carry them
+  if (!g_gemm_x3 || p->NPX != 128 || (a.W != 32 && a.W != 64 && a.W != 128) || (a.x1g && a.NJ > 2) || a.ntiles < 2) return false;
+  const bool two = a.x1g && a.W == 128 && a.NJ == 2;
+  if (a.gadd || (a.lw ? a.x1g != nullptr : (a.xin || two))) return false;
+  *lds = blk_bwd_g2_lds_bytes(a, nterm);
+  return *lds <= FNO_LDS_MAX;
 }
-// k_block_bwd_t (k_block_bwd2.h): two swizzled [3][C][128] bf16 images, the fp32 gout tile, two lifting-input buffers, tables
-static size_t bbwd_t_lds(int C, const BlkBwdArgs& a) {
-  return (size_t)6 * C * 256 +
-         ((size_t)C * 132 + (a.xin ? 2 * 8 * 132 : 0) +
-          (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(128 / a.W) * a.K2in * C * 2 : 0) +
-          (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
-}
-// k_block_bwd_g2: per group two [nterm][64][64] 16-bit images, a 64 x 68 fp32 half-tile, the tile's spectral rows, two
-// lifting-input buffers; shared tables; two barrier counters
-static size_t bbwd_g2_lds(const BlkBwdArgs& a, int nterm = 3) {
-  // spectral K-extension operands: fp32 rows + table, or (kx16) the bf16x3 images [3][rows][64][16] per group + [3][W][16]
-  const size_t kext = !a.zg ? 0 : a.kx16 ? (size_t)2 * 3 * (128 / a.W) * 64 * 32 + (size_t)3 * a.W * 32
-                                         : ((size_t)2 * (128 / a.W) * a.K2in * 64 * 2 + (size_t)2 * a.K2in * a.W) * 4;
-  return (size_t)4 * nterm * 64 * 128 + kext +
-         ((size_t)2 * 64 * 68 + (a.xin ? 2 * 2 * 8 * 68 : 0) + (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0) + 4) * 4 +
-         (a.lines ? 16 + 8 * 2048 : 0);      // whole-line u: 2 KB of staging per wave behind the barrier counters
-}
+// A block's backward.  In this order:
+//   spectral-branch dropout     k_block_bwd_t<DROPK> (three bf16 terms) / k_block_bwd<DROPK> (exact fp32)
+//   loose rows                  k_block_bwd_t<LOOSE> (three bf16 terms), the K-extension in chunks that fit LDS
+//   k_block_bwd_g2              64 channels (blk_bwd_g2_ok): two fp16 terms when both operand bounds came, else three bf16 terms
+//   k_block_bwd_t               split mode, 128-pixel tiles: two fp16 terms at 32 channels when the bounds came, else three bf16
+//   k_block_bwd                 exact fp32: everything else without a recomputed lifting
+// *published (if given): the launched kernel left max |gout| at a.gmax_out (k_block_bwd_g2 and k_block_bwd_t outside the
+// dropout / loose rows, when the pointer is set)
 template <int C>
-static int launch_bbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const BlkBwdArgs& a_in, bool* published = nullptr) {
+static int launch_bbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const BlkBwdArgs& a_in, bool* published_out = nullptr) {
   BlkBwdArgs a = a_in;
+  bool unused = false;
+  bool& published = published_out ? *published_out : unused;
+  published = false;
   // profile labels: block 0 behind a lifting layer reads g and the model input and writes no gradient tile unless dx is asked for
-  const char* nm = (a_in.xin && !a_in.gout) ? "k_block_bwd0" : "k_block_bwd";
-  const char* nm_kch = "k_block_bwd_kch";
-  const bool h2 = g_h2 && g_h2_blocks && a.gmax_in && a.umax;      // two-term fp16 variants (operand bounds known)
-  const int g2_terms = h2 ? 2 : 3;
-  a.kx16 = (C == 64 && a.zg && a.K2in <= 8) ? 1 : 0;
-  if (a.kx16 && bbwd_g2_lds(a, g2_terms) > 160 * 1024) a.kx16 = 0;
+  const char* nm = (a.xin && !a.gout) ? "k_block_bwd0" : "k_block_bwd";
+  const bool h2 = a.gmax_in && a.umax;      // two-term fp16 variants (operand bounds known)
+  const dim3 blk(BlkBwdCfg<C, 128>::NW * 64);
+  const size_t lds_t = blk_bwd_t_lds_bytes(C, a);      // (in every mode: it divides by a.W only under a.zg, and W is set with zg)
+  const bool t_ok = g_gemm_x3 && p->NPX == 128 && lds_t <= FNO_LDS_MAX;      // k_block_bwd_t
   if (a.drop_seed) {      // dropout of the spectral branch (one-layer stacks with a tail, fno_model_*_tail)
-    if (p->loose || a.lw || a.xin || p->NPX != 128 || (g_gemm_x3 ? bbwd_t_lds(C, a) : bbwd_lds(C, 128, a)) > 160 * 1024)
+    const size_t lds_f = blk_bwd_lds_bytes(C, 128, a);
+    if (p->loose || a.lw || a.xin || p->NPX != 128 || (g_gemm_x3 ? lds_t : lds_f) > FNO_LDS_MAX)
       return fail(FNO_EUNSUPPORTED, "spectral-branch dropout: 128-pixel tiles of whole rows, no lifting");
     if (!g_gemm_x3)      // exact-fp32 mode: the first-generation kernel with the same regenerated mask
-      return GT(1), launch(nm, k_block_bwd<C, 128, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_lds(C, 128, a), st, a);
-    return GT(3), launch(nm, k_block_bwd_t<C, 128, false, false, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64),
-                  bbwd_t_lds(C, a), st, a);
+      return GT(1), launch(nm, k_block_bwd<C, 128, true>, dim3(grid), blk, lds_f, st, a);
+    return GT(3), launch(nm, k_block_bwd_t<C, 128, false, false, true>, dim3(grid), blk, lds_t, st, a);
   }
   if (p->loose) {
     if (!g_gemm_x3) return fail(FNO_EUNSUPPORTED, "block stacks on loose rows need the split-precision GEMM mode");
-    BlkBwdArgs al = a;
-    const int rows = 128 / a.W + 2;
-    BlkBwdArgs nz = a;
-    nz.zg = nullptr;
-    const size_t base = bbwd_t_lds(C, nz);   // everything but the spectral rows and their table
-    const size_t per_mode = ((size_t)2 * a.W + (size_t)rows * C * 2) * 4;
-    size_t ldsl = base;
-    if (a.zg) {
-      int kch = a.K2in;
-      while (kch > 1 && base + kch * per_mode > 160 * 1024) --kch;         // chunk the K-extension until the tile fits
-      if (base + kch * per_mode > 160 * 1024) return fail(FNO_EUNSUPPORTED, "loose-row backward tile exceeds LDS");
-      al.kch = kch < a.K2in ? kch : 0;
-      ldsl = base + kch * per_mode;
-    }
-    return GT(3), launch(al.kch ? nm_kch : nm, k_block_bwd_t<C, 128, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), ldsl, st, al);
+    int kch = a.K2in;
+    while (kch > 1 && blk_bwd_t_loose_lds_bytes(C, a, kch) > FNO_LDS_MAX) --kch;         // chunk the K-extension until the tile fits
+    const size_t lds_l = blk_bwd_t_loose_lds_bytes(C, a, kch);
+    if (a.zg && lds_l > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "loose-row backward tile exceeds LDS");
+    if (a.zg) a.kch = kch < a.K2in ? kch : 0;
+    return GT(3), launch(a.kch ? "k_block_bwd_kch" : nm, k_block_bwd_t<C, 128, true>, dim3(grid), blk, lds_l, st, a);
   }
-  // C = 64, rows of 32 / 64 / 128 pixels: two independent 4-wave groups per workgroup (k_block_bwd_g2)
   if constexpr (C == 64) {
-    a.lines = h2 ? 1 : 0;      // whole-line u loads / gout stores (round 6): the two-term variants carry them
-    if (g_gemm_x3 && FNO_BBWD_X3 && p->NPX == 128 && (a.W == 32 || a.W == 64 || a.W == 128) &&
-        (!a.x1g || a.NJ <= 2) && a.ntiles >= 2 && bbwd_g2_lds(a, g2_terms) <= 160 * 1024) {
-      const int g2 = grid;      // the host sums `grid` partial slabs per output: groups without a tile write zeros
-      const size_t lds2 = bbwd_g2_lds(a, g2_terms);
-      const bool two = a.x1g && a.W == 128 && a.NJ == 2;
-      if (a.lw && !a.x1g && !a.gadd) {
-        if (published) *published = a.gmax_out != nullptr;
-        if (h2) return GT(2), launch(nm, k_block_bwd_g2<true, false, 1, 2, true>, dim3(g2), dim3(512), lds2, st, a);
-        return GT(3), launch(nm, k_block_bwd_g2<true, false, 1>, dim3(g2), dim3(512), lds2, st, a);
-      }
-      // (gradient addends and two 16-output blocks per wave do not fit the register budget yet: k_block_bwd_t takes those)
-      if (!a.lw && !a.xin && !a.gadd && !two) {
-        if (published) *published = a.gmax_out != nullptr;
-        if (h2) return GT(2), launch(nm, k_block_bwd_g2<false, false, 1, 2, true>, dim3(g2), dim3(512), lds2, st, a);
-        return GT(3), launch(nm, k_block_bwd_g2<false, false, 1>, dim3(g2), dim3(512), lds2, st, a);
-      }
+    size_t lds_g2 = 0;
+    if (blk_bwd_g2_ok(p, a, h2, &lds_g2)) {
+      published = a.gmax_out != nullptr;
+      GT(h2 ? 2 : 3);
+      // (`grid` workgroups: the host sums `grid` partial slabs per output, groups without a tile write zeros)
+      if (a.lw) return h2 ? launch(nm, k_block_bwd_g2<true, false, 1, 2, true>, dim3(grid), dim3(512), lds_g2, st, a)
+                          : launch(nm, k_block_bwd_g2<true, false, 1>, dim3(grid), dim3(512), lds_g2, st, a);
+      return h2 ? launch(nm, k_block_bwd_g2<false, false, 1, 2, true>, dim3(grid), dim3(512), lds_g2, st, a)
+                : launch(nm, k_block_bwd_g2<false, false, 1>, dim3(grid), dim3(512), lds_g2, st, a);
     }
   }
-  if (a.lw) {
-    if (!(g_gemm_x3 && FNO_BBWD_X3 && p->NPX == 128 && bbwd_t_lds(C, a) <= 160 * 1024))
-      return fail(FNO_EUNSUPPORTED, "block 0 cannot recompute the lifting in this GEMM mode (the forward pass skipped u_0)");
-    if (published) *published = a.gmax_out != nullptr;
-    if constexpr (C == 32)      // (64 channels: k_block_bwd_g2 above carries the two-term variants)
-      if (h2) return GT(2), launch(nm, k_block_bwd_t<C, 128, false, true, false, 2>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
-    return GT(3), launch(nm, k_block_bwd_t<C, 128, false, true>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
+  if (a.lw && !t_ok)
+    return fail(FNO_EUNSUPPORTED, "block 0 cannot recompute the lifting in this GEMM mode (the forward pass skipped u_0)");
+  if (t_ok) {
+    published = a.gmax_out != nullptr;
+    if constexpr (C == 32) if (h2) {      // (64 channels: k_block_bwd_g2 above carries the two-term variants)
+      GT(2);
+      if (a.lw) return launch(nm, k_block_bwd_t<C, 128, false, true, false, 2>, dim3(grid), blk, lds_t, st, a);
+      return launch(nm, k_block_bwd_t<C, 128, false, false, false, 2>, dim3(grid), blk, lds_t, st, a);
+    }
+    GT(3);
+    if (a.lw) return launch(nm, k_block_bwd_t<C, 128, false, true>, dim3(grid), blk, lds_t, st, a);
+    return launch(nm, k_block_bwd_t<C, 128>, dim3(grid), blk, lds_t, st, a);
   }
-  if (g_gemm_x3 && FNO_BBWD_X3 && p->NPX == 128 && bbwd_t_lds(C, a) <= 160 * 1024) {
-    if (published) *published = a.gmax_out != nullptr;
-    if constexpr (C == 32)
-      if (h2) return GT(2), launch(nm, k_block_bwd_t<C, 128, false, false, false, 2>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
-    return GT(3), launch(nm, k_block_bwd_t<C, 128>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), bbwd_t_lds(C, a), st, a);
-  }
-  const size_t lds = bbwd_lds(C, p->NPX, a);
-  if (p->NPX == 128)
-    return GT(1), launch(nm, k_block_bwd<C, 128>, dim3(grid), dim3(BlkBwdCfg<C, 128>::NW * 64), lds, st, a);
-  return GT(1), launch(nm, k_block_bwd<C, 256>, dim3(grid), dim3(BlkBwdCfg<C, 256>::NW * 64), lds, st, a);
+  // no fallback behind the exact-fp32 kernel: launch() refuses what exceeds LDS
+  const size_t lds = blk_bwd_lds_bytes(C, p->NPX, a);
+  GT(1);
+  if (p->NPX == 128) return launch(nm, k_block_bwd<C, 128>, dim3(grid), blk, lds, st, a);
+  return launch(nm, k_block_bwd<C, 256>, dim3(grid), dim3(BlkBwdCfg<C, 256>::NW * 64), lds, st, a);
 }
-// *published (if given): the launched kernel left max |gout| at a.gmax_out (the second-generation kernels do)
 static int launch_bbwd(const FnoModelPlan* p, hipStream_t st, int grid, const BlkBwdArgs& a, bool* published = nullptr) {
-  if (published) *published = false;
   return p->d.C == 32 ? launch_bbwd_c<32>(p, st, grid, a, published) : launch_bbwd_c<64>(p, st, grid, a, published);
 }
 static int bbwd_ksplit(const FnoModelPlan* p) {
   const int ntn = p->NPX / 32, mt = p->d.C / 32;
   return ntn / mt;
 }
+// The projection's forward (no row structure: always 128-pixel tiles).  In this order:
+//   k_proj_fwd_w    two fp16 terms     split mode, the bound of |u_L| came (a.xmax), one output channel, whole 32-pixel columns
+//   k_proj_fwd_x3   three bf16 terms   split mode otherwise
+//   k_proj_fwd      exact fp32
 template <int C, int NCO>
 static int launch_pfwd_cn(const FnoModelPlan* p, hipStream_t st, int grid, const ProjFwdArgs& a) {
-  // no row structure in the projection: always 128-pixel tiles
-  if (g_gemm_x3 && g_h2 && a.xmax && NCO == 1 && a.PW % 32 == 0) {
+  const size_t lds_w = proj_fwd_w_lds(C, kHID);      // (a constant, 67 KB at 64 channels: its test below is for uniformity only)
+  if (g_gemm_x3 && a.xmax && NCO == 1 && a.PW % 32 == 0 && lds_w <= FNO_LDS_MAX) {
     // independent waves, four per SIMD (k_projection_h2.h): two workgroups per CU
     constexpr int NWV = 12;
     const int ncols = a.ntiles * 4;
@@ -1386,15 +1404,11 @@ static int launch_pfwd_cn(const FnoModelPlan* p, hipStream_t st, int grid, const
     const int g = std::min((ncols + NWV - 1) / NWV, 2 * p->ncu);
     ProjFwdArgs aw = a;
     aw.share32 = g == 2 * p->ncu ? share_pf : 0;
-    return GT(2), launch("k_proj_fwd", k_proj_fwd_w<C, kHID, NWV>, dim3(g), dim3(NWV * 64), proj_fwd_w_lds(C, kHID), st, aw);
+    return GT(2), launch("k_proj_fwd", k_proj_fwd_w<C, kHID, NWV>, dim3(g), dim3(NWV * 64), lds_w, st, aw);
   }
-  if (g_gemm_x3) {
-    const size_t lds = (size_t)3 * 128 * (C + 8) * 2 + (size_t)(kHID / 32) * (C / 16) * 3 * 64 * 16 +
-                       (size_t)(kHID + NCO * kHID + NCO * 128) * 4;
-    return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, kHID, 128, NCO>, dim3(grid), dim3(512), lds, st, a);
-  }
-  const size_t lds = ((size_t)C * 132 + kHID + NCO * kHID + NCO * 128 + (size_t)kHID * (C + 1)) * 4;
-  return GT(1), launch("k_proj_fwd", k_proj_fwd<C, kHID, 128, NCO>, dim3(grid), dim3(512), lds, st, a);
+  if (g_gemm_x3)
+    return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, kHID, 128, NCO>, dim3(grid), dim3(512), proj_fwd_x3_lds_bytes(C, kHID, NCO), st, a);
+  return GT(1), launch("k_proj_fwd", k_proj_fwd<C, kHID, 128, NCO>, dim3(grid), dim3(512), proj_fwd_lds_bytes(C, kHID, NCO), st, a);
 }
 template <int C>
 static int launch_pfwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const ProjFwdArgs& a) {
@@ -1402,44 +1416,39 @@ static int launch_pfwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const 
 }
 template <int C, int NCO>
 static int launch_pbwd_cn(const FnoModelPlan* p, hipStream_t st, int grid, const ProjBwdArgs& a) {
-  // LDS: tile + dP1 chunk buffer(s) + dy rows + b1 + W2 + resident W1 (rows padded to C+1)
-  const int pitch = p->NPX + 4;
-  // mirrors the constexpr W1LDS / DBUF choices of k_proj_bwd
-  const size_t small = ((size_t)NCO * p->NPX + kHID + NCO * kHID) * 4;
-  const size_t w1b = (size_t)kHID * (C + 1) * 4;
-  const bool w1lds = (size_t)(C + 64) * pitch * 4 + small + w1b <= 160 * 1024;
-  const bool dbuf = (size_t)(C + 128) * pitch * 4 + small + (w1lds ? w1b : 0) <= 160 * 1024;
-  const size_t lds = (size_t)(C + (dbuf ? 128 : 64)) * pitch * 4 + small + (w1lds ? w1b : 0);
-  if (p->NPX == 128)
-    return GT(1), launch("k_proj_bwd", k_proj_bwd<C, kHID, 128, NCO>, dim3(grid), dim3(512), lds, st, a);
-  return GT(1), launch("k_proj_bwd", k_proj_bwd<C, kHID, 256, NCO>, dim3(grid), dim3(1024), lds, st, a);
+  const size_t lds = proj_bwd_lds_bytes(C, kHID, p->NPX, NCO);
+  GT(1);
+  if (p->NPX == 128) return launch("k_proj_bwd", k_proj_bwd<C, kHID, 128, NCO>, dim3(grid), dim3(512), lds, st, a);
+  return launch("k_proj_bwd", k_proj_bwd<C, kHID, 256, NCO>, dim3(grid), dim3(1024), lds, st, a);
 }
-// second-generation projection backward (k_projection2.h): C = 64, one output channel, 128-pixel tiles, split-precision mode
-static size_t pbwd_t_lds(int C, const ProjBwdArgs& a) {
-  const size_t nt = a.amax ? 2 : 3;       // term planes per image
-  return nt * C * 256 + 2 * nt * 64 * 256 + 128 * 4 + (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) * 4 : 0);
-}
+// second-generation projection backward (k_projection2.h): one output channel, 128-pixel tiles, split-precision mode
 static bool use_pbwd_t(int C, int CO, int npx) {
   return g_gemm_x3 && (C == 64 || C == 32) && CO == 1 && npx == 128;
 }
-// W1 -> bf16x3 fragments in the order the selected projection-backward kernel reads them
-static int pack_w1_x3(hipStream_t st, const float* w1, unsigned short* wa1, unsigned short* wa3, int HID, int C, bool t_order,
-                      const float* wmax = nullptr) {
-  const int nitems = (HID / 32) * (C / 16) * 64 + (HID / 32) * 2 * (C / 32) * 64;
-  // (the two-term fragments of k_proj_bwd_t<.., 2> are made by k_absmax3_pack_w1, in the launch that scans the bounds)
-  if (wmax) return fail(FNO_EUNSUPPORTED, "projection weight fragments: two-term split without the bound scan");
-  if (!t_order) return fail(FNO_EUNSUPPORTED, "projection weight fragments: k_proj_bwd_t's order only");
-  return launch("k_pack_w1_x3", k_pack_w1_t<3>, dim3((nitems + 255) / 256), dim3(256), 0, st, w1, wa1, wa3, HID, C, wmax);
+// W1 -> bf16x3 fragments in the order k_proj_bwd_t reads them (its two-term fp16 fragments are made by k_absmax3_pack_w1, in the
+// launch that scans the bounds)
+static int w1_frag_items(int HID, int C) { return (HID / 32) * (C / 16) * 64 + (HID / 32) * 2 * (C / 32) * 64; }
+static int pack_w1_x3(hipStream_t st, const float* w1, unsigned short* wa1, unsigned short* wa3, int HID, int C) {
+  return launch("k_pack_w1_x3", k_pack_w1_t<3>, dim3((w1_frag_items(HID, C) + 255) / 256), dim3(256), 0, st, w1, wa1, wa3, HID, C,
+                (const float*)nullptr);
 }
+// The projection's backward.  In this order:
+//   k_proj_bwd_t   the host packed W1's fragments (a.wa1; use_pbwd_t).  Two fp16 terms when the bounds came (a.amax): NO fallback,
+//                  the host has started the gradient-bound chain on it (its carve is at most 132608 bytes: NJ <= 4, W <= 128).
+//                  Else three bf16 terms, a third plane per image: with the gradient's row DFT fused (x1g, more than 16 kept
+//                  last-dim bins at 64 channels) that carve outgrows LDS, and the next kernel serves
+//   k_proj_bwd     exact fp32, first generation (same x1g epilogue, same partial slabs; publishes no bound)
 template <int C>
 static int launch_pbwd_c(const FnoModelPlan* p, hipStream_t st, int grid, const ProjBwdArgs& a) {
-  if (a.wa1 && a.amax && use_pbwd_t(C, a.CO, p->NPX))      // two fp16 terms: same LDS carve with two planes per image
-    return GT(2), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false, 2>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
-  // three bf16 terms take a third plane per image: with the gradient's row DFT fused (x1g, more than 16 kept last-dim bins at
-  // 64 channels) that carve outgrows LDS, and the first-generation kernel (same x1g epilogue, same partial slabs) serves instead
-  if (a.wa1 && use_pbwd_t(C, a.CO, p->NPX) && pbwd_t_lds(C, a) <= 160 * 1024)
-    return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
+  const size_t lds_t = proj_bwd_t_lds_bytes(C, a);
+  if (a.wa1 && use_pbwd_t(C, a.CO, p->NPX)) {
+    if (a.amax) return GT(2), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false, 2>, dim3(grid), dim3(512), lds_t, st, a);
+    if (lds_t <= FNO_LDS_MAX) return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, kHID, false>, dim3(grid), dim3(512), lds_t, st, a);
+  }
   return a.CO == 1 ? launch_pbwd_cn<C, 1>(p, st, grid, a) : launch_pbwd_cn<C, PROJ_MAXCO>(p, st, grid, a);
+}
+static int blk_fwd_grid(const FnoModelPlan* p, int ntiles) {      // persistent grid of the block forwards
+  return std::min(ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p->ncu);
 }
 
 // spectral middle of one block: x1 -> (hat) -> ohat -> z
@@ -1451,6 +1460,20 @@ static int spectral_mid_fwd(const FnoModelPlan* p, hipStream_t st, int B, const 
   LAUNCHCHK(lead_forward(st, g, p->t, false, B, C, w.x1, w.tmp, hat));
   LAUNCHCHK(mode_gemm(st, hat, wp, w.ohat, B, g.Ktot, C, C, 0));
   return lead_inverse(st, g, p->t, B, C, w.ohat, w.tmp, w.z);
+}
+// the unfused adjoint middle of nm members (member-major buffers; nm = 1: the model's layer):
+//   G = lead_forward(x1) -> ohat ; dW = conj(Xhat) G -> dwp (skipped if null) ; GX = G conj(W) -> hat ; lead_inverse(GX) -> z
+// Xhat is shared by the members.  The matrix-core adjoint reads the packed weights wps, the VALU one their transposed copy.
+static int spectral_mid_adj(const FnoModelPlan* p, hipStream_t st, const ModelSizes& s, int B, int nm, const float* x1, float* tmp,
+                            float* ohat, const float* xhat, float* dwp, const float* wps, const float* wpts, float* hat, float* z) {
+  const Geom& g = p->g;
+  const int C = p->d.C;
+  const bool adj_mfma = mode_gemm_members_ok(C, C);
+  const size_t hs = nm > 1 ? s.n_hat : 0, ws = nm > 1 ? s.n_wp : 0;      // member strides
+  LAUNCHCHK(lead_forward(st, g, p->t, true, nm * B, C, x1, tmp, ohat));
+  if (dwp) LAUNCHCHK(mode_gemm_dw(st, xhat, ohat, dwp, B, g.Ktot, C, C, nm, 0, hs, ws));
+  LAUNCHCHK(mode_gemm(st, ohat, adj_mfma ? wps : wpts, hat, B, g.Ktot, C, C, 1, nm, hs, ws, hs, adj_mfma ? 1 : 0));
+  return lead_inverse(st, g, p->t, nm * B, C, hat, tmp, z);
 }
 
 // one-layer block stacks with a tail (FnoBlockTail, include/fnoengine.h): what the plan must look like
@@ -1489,30 +1512,22 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
   bool ok;
   ModelWs w = carve_model(p, B, ws, ws_bytes, false, &ok);
   if (!ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
-  float* u = (float*)saved;                                 // u[l] = u + l * n_act
-  float* hats = u + (size_t)(L + 1) * s.n_act;              // hats[l] = hats + l * n_hat
-  float* wps = hats + (size_t)L * s.n_hat;                  // packed weights of every layer (kept for backward)
-  float* wpts = wps + (size_t)L * s.n_wp;
-  float* amax = wpts + (size_t)L * s.n_wp;                  // kNAmax magnitude bounds (fp16 two-term GEMMs)
-  // two-term fp16 GEMMs with published magnitude bounds: from 1024 tiles up - below that the kernels are latency-bound and
-  // the bound bookkeeping (one more launch, the weight scans in the prologues) costs more than three matrix products
-  // save (BASELINE config 1, 128 tiles: 0.27 -> 0.22 ms per step without it)
-  const bool h2 = g_gemm_x3 && g_h2 && d.Cout > 0 && L <= FNO_MAX_LAYERS && (size_t)B * g.PW >= ((size_t)1 << 17);
+  const ModelSaved sv = carve_saved(p, B, saved);
+  float* const u = sv.u;
+  float* const amax = sv.bounds;
+  // The ONE two-term decision of the forward: two-term fp16 GEMMs with published magnitude bounds from 1024 tiles up - below
+  // that the kernels are latency-bound and the bound bookkeeping (one more launch, the weight scans in the prologues) costs
+  // more than three matrix products save (BASELINE config 1, 128 tiles: 0.27 -> 0.22 ms per step without it)
+  const bool h2 = g_gemm_x3 && d.Cout > 0 && (size_t)B * g.PW >= ((size_t)1 << 17);
   static_assert(kNAmax == 64, "k_pack_w_tiled clears 64 slots");
   // (the bound slots are cleared by the weight pack's first workgroup - the first launch of the pass - or, plane-major weights, by a fill)
-  {
-    CornerPtrsL cp;
-    memset(&cp, 0, sizeof(cp));
-    for (int l = 0; l < L; ++l)
-      for (int c = 0; c < (1 << g.nlead); ++c) cp.p[l][c] = (const float2*)prm->spec_w[l][c];
-    // the matrix-core adjoint reads wps; the fused middle's adjoint streams the transposed copy
-    LAUNCHCHK(pack_w_layers(st, g, C, C, cp, L, wps, mode_gemm_members_ok(C, C) && !fused_mid_shape_ok(g, C) ? nullptr : wpts, s.n_wp,
-                            h2 ? amax : nullptr));
-  }
+  // the matrix-core adjoint reads wps; the fused middle's adjoint streams the transposed copy
+  LAUNCHCHK(pack_w_layers(st, g, C, C, corner_ptrs<CornerPtrsL>(g, prm->spec_w, 0, L - 1), L, sv.wps,
+                          mode_gemm_members_ok(C, C) && !fused_mid_shape_ok(g, C) ? nullptr : sv.wpts, s.n_wp, h2 ? amax : nullptr));
 
   const bool has_lift = d.Cin > 0, has_proj = d.Cout > 0;
   bool lift_xmax = false;      // max |x| of the model input was published (k_lift_rowdft)
-  bool u0_bound = false;       // block 0's forward published the bound of |u_0| (amax[8])
+  bool u0_bound = false;       // block 0's forward published the bound of |u_0| (bnd_u(0))
   FnoModelPlan::CallState cs;
   cs.B = B;
   PwFwdArgs a;
@@ -1522,16 +1537,14 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
     a.x = x; a.w = prm->lift_w; a.bias = prm->lift_b;
     cs.u0_skipped = lift_fused(p);
     a.u = cs.u0_skipped ? nullptr : u; a.x1 = p->loose ? nullptr : w.x1; a.tfwd = p->t.tfwd_f;
-    a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = 0; a.K2out = g.Klast; a.NJ = g.NJ;
-    a.act_in = 0; a.act_out = 0;
-    a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
+    set_tile_geom(a, g, s, 0);
     const size_t lds_lr = ((size_t)2 * g.Klast * (g.W + 4) + (size_t)LR_ROWS * d.Cin * (g.W + 4) + 2) * 4 + (size_t)LR_ROWS * g.Klast * (d.Cin + 1) * 8;
     if (cs.u0_skipped && !p->loose && lds_lr <= 48 * 1024) {
       // u_0 is never stored: only its row spectra are needed, and those are linear in the <= 4 input channels
       const int nrows = B * g.P;
       LAUNCHCHK(launch("k_lift_rowdft", k_lift_rowdft, dim3((nrows + LR_ROWS - 1) / LR_ROWS), dim3(256), lds_lr, st, x,
                        prm->lift_w, prm->lift_b, p->t.tfwd_f, (float2*)w.x1, d.Cin, C, g.PW, g.W, g.P, g.Klast, nrows,
-                       h2 ? amax + 7 : nullptr));
+                       h2 ? amax + kBndX : nullptr));
       lift_xmax = h2;
     } else
     LAUNCHCHK(launch_lift(p, st, std::min(s.ntiles, FNO_GRID_LIFT * p->ncu), a));
@@ -1548,7 +1561,7 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
     if (p->loose && l > 0)     // no row-DFT epilogue on loose rows: transform act(u_l) in its own pass
       LAUNCHCHK(row_forward(st, g, p->t.tfwd_f, p->t.tT[0], p->t.K2P, B, C, u + (size_t)l * s.n_act, w.x1,
                             (int)((d.gelu_mask >> (l - 1)) & 1u)));
-    LAUNCHCHK(spectral_mid_fwd(p, st, B, w, wps + (size_t)l * s.n_wp, hats + (size_t)l * s.n_hat));
+    LAUNCHCHK(spectral_mid_fwd(p, st, B, w, sv.wps + (size_t)l * s.n_wp, sv.hats + (size_t)l * s.n_hat));
     memset(&a, 0, sizeof(a));
     a.x = (l == 0 && !has_lift) ? x : u + (size_t)l * s.n_act;
     if (l == 0 && has_lift && cs.u0_skipped) { a.x = x; a.lw = prm->lift_w; a.lb = prm->lift_b; a.CL = d.Cin; }
@@ -1558,23 +1571,22 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
     a.u = (l == L - 1 && !has_proj) ? y : u + (size_t)(l + 1) * s.n_act;
     a.x1 = (l + 1 < L && !p->loose) ? w.x1 : nullptr;
     a.tfwd = p->t.tfwd_f;
-    a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = g.Klast; a.K2out = g.Klast; a.NJ = g.NJ;
+    set_tile_geom(a, g, s, g.Klast);
     a.act_in = (l > 0) && ((d.gelu_mask >> (l - 1)) & 1u);
     a.act_out = (d.gelu_mask >> l) & 1u;
     a.relu_out = tail && tail->relu_out;
-    a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
     if (h2) {      // magnitude bounds for the two-term fp16 GEMMs: every block publishes max |u_{l+1}| for its consumer
       // (measured at 32 channels, FNO3d 64^3: tracking the maximum costs k_pw_fwd_x3 0.012 ms per launch, the fp16 products
       // it enables save the block backward 0.017 ms per launch)
-      a.umax = amax + 8 + l + 1;
-      if (l == 0) { a.xmax = (a.lw && lift_xmax) ? amax + 7 : nullptr; a.ubound = amax + 8; }   // (an unfused u_0 has no published bound)
-      else a.xmax = amax + 8 + l;
+      a.umax = amax + bnd_u(l + 1);
+      if (l == 0) { a.xmax = (a.lw && lift_xmax) ? amax + kBndX : nullptr; a.ubound = amax + bnd_u(0); }   // (an unfused u_0 has no published bound)
+      else a.xmax = amax + bnd_u(l);
     }
     // zigzag: every block walks its tiles in the opposite direction of its producer, so that it starts on the part of its
     // input the producer wrote last - what the 256 MB Infinity Cache still holds of it (kernels without the option walk forward)
     a.rev = g_zigzag ? (l & 1) : 0;
     bool ub = false;
-    LAUNCHCHK(launch_block(p, st, std::min(s.ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p->ncu), a, &ub));
+    LAUNCHCHK(launch_block(p, st, blk_fwd_grid(p, s.ntiles), a, &ub));
     if (l == 0) u0_bound = ub;
   }
 
@@ -1585,10 +1597,10 @@ static int model_forward_impl(const FnoModelPlan* p, int B, const FnoModelParams
   pa.x = u + (size_t)L * s.n_act; pa.w1 = prm->proj_w1; pa.b1 = prm->proj_b1; pa.w2 = prm->proj_w2; pa.b2 = prm->proj_b2;
   pa.y = y; pa.PW = g.PW; pa.CO = d.Cout; pa.act_in = (d.gelu_mask >> (L - 1)) & 1u;
   pa.tiles_per_plane = g.PW / 128; pa.ntiles = B * pa.tiles_per_plane;
-  pa.xmax = (h2 && L > 0) ? amax + 8 + L : nullptr;
-  cs.h2_fwd = pa.xmax != nullptr;
+  pa.xmax = h2 ? amax + bnd_u(L) : nullptr;
+  cs.h2_fwd = h2;
   cs.bwd_clean = h2;
-  cs.h2_u0 = h2 && lift_xmax && g_h2 && u0_bound;      // (else the three-term block-0 backward, which needs no bound)
+  cs.h2_u0 = lift_xmax && u0_bound;      // (both need h2; else the three-term block-0 backward, which needs no bound)
   p->put_call(saved, cs);
   const int pgrid = std::min(pa.ntiles, FNO_GRID_PF * p->ncu);
   if (C == 32) LAUNCHCHK(launch_pfwd_c<32>(p, st, pgrid, pa));
@@ -1640,19 +1652,13 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
   bool ok;
   ModelWs w = carve_model(p, B, ws, ws_bytes, true, &ok);
   if (!ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
-  const float* u = (const float*)saved;
-  const float* hats = u + (size_t)(L + 1) * s.n_act;
-  const float* wps = hats + (size_t)L * s.n_hat;                          // [k][i][o] packed weights from forward
-  float* wpts = const_cast<float*>(wps) + (size_t)L * s.n_wp;            // [k][o][i]: only the VALU adjoint needs them
+  const ModelSaved sv = carve_saved(p, B, saved);
+  const float *u = sv.u, *hats = sv.hats;
+  float* const amax = sv.bounds;
   const bool fused_mid = fused_mid_ok(g, C);           // the forward packed the transposed copy as well
-  const bool adj_mfma = mode_gemm_members_ok(C, C);
-  if (!adj_mfma && !fused_mid_shape_ok(g, C)) {       // VALU contraction (A/B switch): the forward may have skipped the transposed copy
-    CornerPtrsL cpw;
-    memset(&cpw, 0, sizeof(cpw));
-    for (int l = l_lo; l <= l_hi; ++l)
-      for (int c = 0; c < (1 << g.nlead); ++c) cpw.p[l - l_lo][c] = (const float2*)prm->spec_w[l][c];
-    LAUNCHCHK(pack_w_layers(st, g, C, C, cpw, l_hi - l_lo + 1, nullptr, wpts + (size_t)l_lo * s.n_wp, s.n_wp));
-  }
+  if (!mode_gemm_members_ok(C, C) && !fused_mid_shape_ok(g, C))       // VALU contraction (A/B switch): the forward may have skipped the transposed copy
+    LAUNCHCHK(pack_w_layers(st, g, C, C, corner_ptrs<CornerPtrsL>(g, prm->spec_w, l_lo, l_hi), l_hi - l_lo + 1, nullptr,
+                            sv.wpts + (size_t)l_lo * s.n_wp, s.n_wp));
   JobList jobs;
 
   const bool has_lift = d.Cin > 0, has_proj = d.Cout > 0;
@@ -1666,9 +1672,13 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
     cs.u0_skipped = has_lift && lift_fused(p);
   }
   cs.B = B;
-  bool gvalid = false;      // amax[32 + l + 1] bounds the gradient the next block kernel reads (two-term fp16 GEMMs)
-  float* amax_b = const_cast<float*>(wps) + (size_t)2 * L * s.n_wp;
-  if (l_hi < L - 1 && g_gemm_x3 && g_h2 && cs.h2_fwd) gvalid = cs.gchain_valid;      // a later part: left by the previous part's last kernel
+  // The two-term decisions of this pass (fno_dev.h "h2"), made here once.  The forward pass of THIS buffer published max |u_l| and
+  // the mode allows two-term: the block kernels may take their fp16 variants (each needs its input gradient's bound too: gvalid)
+  const bool h2_chain = g_gemm_x3 && cs.h2_fwd;
+  // ... and the projection backward has a two-term kernel for this plan: it scans its scalars' bounds and starts the chain
+  const bool h2_proj = h2_chain && use_pbwd_t(C, d.Cout, p->NPX);
+  bool gvalid = false;      // amax[bnd_g(l + 1)] bounds the gradient the next block kernel reads
+  if (l_hi < L - 1 && h2_chain) gvalid = cs.gchain_valid;      // a later part: left by the previous part's last kernel
   // ---- projection backward -> gA = dL/du_L, row DFT (gradient tables) -> x1 ----
   ProjBwdArgs pb;
   memset(&pb, 0, sizeof(pb));
@@ -1683,44 +1693,31 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
   } else if (!has_proj) {
     LAUNCHCHK(row_forward(st, g, p->t.tfwd_b, p->t.tT[1], p->t.K2P, B, C, dy, w.x1));     // dy is dL/du_L
   } else {
-  // two-term fp16 GEMMs (fno_dev.h "h2") when the forward pass left the bound of |u_L|: bounds of dy and the weights now
-  // Bound slots written by the backward pass: [32 + l] max |g_l| (the chain) and, through bwd_b = amax + 59, [60] max |dy|,
-  // [61] max |W1|, [62] max |w2| (the kernels index them as bwd_b[1..3]) - ONE contiguous range, cleared by ONE memset at
-  // the start of the pass (round 3 issued five small ones per step; the forward's memset of all 64 slots is the other one)
-  float* amax = const_cast<float*>(wps) + (size_t)2 * L * s.n_wp;
-  float* bwd_b = amax + 59;
-  bool db2_done = false, w1_packed = false;
-  const bool h2 = g_gemm_x3 && g_h2 && use_pbwd_t(C, d.Cout, p->NPX) && cs.h2_fwd;      // (this buffer's forward published max |u_L|)
-  // cleared whenever ANY slot of the range is written in this pass: the projection's scalars (h2) or the chain of gradient
-  // bounds the layer loop hands out (same condition as there) - a second backward on the same `saved` must not keep the first one's
-  const bool chain = g_gemm_x3 && g_h2 && cs.h2_fwd && L <= 24;
-  // (not after a forward that has just cleared all 64 slots: one 4.5 us fill less per step; a second backward on the same
-  // `saved`, or an unknown buffer, clears)
+  // Bound slots written by the backward pass: bnd_g(l) (the chain) and the projection's scalars behind kBndProj - ONE contiguous
+  // range, [bnd_g(0), kNAmax), cleared by ONE memset at the start of the pass (round 3 issued five small ones per step; the
+  // forward's clearing of all slots is the other one) whenever any of its slots is written in this pass: a second backward on
+  // the same `saved` must not keep the first one's.  (Not after a forward that has just cleared all slots: one 4.5 us fill
+  // less per step; a second backward on the same `saved`, or an unknown buffer, clears.)
+  bool db2_done = false;
 #ifndef FNO_DEBUG_NO_BWD_FILL      // (debug builds of the detector test: 1 = never clear - tests/test_boundary_gpu.py must then fail)
 #define FNO_DEBUG_NO_BWD_FILL 0
 #endif
-  if (!FNO_DEBUG_NO_BWD_FILL && (h2 || chain) && !(cs_found && cs.bwd_clean) && hipMemsetAsync(amax + 32, 0, 32 * sizeof(float), st) != hipSuccess)
+  if (!FNO_DEBUG_NO_BWD_FILL && h2_chain && !(cs_found && cs.bwd_clean) &&
+      hipMemsetAsync(amax + bnd_g(0), 0, (kNAmax - bnd_g(0)) * sizeof(float), st) != hipSuccess)
     return fail(FNO_EHIP, "memset of the magnitude bounds");
-  if (h2) {
-    // (one output channel: the same launch leaves 256 partial sums of dy = the bias gradient's partial slabs; k_channel_sums
-    // below is then not launched)
-    db2_done = d.Cout == 1;
-    // the scan and the split of W1 into its two fp16 terms share a launch
-    {
-      const int nitems = (kHID / 32) * (C / 16) * 64 + (kHID / 32) * 2 * (C / 32) * 64;
-      LAUNCHCHK(launch("k_absmax", k_absmax3_pack_w1, dim3(256 + 8 + 1 + (nitems + 255) / 256), dim3(256), 0, st, dy,
-                       (size_t)B * d.Cout * g.PW, 256, prm->proj_w1, 8, prm->proj_w2, (size_t)d.Cout * kHID, 1, bwd_b + 1,
-                       db2_done ? w.db2_part : nullptr, w.wa1, w.wa3, kHID, C));
-      w1_packed = true;
-    }
-    pb.amax = bwd_b; pb.xmax = amax + 8 + L;
-  }
-  if (g_gemm_x3 && g_h2 && cs.h2_fwd && use_pbwd_t(C, d.Cout, p->NPX)) {      // the chain of gradient bounds starts here
-    pb.gmax_out = amax + 32 + L;
-    gvalid = true;
-  }
-  if (use_pbwd_t(C, d.Cout, p->NPX)) {      // (g_gemm_x3, one output channel: the fragments of k_proj_bwd_t)
-    if (!w1_packed) LAUNCHCHK(pack_w1_x3(st, prm->proj_w1, w.wa1, w.wa3, kHID, C, true, h2 ? bwd_b + 2 : nullptr));
+  if (use_pbwd_t(C, d.Cout, p->NPX)) {      // (split mode, one output channel: k_proj_bwd_t reads W1 as packed fragments)
+    if (h2_proj) {
+      // the scan of max |dy|, max |W1|, max |w2| and the split of W1 into its two fp16 terms share a launch, which also leaves
+      // 256 partial sums of dy = the bias gradient's partial slabs (one output channel; k_channel_sums below is then not launched)
+      static_assert(kBndW1 == kBndDy + 1 && kBndW2 == kBndDy + 2, "k_absmax3_pack_w1 writes three consecutive slots");
+      db2_done = true;
+      LAUNCHCHK(launch("k_absmax", k_absmax3_pack_w1, dim3(256 + 8 + 1 + (w1_frag_items(kHID, C) + 255) / 256), dim3(256), 0, st, dy,
+                       (size_t)B * d.Cout * g.PW, 256, prm->proj_w1, 8, prm->proj_w2, (size_t)d.Cout * kHID, 1, amax + kBndDy,
+                       w.db2_part, w.wa1, w.wa3, kHID, C));
+      pb.amax = amax + kBndProj; pb.xmax = amax + bnd_u(L);
+      pb.gmax_out = amax + bnd_g(L);      // the chain of gradient bounds starts here
+      gvalid = true;
+    } else LAUNCHCHK(pack_w1_x3(st, prm->proj_w1, w.wa1, w.wa3, kHID, C));
     pb.wa1 = w.wa1; pb.wa3 = w.wa3;
   }
   pb.x = u + (size_t)L * s.n_act; pb.dy = dy; pb.w1 = prm->proj_w1; pb.b1 = prm->proj_b1;
@@ -1749,15 +1746,7 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
     float* t = gnext; gnext = gspare; gspare = t;
   }
   const int ks = bbwd_ksplit(p);
-  auto unpack_spec_grads = [&](hipStream_t su) -> int {      // packed dW of this part's layers -> the corner gradients
-    CornerPtrsMutL cp;
-    memset(&cp, 0, sizeof(cp));
-    for (int l = l_lo; l <= l_hi; ++l)
-      for (int c = 0; c < (1 << g.nlead); ++c) cp.p[l - l_lo][c] = (float2*)gr->spec_w[l][c];
-    return unpack_dw_layers(su, g, C, C, w.dwp + (size_t)l_lo * s.n_wp, cp, l_hi - l_lo + 1, s.n_wp);
-  };
-  const bool batch_dw = l_hi > l_lo && mode_gemm_members_ok(C, C) && g_mode_mfma &&
-                        !(g_mode_gemv && B <= 4 && (long)g.Ktot * C * C >= (1L << 21));
+  const bool batch_dw = l_hi > l_lo && mode_gemm_members_ok(C, C) && !(B <= 4 && (long)g.Ktot * C * C >= (1L << 21));
   for (int l = l_hi; l >= l_lo; --l) {
     // spectral backward middle: G = lead_forward(x1) ; dW = conj(Xhat) G ; GX = G conj(W) ; zg = lead_inverse(GX)
     float* dwp_l = w.dwp + (size_t)l * s.n_wp;
@@ -1767,15 +1756,11 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
     // contraction launch behind the loop (layer index on the grid) instead of one 72-workgroup launch each
     float* ohat_l = w.ohat + (size_t)(batch_dw ? l : 0) * s.n_hat;
     if (fused_mid) {
-      LAUNCHCHK(spectral_mid_fused(st, g, p->t, true, B, C, w.x1, ohat_l, wpts + (size_t)l * s.n_wp, w.z, 1));
+      LAUNCHCHK(spectral_mid_fused(st, g, p->t, true, B, C, w.x1, ohat_l, sv.wpts + (size_t)l * s.n_wp, w.z, 1));
       if (!batch_dw) LAUNCHCHK(mode_gemm_dw(st, hats + (size_t)l * s.n_hat, ohat_l, dwp_l, B, g.Ktot, C, C));
-    } else {
-    LAUNCHCHK(lead_forward(st, g, p->t, true, B, C, w.x1, w.tmp, ohat_l));
-    if (!batch_dw) LAUNCHCHK(mode_gemm_dw(st, hats + (size_t)l * s.n_hat, ohat_l, dwp_l, B, g.Ktot, C, C));
-    if (adj_mfma) LAUNCHCHK(mode_gemm(st, ohat_l, wps + (size_t)l * s.n_wp, w.hat, B, g.Ktot, C, C, 1, 1, 0, 0, 0, 1));
-    else LAUNCHCHK(mode_gemm(st, ohat_l, wpts + (size_t)l * s.n_wp, w.hat, B, g.Ktot, C, C, 1));
-    LAUNCHCHK(lead_inverse(st, g, p->t, B, C, w.hat, w.tmp, w.z));
-    }
+    } else
+      LAUNCHCHK(spectral_mid_adj(p, st, s, B, 1, w.x1, w.tmp, ohat_l, hats + (size_t)l * s.n_hat, batch_dw ? nullptr : dwp_l,
+                                 sv.wps + (size_t)l * s.n_wp, sv.wpts + (size_t)l * s.n_wp, w.hat, w.z));
 
     BlkBwdArgs a;
     memset(&a, 0, sizeof(a));
@@ -1787,14 +1772,13 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
     a.dw_part = dw_part_l; a.db_part = db_part_l;
     a.xin = (l == 0 && has_lift) ? x : nullptr; a.dwl_part = w.dwl_part; a.CL = d.Cin;
     if (l == 0 && has_lift && cs.u0_skipped) { a.lw = prm->lift_w; a.lb = prm->lift_b; }
-    a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = g.Klast; a.K2out = g.Klast; a.NJ = g.NJ;
+    set_tile_geom(a, g, s, g.Klast);
     a.act_in = (l > 0) && ((d.gelu_mask >> (l - 1)) & 1u);
-    a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
     if (tail && tail->drop_p > 0.f) { a.drop_seed = tail->drop_seed; a.drop_p = tail->drop_p; }
-    if (g_gemm_x3 && g_h2 && cs.h2_fwd && L <= 24) {
+    if (h2_chain) {
       // bounds for the two-term fp16 GEMMs: |g| from the previous kernel of the chain, |u_l| from the forward pass
-      if (gvalid && (l > 0 || (a.lw && cs.h2_u0))) { a.gmax_in = amax_b + 32 + l + 1; a.umax = amax_b + 8 + l; }
-      if (l > 0) a.gmax_out = amax_b + 32 + l;      // (cleared with the whole range at the start of the pass)
+      if (gvalid && (l > 0 || (a.lw && cs.h2_u0))) { a.gmax_in = amax + bnd_g(l + 1); a.umax = amax + bnd_u(l); }
+      if (l > 0) a.gmax_out = amax + bnd_g(l);      // (cleared with the whole range at the start of the pass)
     }
     a.rev = g_zigzag ? ((L - 1 - l) & 1) : 0;      // zigzag along the chain: the projection backward ended at the front
     bool published = false;
@@ -1823,7 +1807,9 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
     LAUNCHCHK(mode_gemm_dw(st, hats + (size_t)l_lo * s.n_hat, w.ohat + (size_t)l_lo * s.n_hat, w.dwp + (size_t)l_lo * s.n_wp, B,
                            g.Ktot, C, C, l_hi - l_lo + 1, s.n_hat, s.n_hat, s.n_wp));
   LAUNCHCHK(jobs.run(st));
-  return unpack_spec_grads(st);
+  // packed dW of this part's layers -> the corner gradients
+  return unpack_dw_layers(st, g, C, C, w.dwp + (size_t)l_lo * s.n_wp, corner_ptrs<CornerPtrsMutL>(g, gr->spec_w, l_lo, l_hi),
+                          l_hi - l_lo + 1, s.n_wp);
 }
 
 // ===========================================================================
@@ -1840,6 +1826,10 @@ static int fanout_check(const FnoModelPlan* p, int B, int n_out) {
     return fail(FNO_EINVAL, "fno_fanout: needs a block-stack plan (Cin = Cout = 0) without activations");
   if (n_out < 1 || n_out > p->d.n_layers) return fail(FNO_EINVAL, "fno_fanout: %d members on a plan sized for %d", n_out, p->d.n_layers);
   return FNO_OK;
+}
+// every member's contraction and leading-axis passes in one launch each
+static bool fanout_batched(const FnoModelPlan* p, int B, int n_out) {
+  return n_out > 1 && mode_gemm_members_ok(p->d.C, p->d.C) && (long)n_out * B * (p->g.nlead == 2 ? p->g.dims[0] : 1) <= 65535;
 }
 extern "C" size_t fno_fanout_saved_bytes(const FnoModelPlan* p, int B, int n_out) {
   if (!p || B < 1 || n_out < 1) return 0;
@@ -1883,17 +1873,12 @@ extern "C" int fno_fanout_forward(const FnoModelPlan* p, int B, int n_out, const
   float* hat = (float*)saved;
   float* wps = hat + s.n_hat;
   float* wpts = wps + (size_t)n_out * s.n_wp;
-  {
-    CornerPtrsL cp;
-    memset(&cp, 0, sizeof(cp));
-    for (int j = 0; j < n_out; ++j)
-      for (int c = 0; c < (1 << g.nlead); ++c) cp.p[j][c] = (const float2*)prm->spec_w[j][c];
-    LAUNCHCHK(pack_w_layers(st, g, C, C, cp, n_out, wps, mode_gemm_members_ok(C, C) ? nullptr : wpts, s.n_wp));
-  }
+  LAUNCHCHK(pack_w_layers(st, g, C, C, corner_ptrs<CornerPtrsL>(g, prm->spec_w, 0, n_out - 1), n_out, wps,
+                          mode_gemm_members_ok(C, C) ? nullptr : wpts, s.n_wp));
   LAUNCHCHK(row_forward(st, g, p->t.tfwd_f, p->t.tT[0], p->t.K2P, B, C, x, w.x1));
   LAUNCHCHK(lead_forward(st, g, p->t, false, B, C, w.x1, w.tmp, hat));        // the shared truncated spectrum of x
-  const bool batched = n_out > 1 && mode_gemm_members_ok(C, C) && (long)n_out * B * (g.nlead == 2 ? g.dims[0] : 1) <= 65535;
-  if (batched) {      // every member's contraction and leading-axis inverse in one launch each
+  const bool batched = fanout_batched(p, B, n_out);
+  if (batched) {
     LAUNCHCHK(mode_gemm(st, hat, wps, f.ohat, B, g.Ktot, C, C, 0, n_out, 0, s.n_wp, s.n_hat));
     LAUNCHCHK(lead_inverse(st, g, p->t, n_out * B, C, f.ohat, f.tmp, f.z));
   }
@@ -1909,9 +1894,8 @@ extern "C" int fno_fanout_forward(const FnoModelPlan* p, int B, int n_out, const
     memset(&a, 0, sizeof(a));
     a.x = x; a.w = prm->skip_w[j]; a.bias = bias ? bias[j] : nullptr;
     a.z = zj; a.tinv = p->t.tinv_f; a.u = y[j]; a.tfwd = p->t.tfwd_f;
-    a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = g.Klast; a.K2out = g.Klast; a.NJ = g.NJ;
-    a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
-    LAUNCHCHK(launch_block(p, st, std::min(s.ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p->ncu), a));
+    set_tile_geom(a, g, s, g.Klast);
+    LAUNCHCHK(launch_block(p, st, blk_fwd_grid(p, s.ntiles), a));
   }
   return FNO_OK;
 }
@@ -1931,25 +1915,16 @@ extern "C" int fno_fanout_backward(const FnoModelPlan* p, int B, int n_out, cons
   const float* hat = (const float*)saved;
   const float* wps = hat + s.n_hat;
   float* wpts = const_cast<float*>(wps) + (size_t)n_out * s.n_wp;
-  const bool adj_mfma = mode_gemm_members_ok(C, C);
-  if (!adj_mfma) {
-    CornerPtrsL cpw;
-    memset(&cpw, 0, sizeof(cpw));
-    for (int j = 0; j < n_out; ++j)
-      for (int c = 0; c < (1 << g.nlead); ++c) cpw.p[j][c] = (const float2*)prm->spec_w[j][c];
-    LAUNCHCHK(pack_w_layers(st, g, C, C, cpw, n_out, nullptr, wpts, s.n_wp));
-  }
+  if (!mode_gemm_members_ok(C, C))      // VALU contraction: the forward skipped the transposed copy
+    LAUNCHCHK(pack_w_layers(st, g, C, C, corner_ptrs<CornerPtrsL>(g, prm->spec_w, 0, n_out - 1), n_out, nullptr, wpts, s.n_wp));
   const int ks = bbwd_ksplit(p);
   for (int j = 0; j < n_out; ++j)
     if (!dy[j]) return fail(FNO_EINVAL, "fno_fanout_backward: dy[%d] is null", j);
-  const bool batched = n_out > 1 && mode_gemm_members_ok(C, C) && (long)n_out * B * (g.nlead == 2 ? g.dims[0] : 1) <= 65535;
+  const bool batched = fanout_batched(p, B, n_out);
   if (batched) {
     for (int j = 0; j < n_out; ++j)
       LAUNCHCHK(row_forward(st, g, p->t.tfwd_b, p->t.tT[1], p->t.K2P, B, C, dy[j], f.x1 + (size_t)j * s.n_x1));
-    LAUNCHCHK(lead_forward(st, g, p->t, true, n_out * B, C, f.x1, f.tmp, f.ohat));
-    LAUNCHCHK(mode_gemm_dw(st, hat, f.ohat, w.dwp, B, g.Ktot, C, C, n_out, 0, s.n_hat, s.n_wp));
-    LAUNCHCHK(mode_gemm(st, f.ohat, adj_mfma ? wps : wpts, f.hat2, B, g.Ktot, C, C, 1, n_out, s.n_hat, s.n_wp, s.n_hat, adj_mfma ? 1 : 0));
-    LAUNCHCHK(lead_inverse(st, g, p->t, n_out * B, C, f.hat2, f.tmp, f.z));
+    LAUNCHCHK(spectral_mid_adj(p, st, s, B, n_out, f.x1, f.tmp, f.ohat, hat, w.dwp, wps, wpts, f.hat2, f.z));
   }
   JobList jobs;
   for (int j = 0; j < n_out; ++j) {
@@ -1960,11 +1935,8 @@ extern "C" int fno_fanout_backward(const FnoModelPlan* p, int B, int n_out, cons
     if (batched) zj = f.z + (size_t)j * s.n_x1;
     else {
       LAUNCHCHK(row_forward(st, g, p->t.tfwd_b, p->t.tT[1], p->t.K2P, B, C, dy[j], w.x1));
-      LAUNCHCHK(lead_forward(st, g, p->t, true, B, C, w.x1, w.tmp, w.ohat));
-      LAUNCHCHK(mode_gemm_dw(st, hat, w.ohat, dwp_j, B, g.Ktot, C, C));
-      if (adj_mfma) LAUNCHCHK(mode_gemm(st, w.ohat, wps + (size_t)j * s.n_wp, w.hat, B, g.Ktot, C, C, 1, 1, 0, 0, 0, 1));
-      else LAUNCHCHK(mode_gemm(st, w.ohat, wpts + (size_t)j * s.n_wp, w.hat, B, g.Ktot, C, C, 1));
-      LAUNCHCHK(lead_inverse(st, g, p->t, B, C, w.hat, w.tmp, w.z));
+      LAUNCHCHK(spectral_mid_adj(p, st, s, B, 1, w.x1, w.tmp, w.ohat, hat, dwp_j, wps + (size_t)j * s.n_wp, wpts + (size_t)j * s.n_wp,
+                                 w.hat, w.z));
     }
     BlkBwdArgs a;
     memset(&a, 0, sizeof(a));
@@ -1973,18 +1945,13 @@ extern "C" int fno_fanout_backward(const FnoModelPlan* p, int B, int n_out, cons
     a.gout = dx; a.gadd = j > 0 ? dx : nullptr;          // every lane re-reads exactly the elements it then rewrites
     a.tfwd = p->t.tfwd_b;
     a.dw_part = dw_part_j; a.db_part = db_part_j;
-    a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = g.Klast; a.K2out = g.Klast; a.NJ = g.NJ;
-    a.tiles_per_plane = s.tiles_per_plane; a.ntiles = s.ntiles;
+    set_tile_geom(a, g, s, g.Klast);
     LAUNCHCHK(launch_bbwd(p, st, s.grid_bb, a));
     jobs.add(dw_part_j, gr->skip_w[j], s.grid_bb * ks, C, C, C, C);
     if (dbias && dbias[j]) jobs.add(db_part_j, dbias[j], s.grid_bb, 1, C, C, C);
   }
   LAUNCHCHK(jobs.run(st));
-  CornerPtrsMutL cp;
-  memset(&cp, 0, sizeof(cp));
-  for (int j = 0; j < n_out; ++j)
-    for (int c = 0; c < (1 << g.nlead); ++c) cp.p[j][c] = (float2*)gr->spec_w[j][c];
-  return unpack_dw_layers(st, g, C, C, w.dwp, cp, n_out, s.n_wp);
+  return unpack_dw_layers(st, g, C, C, w.dwp, corner_ptrs<CornerPtrsMutL>(g, gr->spec_w, 0, n_out - 1), n_out, s.n_wp);
 }
 
 // ===========================================================================
@@ -2429,7 +2396,7 @@ extern "C" int fno_pointwise_forward(int B, int C, size_t PW, const float* x, co
   a.x = x; a.w = w; a.bias = bias; a.add = addend; a.u = y; a.act_in = input_gelu ? 1 : 0;
   a.PW = (int)PW; a.W = 128; a.P = (int)(PW / 128);
   a.tiles_per_plane = (int)(PW / 128); a.ntiles = B * a.tiles_per_plane;
-  return launch_block(&p, (hipStream_t)stream, std::min(a.ntiles, (g_gemm_x3 ? FNO_GRID_PWX : FNO_GRID_PW) * p.ncu), a);
+  return launch_block(&p, (hipStream_t)stream, blk_fwd_grid(&p, a.ntiles), a);
 }
 extern "C" int fno_pointwise_backward(int B, int C, size_t PW, const float* x, const float* w, const float* dy,
                                       const float* dx_addend, int input_gelu, float* dx, float* dw, float* dbias, void* ws,
@@ -2490,46 +2457,24 @@ extern "C" size_t fno_projection_workspace_bytes(int C, int hidden) {
   if ((C != 32 && C != 64) || (hidden != 128 && hidden != 256)) return 0;
   return carve_proj(C, hidden, nullptr, 0).total;
 }
-// exact-fp32 projection kernels (k_projection.h): LDS of k_proj_fwd / k_proj_bwd at 128-pixel tiles
-static size_t proj_fwd_f32_lds(int C, int HID, int NCO) {
-  return ((size_t)C * 132 + HID + NCO * HID + NCO * 128 + (size_t)HID * (C + 1)) * 4;
-}
-static size_t proj_bwd_f32_lds(int C, int HID, int NCO) {
-  const int pitch = 132;          // mirrors the constexpr W1LDS / DBUF choices of k_proj_bwd
-  const size_t small = ((size_t)NCO * 128 + HID + NCO * HID) * 4;
-  const size_t w1b = (size_t)HID * (C + 1) * 4;
-  const bool w1lds = (size_t)(C + 64) * pitch * 4 + small + w1b <= 160 * 1024;
-  const bool dbuf = (size_t)(C + 128) * pitch * 4 + small + (w1lds ? w1b : 0) <= 160 * 1024;
-  return (size_t)(C + (dbuf ? 128 : 64)) * pitch * 4 + small + (w1lds ? w1b : 0);
-}
-template <int C, int HID, bool RELU>
+// (2..PROJ_MAXCO output channels - PlanePredHead, pinobserver.py:257-273: fc2 -> out_dim * plane_num - run as NCO = PROJ_MAXCO rows)
+template <int C, int HID, bool RELU, int NCO = 1>
 static int proj_fwd_launch(hipStream_t st, int grid, const ProjFwdArgs& a) {
   if (!g_gemm_x3)
-    return GT(1), launch("k_proj_fwd", k_proj_fwd<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), proj_fwd_f32_lds(C, HID, 1), st, a);
-  const size_t lds = (size_t)3 * 128 * (C + 8) * 2 + (size_t)(HID / 32) * (C / 16) * 3 * 64 * 16 + (size_t)(HID + HID + 128) * 4;
-  return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), lds, st, a);
+    return GT(1), launch("k_proj_fwd", k_proj_fwd<C, HID, 128, NCO, RELU>, dim3(grid), dim3(512), proj_fwd_lds_bytes(C, HID, NCO), st, a);
+  return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, HID, 128, NCO, RELU>, dim3(grid), dim3(512), proj_fwd_x3_lds_bytes(C, HID, NCO), st, a);
 }
 template <int C, int HID, bool RELU>
 static int proj_bwd_launch(hipStream_t st, int grid, const ProjBwdArgs& a) {
   if (!g_gemm_x3)      // exact-fp32 mode: the first-generation kernel
-    return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), proj_bwd_f32_lds(C, HID, 1), st, a);
-  return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, HID, RELU>, dim3(grid), dim3(512), pbwd_t_lds(C, a), st, a);
+    return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, 1, RELU>, dim3(grid), dim3(512), proj_bwd_lds_bytes(C, HID, 128, 1), st, a);
+  return GT(3), launch("k_proj_bwd", k_proj_bwd_t<C, HID, RELU>, dim3(grid), dim3(512), proj_bwd_t_lds_bytes(C, a), st, a);
 }
-// 2..PROJ_MAXCO output channels (PlanePredHead, pinobserver.py:257-273: fc2 -> out_dim * plane_num): the forward kernel with
-// PROJ_MAXCO output rows (split-precision or exact fp32 by the GEMM mode), the backward on the exact-fp32 first-generation
-// kernel in both modes (the split-precision ones are built for one)
-template <int C, int HID>
-static int proj_fwd_launch_mo(hipStream_t st, int grid, const ProjFwdArgs& a) {
-  constexpr int NCO = PROJ_MAXCO;
-  if (!g_gemm_x3)
-    return GT(1), launch("k_proj_fwd", k_proj_fwd<C, HID, 128, NCO>, dim3(grid), dim3(512), proj_fwd_f32_lds(C, HID, NCO), st, a);
-  const size_t lds = (size_t)3 * 128 * (C + 8) * 2 + (size_t)(HID / 32) * (C / 16) * 3 * 64 * 16 + (size_t)(HID + NCO * HID + NCO * 128) * 4;
-  return GT(3), launch("k_proj_fwd", k_proj_fwd_x3<C, HID, 128, NCO, false>, dim3(grid), dim3(512), lds, st, a);
-}
+// several output channels: the backward runs on the exact-fp32 first-generation kernel in both modes (the split-precision ones
+// are built for one)
 template <int C, int HID>
 static int proj_bwd_launch_mo(hipStream_t st, int grid, const ProjBwdArgs& a) {
-  constexpr int NCO = PROJ_MAXCO;
-  return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, NCO>, dim3(grid), dim3(512), proj_bwd_f32_lds(C, HID, NCO), st, a);
+  return GT(1), launch("k_proj_bwd", k_proj_bwd<C, HID, 128, PROJ_MAXCO>, dim3(grid), dim3(512), proj_bwd_lds_bytes(C, HID, 128, PROJ_MAXCO), st, a);
 }
 static int proj_act_check(int hidden, int act) {
   if (act != FNO_ACT_GELU && act != FNO_ACT_RELU) return fail(FNO_EINVAL, "projection: hidden_act %d (FNO_ACT_GELU or FNO_ACT_RELU)", act);
@@ -2550,8 +2495,8 @@ extern "C" int fno_projection_forward_act(int B, int C, int hidden, int Cout, si
   hipStream_t st = (hipStream_t)stream;
   if (Cout > 1) {
     if (hidden_act != FNO_ACT_GELU) return fail(FNO_EUNSUPPORTED, "projection: several output channels with the GELU head only");
-    if (C == 32) return hidden == 128 ? proj_fwd_launch_mo<32, 128>(st, grid, pa) : proj_fwd_launch_mo<32, 256>(st, grid, pa);
-    return hidden == 128 ? proj_fwd_launch_mo<64, 128>(st, grid, pa) : proj_fwd_launch_mo<64, 256>(st, grid, pa);
+    if (C == 32) return hidden == 128 ? proj_fwd_launch<32, 128, false, PROJ_MAXCO>(st, grid, pa) : proj_fwd_launch<32, 256, false, PROJ_MAXCO>(st, grid, pa);
+    return hidden == 128 ? proj_fwd_launch<64, 128, false, PROJ_MAXCO>(st, grid, pa) : proj_fwd_launch<64, 256, false, PROJ_MAXCO>(st, grid, pa);
   }
   if (hidden_act == FNO_ACT_RELU) return C == 32 ? proj_fwd_launch<32, 256, true>(st, grid, pa) : proj_fwd_launch<64, 256, true>(st, grid, pa);
   if (C == 32) return hidden == 128 ? proj_fwd_launch<32, 128, false>(st, grid, pa) : proj_fwd_launch<32, 256, false>(st, grid, pa);
@@ -2573,7 +2518,7 @@ extern "C" int fno_projection_backward_act(int B, int C, int hidden, int Cout, s
   if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
   hipStream_t st = (hipStream_t)stream;
   const bool split = Cout == 1 && g_gemm_x3;      // k_proj_bwd_t reads W1 as split-precision fragments
-  if (split) LAUNCHCHK(pack_w1_x3(st, w1, w.wa1, w.wa3, hidden, C, true));
+  if (split) LAUNCHCHK(pack_w1_x3(st, w1, w.wa1, w.wa3, hidden, C));
   ProjBwdArgs pb;
   memset(&pb, 0, sizeof(pb));
   pb.x = x; pb.dy = dy; pb.w1 = w1; pb.b1 = b1; pb.w2 = w2; pb.gout = dx;

@@ -8,6 +8,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define FNO_DEV __device__ __forceinline__
 
+// LDS per CU (gfx950): what a workgroup's carve may reach.  The host launchers compare every kernel's *_lds_bytes (the host
+// function beside the kernel it sizes) to this one constant.
+static constexpr size_t FNO_LDS_MAX = 160 * 1024;
+
 // v_mfma_f32_32x32x2_f32: A[i=l&31][k=l>>5], B[k=l>>5][j=l&31];
 // D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5)   (exact fp32 FMA chain)
 FNO_DEV f32x16 mfma32(float a, float b, f32x16 c) {

@@ -70,6 +70,12 @@ struct BlkBwdCfg {
   static_assert(NW % TILES == 0 && KSPLIT >= 1, "C <= NPX required");
 };
 
+// dynamic LDS bytes of k_block_bwd<C, NPX>: g and u tiles, lifting-input rows, the tile's spectral rows and tables
+static inline size_t blk_bwd_lds_bytes(int C, int npx, const BlkBwdArgs& a) {
+  return ((size_t)2 * C * (npx + 4) + (a.xin ? 8 * (npx + 4) : 0) +
+          (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(npx / a.W) * a.K2in * C * 2 : 0) +
+          (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
+}
 // DROPK: the spectral branch saw drop(x) in the forward pass (rno.py:98): the K-extension part of dx is accumulated first and
 // multiplied by the regenerated dropout scale (the same drop_cfg hash as the forward's row pass and k_block_bwd_t<.., DROPK>),
 // then W^T g is accumulated on top of it.

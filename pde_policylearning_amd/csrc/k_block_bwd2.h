@@ -85,6 +85,20 @@ FNO_DEV f32x16 kext_loose_rows_t(f32x16 acc, const float* zs, const float* tinv_
   return acc;
 }
 
+// dynamic LDS bytes of k_block_bwd_t<C, 128>: two swizzled [3][C][128] bf16 images, the fp32 gout tile, two lifting-input
+// buffers, the tile's spectral rows and tables
+static inline size_t blk_bwd_t_lds_bytes(int C, const BlkBwdArgs& a) {
+  return (size_t)6 * C * 256 +
+         ((size_t)C * 132 + (a.xin ? 2 * 8 * 132 : 0) +
+          (a.zg ? (size_t)2 * a.K2in * a.W + (size_t)(128 / a.W) * a.K2in * C * 2 : 0) +
+          (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0)) * 4;
+}
+// ... of its LOOSE variant with `kch` kept last-dim modes resident per K-extension chunk (two more spectral rows per tile)
+static inline size_t blk_bwd_t_loose_lds_bytes(int C, const BlkBwdArgs& a, int kch) {
+  BlkBwdArgs nz = a;
+  nz.zg = nullptr;      // everything but the spectral rows and their table
+  return blk_bwd_t_lds_bytes(C, nz) + (a.zg ? kch * ((size_t)2 * a.W + (size_t)(128 / a.W + 2) * C * 2) * 4 : 0);
+}
 // DROPK: the spectral branch saw drop(x) in the forward pass (rno.py:98): its gradient, the K-extension part of dx, is
 // multiplied by the regenerated dropout scale before the skip branch's W^T g is accumulated on top of it.
 // NT3: terms of the two channel GEMMs' operands: 3 = bf16 (six products per k block), 2 = fp16 (three; fno_dev.h "h2") with g, a
@@ -435,6 +449,16 @@ FNO_DEV void group_barrier(unsigned* cnt, unsigned& epoch, int lane) {
   asm volatile("" ::: "memory");
 }
 
+// dynamic LDS bytes of k_block_bwd_g2<.., NT3 = nterm, ..>: per group two [nterm][64][64] 16-bit images, a 64 x 68 fp32
+// half-tile, the tile's spectral rows, two lifting-input buffers; shared tables; two barrier counters
+static inline size_t blk_bwd_g2_lds_bytes(const BlkBwdArgs& a, int nterm) {
+  // spectral K-extension operands: fp32 rows + table, or (kx16) the bf16x3 images [3][rows][64][16] per group + [3][W][16]
+  const size_t kext = !a.zg ? 0 : a.kx16 ? (size_t)2 * 3 * (128 / a.W) * 64 * 32 + (size_t)3 * a.W * 32
+                                         : ((size_t)2 * (128 / a.W) * a.K2in * 64 * 2 + (size_t)2 * a.K2in * a.W) * 4;
+  return (size_t)4 * nterm * 64 * 128 + kext +
+         ((size_t)2 * 64 * 68 + (a.xin ? 2 * 2 * 8 * 68 : 0) + (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) : 0) + 4) * 4 +
+         (a.lines ? 16 + 8 * 2048 : 0);      // whole-line u: 2 KB of staging per wave behind the barrier counters
+}
 // LIFT: block 0 of a model with a lifting layer (u_0 recomputed from the model input, lifting gradients instead of a row DFT);
 // GADD: a gradient addend is added to dx (fan-out chains); NJP: 16-output blocks of the row DFT per wave when a row spans both halves
 // LINES: u is loaded and gout stored in whole lines (a.lines; the host adds the staging to the LDS size)

@@ -26,6 +26,14 @@ struct ProjFwdArgs {
 
 constexpr int PROJ_MAXCO = 4;   // largest supported projection output width
 
+// dynamic LDS bytes of k_proj_fwd<C, HID, 128, NCO>: the tile, b1, W2, the output rows and the resident W1 (rows padded to C+1)
+static inline size_t proj_fwd_lds_bytes(int C, int HID, int NCO) {
+  return ((size_t)C * 132 + HID + NCO * HID + NCO * 128 + (size_t)HID * (C + 1)) * 4;
+}
+// ... of k_proj_fwd_x3<C, HID, 128, NCO>: the bf16x3 tile, W1's fragments, b1, W2, the output rows
+static inline size_t proj_fwd_x3_lds_bytes(int C, int HID, int NCO) {
+  return (size_t)3 * 128 * (C + 8) * 2 + (size_t)(HID / 32) * (C / 16) * 3 * 64 * 16 + (size_t)(HID + NCO * HID + NCO * 128) * 4;
+}
 // RELU: hidden activation max(h, 0) instead of GELU (RNO2d's regressor head, rno.py:171-175), as k_proj_fwd_x3<.., RELU>.
 // wave (hm, nt): hidden rows [64*ch + 32*hm, +32) of every chunk ch, pixels [32*nt, +32).
 // W1 stays in LDS for the lifetime of the (persistent) workgroup, rows padded to C+1 floats so
@@ -145,6 +153,15 @@ struct ProjBwdCfg {
   static_assert(NW % TILES == 0 && G >= 1 && NCH % G == 0, "projection backward tiling");
 };
 
+// dynamic LDS bytes of k_proj_bwd<C, HID, NPX, NCO>: tile + dP1 chunk buffer(s) + dy rows + b1 + W2 + resident W1 (rows padded
+// to C+1); mirrors the kernel's constexpr W1LDS / DBUF choices
+static inline size_t proj_bwd_lds_bytes(int C, int HID, int npx, int NCO) {
+  const int pitch = npx + 4;
+  const size_t small = ((size_t)NCO * npx + HID + NCO * HID) * 4, w1b = (size_t)HID * (C + 1) * 4;
+  const bool w1lds = (size_t)(C + 64) * pitch * 4 + small + w1b <= FNO_LDS_MAX;
+  const bool dbuf = (size_t)(C + 128) * pitch * 4 + small + (w1lds ? w1b : 0) <= FNO_LDS_MAX;
+  return (size_t)(C + (dbuf ? 128 : 64)) * pitch * 4 + small + (w1lds ? w1b : 0);
+}
 // wave (hm, nt) as in k_proj_fwd.  Per 64-row hidden chunk (ONE barrier per chunk, the dP1
 // chunk is double-buffered in LDS so wave groups run up to a chunk apart):
 //   A1  recompute P1 (MFMA 32x32x2)

@@ -140,6 +140,11 @@ __global__ void __launch_bounds__(256) k_absmax3_pack_w1(const float* __restrict
 // a chunk's dW1 (two 32 x 32 tiles) is split over the owner group's four waves by pixel halves (added through LDS at the end).
 // NT3 = 3: three bf16 terms, six products per k block; NT3 = 2: two fp16 terms, three products (fno_dev.h "h2"), operands
 // scaled by powers of two from a.amax = {max |x|, max |dy|, max |W1|, max |w2|} (device scalars)
+// dynamic LDS bytes of k_proj_bwd_t<C, ..>: two (a.amax set: fp16) or three (bf16) term planes per image
+static inline size_t proj_bwd_t_lds_bytes(int C, const ProjBwdArgs& a) {
+  const size_t nt = a.amax ? 2 : 3;
+  return nt * C * 256 + 2 * nt * 64 * 256 + 128 * 4 + (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) * 4 : 0);
+}
 #ifndef FNO_PB_SDFOLD
 #define FNO_PB_SDFOLD 1      // 0: the split multiplies by the fp16 scale itself (A/B arm)
 #endif

@@ -24,7 +24,7 @@ bit patterns - the magnitude-bound slots are accumulated that way).
 
 Safety: poison only data.  The harness must expose numeric dependence on stale memory, never make a kernel fault, so no
 poisoned buffer may hold something a kernel turns into an address.  Checked against fno_abi.hip (carve_spec, carve_model,
-carve_fanout, carve_pino, carve_chanflow, carve_proj, fno_lploss_rel_*, the Adam entry points) and the kernel headers:
+carve_saved, carve_fanout, carve_pino, carve_chanflow, carve_proj, fno_lploss_rel_*, the Adam entry points) and the kernel headers:
   - every carved region is float, float2 or packed 16-bit weight data (ModelWs::wa1 / wa3, ProjWs::wa1 / wa3);
   - the partial-sum reductions (k_reduce_jobs) get their job lists (ReduceJobs) as kernel arguments, not from memory;
   - the block backward's barrier counters and the projection's column queue live in LDS (k_block_bwd2.h, k_projection_h2.h);

@@ -139,7 +139,8 @@ def _rel(a, b):
 
 def _check_bound_slots(slots, ref, L, fused, npx128):
     """The 64 magnitude-bound slots at the end of `saved` after forward + backward, against the float64 tensors their consumers
-    split (slot map: model_forward_impl / model_backward_impl in fno_abi.hip).  [7] max |x| (k_lift_rowdft, fused lifting);
+    split (the host names them kBndX, bnd_u(l), bnd_g(l), kBndProj.. in fno_abi.hip; the literal numbers here are the independent
+    statement of that map).  [7] max |x| (k_lift_rowdft, fused lifting);
     [8] the derived bound of |u_0| (block 0's forward, fused lifting); [8 + l] max |u_l| as stored, l = 1..L (before the GELU
     gate); [32 + l] max |dL/du_l|, l = 1..L (the gradient chain: the projection backward and the block backwards publish their
     gout, which is the gradient AFTER the GELU derivative of the stored u_l; [32 + L] is the two-term projection backward's, the

@@ -62,7 +62,7 @@ int main(int argc, char** argv) {
   #if defined(USE_R3)
   const size_t lds = proj_bwd_r3_lds(W, NJ, true);
 #elif defined(USE_T)
-  const size_t lds = (size_t)2 * C * 256 + 2 * 2 * 64 * 256 + 128 * 4 + (size_t)16 * NJ * (W + 4) * 4;      // pbwd_t_lds (fno_abi.hip)
+  const size_t lds = (size_t)2 * C * 256 + 2 * 2 * 64 * 256 + 128 * 4 + (size_t)16 * NJ * (W + 4) * 4;      // proj_bwd_t_lds_bytes (k_projection2.h)
 #else
   const size_t lds = proj_bwd_r_lds(W, NJ, true);
 #endif
