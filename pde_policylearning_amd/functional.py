@@ -2,9 +2,18 @@
 
 PyTorch is plumbing here: it owns device memory (inputs, outputs, workspace, the
 forward->backward stash) and the stream; all arithmetic happens in the HIP library.
+
+The C ABI takes raw pointers and cannot see a tensor's device, dtype or extent, so this module is where they are checked.
+Two helpers carry that ("The Python bridge"):
+  _operand   every tensor passes through it before its address is taken: same device as the entry point's anchor (its first
+             operand, itself through _require_cuda), the expected dtype, the stated extent; returns it contiguous.
+  _call      every launching engine function is called through it: enters the anchor's device, reads the current stream
+             there, turns tensors into addresses, calls, and raises on a non-zero return code.
+Every forward / backward below reads: check operands, allocate, call.
 """
 import ctypes as C
-
+import math
+import typing
 import weakref
 
 import torch
@@ -13,14 +22,7 @@ from . import _lib
 
 _spec_plans = {}
 _model_plans = {}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_Tensor = torch.Tensor
 
 
 def _require_cuda(t, name):
@@ -33,6 +35,139 @@ def _require_cuda(t, name):
 
 def _bytes(n, device):
     return torch.empty(max(int(n), 256), dtype=torch.uint8, device=device)
+
+
+def _refuse(entry, name, need, got):
+    return RuntimeError(f"fnoengine {entry}: `{name}` must {need} (got {got}); refused before anything is launched")
+
+
+def _operand(entry, name, t, anchor, dtype=torch.float32, numel=None, shape=None, optional=False, layout="copy"):
+    """The one check between a tensor and its address.  `anchor`: the entry point's first operand (already through
+    _require_cuda); only its device is read, so CPU tensors can drive this function in a test.  Returns the tensor
+    contiguous (layout "copy": a copy when it is not), or None for an absent `optional` operand.  layout "dense": the engine
+    writes the tensor in place, so it must be contiguous as it stands; "keep": returned as it is (corner weights, whose
+    layout _weights_ready has settled).  Raises RuntimeError naming entry point, operand, what is needed and what was got."""
+    if t is None:
+        if optional:
+            return None
+        raise _refuse(entry, name, "be given", None)
+    if t.device != anchor.device:
+        raise _refuse(entry, name, f"live on {anchor.device}, the GPU of the call's first operand", t.device)
+    if t.dtype != dtype:
+        raise _refuse(entry, name, f"be {dtype}", t.dtype)
+    if numel is not None and t.numel() != numel:
+        raise _refuse(entry, name, f"have {numel} elements", f"{t.numel()}, shape {tuple(t.shape)}")
+    if shape is not None and t.shape != shape:
+        raise _refuse(entry, name, f"have shape {tuple(shape)}", tuple(t.shape))
+    if layout == "copy":
+        return t.contiguous()
+    if layout == "dense" and not t.is_contiguous():
+        raise _refuse(entry, name, "be contiguous (it is written in place)", f"strides {t.stride()}")
+    return t
+
+
+STREAM = object()       # stands for the current stream in _call's argument list (it is not always the last argument)
+
+
+def _ptr(t):
+    """address of a tensor that has been through _operand (None: NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _call(what, device, fname, *args):
+    """The one way into a launching engine function: on `device` (the anchor's), with the stream current THERE in place of
+    STREAM and tensors / None as addresses / NULL; a non-zero return code raises with the library's message."""
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = getattr(_lib.lib(), fname)(*[stream if a is STREAM else a.data_ptr() if isinstance(a, _Tensor) else a
+                                          for a in args])
+    _lib.check(rc, what)
+
+
+def _ptr_array(tensors, slots=None):
+    """void*[slots] over checked tensors, NULL-filled (None: NULL); slots = 4 is the corner-weight array of fno_spec_*"""
+    if tensors is None:
+        return None
+    slots = len(tensors) if slots is None else slots
+    return (C.c_void_p * slots)(*[t.data_ptr() for t in tensors] + [0] * (slots - len(tensors)))
+
+
+def _plan_available(cache, key, create, *args):
+    """True when `create(*args)` (a plan constructor) accepts the configuration; cached under `key`.  An unsupported shape is
+    not an error for callers that have another path."""
+    ok = cache.get(key)
+    if ok is None:
+        try:
+            create(*args)
+            ok = True
+        except RuntimeError:
+            ok = False
+        cache[key] = ok
+    return ok
+
+
+# ----------------------------------------------------------------------------
+# shape rules, each stated once
+# ----------------------------------------------------------------------------
+def plane_size(shape):
+    """elements per (batch, channel) plane of a (B, C, ...) shape"""
+    return math.prod(shape[2:])
+
+
+def gemm_mode():
+    """the engine's channel-GEMM mode: 1 split precision (default), 0 exact fp32 (include/fnoengine.h, fno_set_gemm_mode)"""
+    return _lib.lib().fno_get_gemm_mode()
+
+
+def row_tiling(dims, mode=None):
+    """How the fused block kernels cover a grid `dims`: "tiled" - rows of 32 / 64 / 128 / 256 floats that tile the 128-pixel
+    (256 for rows above 128) workgroup tile, planes a multiple of the tile; "loose" - any other last dim in 32..320 on planes
+    that tile by 128 pixels (the PINO observers' padded time axis 73, 96 x 96, 160 x 160): tiles of the flattened plane,
+    spectral rows gathered per tile, split-precision GEMM mode only (`mode`, default: the engine's current one); else None.
+    The engine keeps the last word (fno_model_plan_create: tile + twiddle tables must fit LDS)."""
+    w, pw = dims[-1], math.prod(dims)
+    npx = 256 if w > 128 else 128
+    if w % 32 == 0 and w <= 256 and npx % w == 0 and pw % npx == 0:
+        return "tiled"
+    if 32 <= w <= 320 and pw % 128 == 0 and (gemm_mode() if mode is None else mode) == 1:
+        return "loose"
+    return None
+
+
+def default_gelu_mask(n_layers):
+    """bit l set = GELU after layer l: the reference applies it while l < n_layers - l (fno_block.py:149)"""
+    return sum(1 << l for l in range(n_layers) if l < n_layers - l)
+
+
+class _Cfg(typing.NamedTuple):
+    """the non-tensor argument of the three plan-based Functions"""
+    n_layers: int
+    modes: tuple
+    norm: typing.Optional[str]
+    gelu_mask: int = 0
+    direct: typing.Any = None       # gradient storage the backward writes in place (_direct_views / fno_model), or None
+    overlap: typing.Any = None      # fno_model: the trainer's exchange-overlap hook
+    tail: typing.Any = None         # fno_block_tail: (relu_out, drop_p, seed tensor or None)
+
+
+def _fill_params(ncorner, skip_ws, spec_ws, spec_bias=None, ends=None):
+    """FnoModelParams (= FnoModelGrads) over checked tensors: per layer / fan-out member one skip weight and `ncorner` corner
+    weights, the bias rows, and for the whole model `ends` = (lift_w, lift_b, proj_w1, proj_b1, proj_w2, proj_b2)."""
+    s = _lib.FnoModelParams()
+    for l, t in enumerate(skip_ws):
+        s.skip_w[l] = t.data_ptr()
+        for c in range(ncorner):
+            s.spec_w[l][c] = spec_ws[l * ncorner + c].data_ptr()
+    s.spec_bias = _ptr(spec_bias)
+    if ends is not None:
+        s.lift_w, s.lift_b, s.proj_w1, s.proj_b1, s.proj_w2, s.proj_b2 = [t.data_ptr() for t in ends]
+    return s
+
+
+def _saved_params(sv, head, n_layers, ncorner, has_bias=False):
+    """(skip weights, corner weights, bias rows or None) back out of saved_tensors, where they follow `head` other tensors"""
+    a, b = head + n_layers, head + n_layers + n_layers * ncorner
+    return list(sv[head:a]), list(sv[a:b]), sv[b] if has_bias else None
 
 
 # ----------------------------------------------------------------------------
@@ -51,10 +186,8 @@ def spec_plan(ndim, cin, cout, dims, modes, weight_last_extent, norm, device, in
         d.norm = _lib.NORM_CODES[norm]
         d.input_gelu = 1 if input_gelu else 0
         d.weight_planes = 1 if weight_planes else 0
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().fno_spec_plan_create(C.byref(d), C.byref(h)), "spec_plan_create")
-        plan = h
+        plan = C.c_void_p()
+        _call("spec_plan_create", device, "fno_spec_plan_create", C.byref(d), C.byref(plan))
         _spec_plans[key] = plan
     return plan
 
@@ -111,17 +244,17 @@ def _weights_ready(ws):
     return [t.contiguous() for t in ws], False
 
 
-def _check_corner_weights(spec_ws, cin, cout, modes, planes, what):
-    """The C ABI takes raw pointers: a corner weight of the wrong extent is an out-of-bounds read on the device, not an
-    error.  Contiguous corner weights (real view) must be (cin, cout, *modes, 2) - what the reference's einsum would
-    have refused otherwise; plane-major ones carry their own (checked) extents."""
-    if planes:
-        return
-    want = (int(cin), int(cout)) + tuple(int(m) for m in modes) + (2,)
-    for i, t in enumerate(spec_ws):
-        if tuple(t.shape) != want:
-            raise RuntimeError(f"fnoengine {what}: spectral weight {i} has shape {tuple(t.shape)}, the plan's kept modes "
-                               f"{tuple(modes)} need {want} (real view of a ({cin}, {cout}, {', '.join(str(int(m)) for m in modes)}) complex corner)")
+def _check_corner_weights(entry, ws, anchor, cin, cout, modes, last=None):
+    """The front door for corner weights (real views): -> (tensors the engine reads in place, weight_planes flag).  Each goes
+    through _operand in the layout _weights_ready settled.  A corner weight of the wrong extent is an out-of-bounds read on
+    the device, not an error, so the shape must be (cin, cout, *modes, 2) - what the reference's einsum would have refused
+    otherwise - with `last` (the stored last-dim extent of the standalone plans) in place of modes[-1] when given.  Without
+    `last` (block stacks), plane-major weights carry their own extents: plane_major() has checked them against the strides."""
+    ws, planes = _weights_ready(ws)
+    want = None
+    if last is not None or not planes:
+        want = (int(cin), int(cout)) + tuple(int(m) for m in modes[:-1]) + (int(modes[-1] if last is None else last), 2)
+    return [_operand(entry, f"spectral weight {i}", t, anchor, shape=want, layout="keep") for i, t in enumerate(ws)], planes
 
 
 def _same_layout(g, w):
@@ -131,6 +264,10 @@ def _same_layout(g, w):
 def _fresh_grads(ws, planes):
     """gradient tensors laid out like the weights; plane-major: zeros (the engine writes the live planes only)"""
     return [torch.zeros_like(t) if planes else torch.empty_like(t) for t in ws]
+
+
+def _real_views(ws):
+    return [torch.view_as_real(t) if t.is_complex() else t for t in ws]
 
 
 def _direct_views(direct_grads, spec_ws, last_dim=None):
@@ -170,26 +307,18 @@ def _notify_direct(tensors):
 class _SpectralConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, modes, norm, weight_last_extent, direct, *weights):
+        e = "spectral_conv"
         _require_cuda(x, "x")
         x = x.contiguous()
-        ws_list, planes = _weights_ready(weights)            # real views (.., 2)
-        for w in ws_list:
-            _require_cuda(w, "weight")
         B, cin = x.shape[0], x.shape[1]
         dims = tuple(x.shape[2:])
         ndim = len(dims)
-        cout = ws_list[0].shape[1]
-        # (raw pointers from here on: extents the plan will assume are checked against the tensors first)
-        if len(ws_list) != 2 ** (ndim - 1) or len(modes) != ndim:
-            raise RuntimeError(f"fnoengine spectral_conv: {len(ws_list)} corner weights / {len(modes)} mode counts for {ndim}-d data")
+        if len(weights) != 2 ** (ndim - 1) or len(modes) != ndim:
+            raise RuntimeError(f"fnoengine {e}: {len(weights)} corner weights / {len(modes)} mode counts for {ndim}-d data")
+        cout = weights[0].shape[1]
         wl = int(weight_last_extent) if weight_last_extent else int(modes[-1])
-        want = (int(cin), int(cout)) + tuple(int(m) for m in modes[:-1]) + (wl, 2)
-        for i, w in enumerate(ws_list):
-            if tuple(w.shape) != want:
-                raise RuntimeError(f"fnoengine spectral_conv: corner weight {i} has shape {tuple(w.shape)}, kept modes {tuple(modes)} "
-                                   f"(last extent {wl}) need {want}")
-        if bias is not None and bias.numel() != cout:
-            raise RuntimeError(f"fnoengine spectral_conv: bias has {bias.numel()} elements, {cout} output channels")
+        ws_list, planes = _check_corner_weights(e, weights, x, cin, cout, modes, last=wl)        # real views (.., 2)
+        b = _operand(e, "bias", bias, x, numel=cout, optional=True)
         L = _lib.lib()
         plan = spec_plan(ndim, cin, cout, dims, modes, weight_last_extent, norm, x.device, weight_planes=planes)
         ctx.planes = planes
@@ -197,11 +326,7 @@ class _SpectralConvFn(torch.autograd.Function):
         xhat = _bytes(L.fno_spec_xhat_bytes(plan, B), x.device)
         nws = L.fno_spec_workspace_bytes(plan, B)
         ws = _bytes(nws, x.device)
-        wp = (C.c_void_p * 4)(*[w.data_ptr() for w in ws_list] + [0] * (4 - len(ws_list)))
-        b = bias.contiguous() if bias is not None else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_spec_forward(plan, B, _ptr(x), wp, _ptr(b), _ptr(y), _ptr(xhat), _ptr(ws), nws,
-                                          _stream()), "spec_forward")
+        _call("spec_forward", x.device, "fno_spec_forward", plan, B, x, _ptr_array(ws_list, 4), b, y, xhat, ws, nws, STREAM)
         ctx.plan, ctx.B, ctx.has_bias = plan, B, bias is not None
         ctx.x_shape = x.shape
         ctx.direct = direct
@@ -211,7 +336,7 @@ class _SpectralConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xhat, *ws_list = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = _operand("spectral_conv backward", "dy", dy, xhat)
         L = _lib.lib()
         need_dx = ctx.needs_input_grad[0]
         need_db = ctx.has_bias and ctx.needs_input_grad[1]
@@ -222,11 +347,8 @@ class _SpectralConvFn(torch.autograd.Function):
         db = torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device) if need_db else None
         nws = L.fno_spec_workspace_bytes(ctx.plan, ctx.B)
         ws = _bytes(nws, dy.device)
-        wp = (C.c_void_p * 4)(*[w.data_ptr() for w in ws_list] + [0] * (4 - len(ws_list)))
-        dwp = (C.c_void_p * 4)(*[w.data_ptr() for w in dws] + [0] * (4 - len(dws))) if need_dw else None
-        with torch.cuda.device(dy.device):
-            _lib.check(L.fno_spec_backward(ctx.plan, ctx.B, _ptr(dy), _ptr(xhat), wp, _ptr(dx),
-                                           dwp, _ptr(db), _ptr(ws), nws, _stream()), "spec_backward")
+        _call("spec_backward", dy.device, "fno_spec_backward", ctx.plan, ctx.B, dy, xhat, _ptr_array(ws_list, 4), dx,
+              _ptr_array(dws, 4), db, ws, nws, STREAM)
         if direct is not None:                     # written in place into the caller's gradient storage
             _notify_direct(direct)
             return (dx, db, None, None, None, None) + (None,) * len(ws_list)
@@ -242,7 +364,7 @@ def spectral_conv(x, weights, bias, modes, norm="backward", weight_last_extent=N
     trainer.FlatGradBucket) instead of returning it to autograd: no accumulation kernel, no zeroing needed.  Only valid when
     each weight feeds exactly one spectral_conv call per step.
     """
-    ws = [torch.view_as_real(w) if w.is_complex() else w for w in weights]
+    ws = _real_views(weights)
     wle = int(weight_last_extent) if weight_last_extent is not None else int(ws[0].shape[-2])
     b = bias.reshape(-1) if bias is not None else None
     direct = _direct_views(direct_grads, weights, last_dim=x.shape[-1])
@@ -265,10 +387,8 @@ def model_plan(ndim, cin, c, cout, hidden_proj, n_layers, dims, modes, norm, gel
         d.norm = _lib.NORM_CODES[norm]
         d.gelu_mask = gelu_mask
         d.weight_planes = 1 if weight_planes else 0
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().fno_model_plan_create(C.byref(d), C.byref(h)), "model_plan_create")
-        plan = h
+        plan = C.c_void_p()
+        _call("model_plan_create", device, "fno_model_plan_create", C.byref(d), C.byref(plan))
         _model_plans[key] = plan
     return plan
 
@@ -277,26 +397,11 @@ def model_plan_available(ndim, cin, c, cout, hidden_proj, n_layers, dims, modes,
     """True when fno_model_plan_create accepts the configuration (result cached; an unsupported shape is not an error
     for callers that have an unfused path)."""
     key = ("avail", ndim, cin, c, cout, hidden_proj, n_layers, tuple(dims), tuple(modes), norm, gelu_mask, device.index)
-    ok = _model_plans.get(key)
-    if ok is None:
-        try:
-            model_plan(ndim, cin, c, cout, hidden_proj, n_layers, dims, modes, norm, gelu_mask, device)
-            ok = True
-        except RuntimeError:
-            ok = False
-        _model_plans[key] = ok
-    return ok
+    return _plan_available(_model_plans, key, model_plan, ndim, cin, c, cout, hidden_proj, n_layers, dims, modes, norm,
+                           gelu_mask, device)
 
 
-def _fill_params(struct, n_layers, ncorner, lift_w, lift_b, skip_ws, spec_ws, spec_bias, w1, b1, w2, b2):
-    struct.lift_w, struct.lift_b = lift_w.data_ptr(), lift_b.data_ptr()
-    for l in range(n_layers):
-        struct.skip_w[l] = skip_ws[l].data_ptr()
-        for c in range(ncorner):
-            struct.spec_w[l][c] = spec_ws[l * ncorner + c].data_ptr()
-    struct.spec_bias = spec_bias.data_ptr() if spec_bias is not None else 0
-    struct.proj_w1, struct.proj_b1 = w1.data_ptr(), b1.data_ptr()
-    struct.proj_w2, struct.proj_b2 = w2.data_ptr(), b2.data_ptr()
+_ENDS = ("lift_w", "lift_b", "w1", "b1", "w2", "b2")        # the model's parameters outside the block stack, in ABI order
 
 
 class _FNOModelFn(torch.autograd.Function):
@@ -305,7 +410,8 @@ class _FNOModelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, lift_w, lift_b, spec_bias, w1, b1, w2, b2, *rest):
-        n_layers, modes, norm, gelu_mask, direct, overlap = cfg
+        e = "fno_model"
+        n_layers, modes, norm, gelu_mask, direct, overlap, _ = cfg
         ctx.direct = direct
         ctx.overlap = overlap
         _require_cuda(x, "x")
@@ -313,88 +419,72 @@ class _FNOModelFn(torch.autograd.Function):
         dims = tuple(x.shape[2:])
         ndim = len(dims)
         ncorner = 2 ** (ndim - 1)
-        skip_ws = [t.contiguous() for t in rest[:n_layers]]
-        spec_ws = [t.contiguous() for t in rest[n_layers:]]
-        assert len(spec_ws) == n_layers * ncorner
-        tensors = [lift_w, lift_b, w1, b1, w2, b2] + skip_ws + spec_ws + ([spec_bias] if spec_bias is not None else [])
-        for t in tensors:
-            _require_cuda(t, "parameter")
-        lift_w, lift_b, w1, b1, w2, b2 = [t.contiguous() for t in (lift_w, lift_b, w1, b1, w2, b2)]
-        sb = spec_bias.contiguous() if spec_bias is not None else None
+        assert len(rest) == n_layers + n_layers * ncorner
         B, cin = x.shape[0], x.shape[1]
         c, cout, hid = lift_w.shape[0], w2.shape[0], w1.shape[0]
-        _check_corner_weights(spec_ws, c, c, modes, False, "fno_model")
-        for t, want, nm in ((lift_w, c * cin, "lifting weight"), (lift_b, c, "lifting bias"), (w1, hid * c, "projection W1"), (b1, hid, "projection b1"),
-                            (w2, cout * hid, "projection W2"), (b2, cout, "projection b2")):
-            if t.numel() != want:
-                raise RuntimeError(f"fnoengine fno_model: {nm} has {t.numel()} elements, the model's widths need {want}")
-        for l, t in enumerate(skip_ws):
-            if t.numel() != c * c:
-                raise RuntimeError(f"fnoengine fno_model: skip weight {l} has {t.numel()} elements, need {c * c}")
+        ends = [_operand(e, nm, t, x, numel=n) for nm, t, n in (
+            ("lifting weight", lift_w, c * cin), ("lifting bias", lift_b, c), ("projection W1", w1, hid * c),
+            ("projection b1", b1, hid), ("projection W2", w2, cout * hid), ("projection b2", b2, cout))]
+        skip_ws = [_operand(e, f"skip weight {l}", t, x, numel=c * c) for l, t in enumerate(rest[:n_layers])]
+        want = (c, c) + tuple(modes) + (2,)             # the whole model takes contiguous corner weights only
+        spec_ws = [_operand(e, f"spectral weight {i}", t, x, shape=want) for i, t in enumerate(rest[n_layers:])]
+        sb = _operand(e, "spectral bias", spec_bias, x, numel=n_layers * c, optional=True)
+        if direct is not None:          # gradient storage the backward writes in place: one tensor per parameter, same extent
+            pairs = list(zip(ends, (direct[k] for k in _ENDS))) + list(zip(skip_ws, direct["skip"])) \
+                + list(zip(spec_ws, direct["spec"])) + ([(sb, direct["spec_bias"])] if sb is not None else [])
+            for p, g in pairs:
+                _operand(e, "direct-write gradient", g, x, numel=p.numel(), layout="dense")
         L = _lib.lib()
         plan = model_plan(ndim, cin, c, cout, hid, n_layers, dims, modes, norm, gelu_mask, x.device)
-        prm = _lib.FnoModelParams()
-        _fill_params(prm, n_layers, ncorner, lift_w, lift_b, skip_ws, spec_ws, sb, w1, b1, w2, b2)
+        prm = _fill_params(ncorner, skip_ws, spec_ws, sb, ends)
         y = torch.empty((B, cout) + dims, dtype=torch.float32, device=x.device)
         saved = _bytes(L.fno_model_saved_bytes(plan, B), x.device)
         nws = L.fno_model_workspace_bytes(plan, B)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_model_forward(plan, B, C.byref(prm), _ptr(x), _ptr(y), _ptr(saved), _ptr(ws), nws,
-                                           _stream()), "model_forward")
+        _call("model_forward", x.device, "fno_model_forward", plan, B, C.byref(prm), x, y, saved, ws, nws, STREAM)
         ctx.plan, ctx.B, ctx.n_layers, ctx.ncorner = plan, B, n_layers, ncorner
         ctx.has_sb = sb is not None
-        ctx.save_for_backward(x, saved, lift_w, lift_b, w1, b1, w2, b2, *skip_ws, *spec_ws,
-                              *([sb] if sb is not None else []))
+        ctx.save_for_backward(x, saved, *ends, *skip_ws, *spec_ws, *([sb] if sb is not None else []))
         return y
 
     @staticmethod
     def backward(ctx, dy):
         sv = ctx.saved_tensors
-        x, saved, lift_w, lift_b, w1, b1, w2, b2 = sv[:8]
+        x, saved = sv[:2]
+        ends = sv[2:8]
         nl, nc = ctx.n_layers, ctx.ncorner
-        skip_ws = list(sv[8:8 + nl])
-        spec_ws = list(sv[8 + nl:8 + nl + nl * nc])
-        sb = sv[8 + nl + nl * nc] if ctx.has_sb else None
-        dy = dy.contiguous()
+        skip_ws, spec_ws, sb = _saved_params(sv, 8, nl, nc, ctx.has_sb)
+        dy = _operand("fno_model backward", "dy", dy, x)
         L = _lib.lib()
-        prm = _lib.FnoModelParams()
-        _fill_params(prm, nl, nc, lift_w, lift_b, skip_ws, spec_ws, sb, w1, b1, w2, b2)
+        prm = _fill_params(nc, skip_ws, spec_ws, sb, ends)
         if ctx.direct is not None:
             # the engine WRITES gradients: hand it the parameters' own (pre-allocated, flat-bucket)
             # .grad storage and return None so autograd launches no accumulation kernels
             dg = ctx.direct
-            g = [dg[k] for k in ("lift_w", "lift_b", "w1", "b1", "w2", "b2")]
+            g = [dg[k] for k in _ENDS]
             g_skip, g_spec, g_sb = dg["skip"], dg["spec"], dg["spec_bias"]
         else:
-            g = [torch.empty_like(t) for t in (lift_w, lift_b, w1, b1, w2, b2)]
+            g = [torch.empty_like(t) for t in ends]
             g_skip = [torch.empty_like(t) for t in skip_ws]
             g_spec = [torch.empty_like(t) for t in spec_ws]
             g_sb = torch.empty_like(sb) if sb is not None else None
-        grd = _lib.FnoModelGrads()
-        _fill_params(grd, nl, nc, g[0], g[1], g_skip, g_spec, g_sb, g[2], g[3], g[4], g[5])
+        grd = _fill_params(nc, g_skip, g_spec, g_sb, g)
         nws = L.fno_model_workspace_bytes(ctx.plan, ctx.B)
         ws = _bytes(nws, dy.device)
         ov = ctx.overlap
         # dL/dx through the lifting layer (run_control.py:186-224 differentiates the observer down to its input field)
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dy.device):
-            if dx is not None:
-                _lib.check(L.fno_model_backward_dx(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                   C.byref(grd), _ptr(dx), _ptr(ws), nws, _stream()), "model_backward_dx")
-            elif ov is not None and ctx.direct is not None and 0 < ov.split_layer < nl:
-                # late layers first; their finished gradients go on the wire while the early layers are differentiated
-                k = ov.split_layer
-                _lib.check(L.fno_model_backward_part(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                     C.byref(grd), None, _ptr(ws), nws, _stream(), nl - 1, k),
-                           "model_backward_part")
-                ov.late_gradients_ready()
-                _lib.check(L.fno_model_backward_part(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                     C.byref(grd), None, _ptr(ws), nws, _stream(), k - 1, 0),
-                           "model_backward_part")
-            else:
-                _lib.check(L.fno_model_backward(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                C.byref(grd), _ptr(ws), nws, _stream()), "model_backward")
+        common = (ctx.plan, ctx.B, C.byref(prm), x, dy, saved, C.byref(grd))
+        if dx is not None:
+            _call("model_backward_dx", dy.device, "fno_model_backward_dx", *common, dx, ws, nws, STREAM)
+        elif ov is not None and ctx.direct is not None and 0 < ov.split_layer < nl:
+            # late layers first; their finished gradients go on the wire while the early layers are differentiated
+            k = ov.split_layer
+            _call("model_backward_part", dy.device, "fno_model_backward_part", *common, None, ws, nws, STREAM, nl - 1, k)
+            ov.late_gradients_ready()
+            _call("model_backward_part", dy.device, "fno_model_backward_part", *common, None, ws, nws, STREAM, k - 1, 0)
+        else:
+            _call("model_backward", dy.device, "fno_model_backward", *common, ws, nws, STREAM)
         if ctx.direct is not None:
             return (None, dx) + (None,) * (7 + len(skip_ws) + len(spec_ws))
         return (None, dx, g[0], g[1], g_sb, g[2], g[3], g[4], g[5]) + tuple(g_skip) + tuple(g_spec)
@@ -406,10 +496,7 @@ def fno_model(x, lift_w, lift_b, skip_ws, spec_ws, spec_bias, w1, b1, w2, b2, mo
     corner per dim (n_modes // 2); `spec_ws` real-view corner weights, layer-major."""
     n_layers = len(skip_ws)
     if gelu_mask is None:
-        gelu_mask = 0
-        for l in range(n_layers):
-            if l < n_layers - l:                 # fno_block.py:149
-                gelu_mask |= 1 << l
+        gelu_mask = default_gelu_mask(n_layers)
     direct = None
     if direct_grads:
         params = [lift_w, lift_b, w1, b1, w2, b2] + list(skip_ws) + list(spec_ws) + ([spec_bias] if spec_bias is not None else [])
@@ -417,7 +504,7 @@ def fno_model(x, lift_w, lift_b, skip_ws, spec_ws, spec_bias, w1, b1, w2, b2, mo
             direct = dict(lift_w=lift_w.grad, lift_b=lift_b.grad, w1=w1.grad, b1=b1.grad, w2=w2.grad, b2=b2.grad,
                           skip=[p.grad for p in skip_ws], spec=[p.grad for p in spec_ws],
                           spec_bias=spec_bias.grad if spec_bias is not None else None)
-    cfg = (n_layers, tuple(int(m) for m in modes), norm, int(gelu_mask), direct, overlap if direct is not None else None)
+    cfg = _Cfg(n_layers, tuple(int(m) for m in modes), norm, int(gelu_mask), direct, overlap if direct is not None else None)
     return _FNOModelFn.apply(cfg, x, lift_w, lift_b, spec_bias, w1, b1, w2, b2, *skip_ws, *spec_ws)
 
 
@@ -427,29 +514,25 @@ def fno_model(x, lift_w, lift_b, skip_ws, spec_ws, spec_bias, w1, b1, w2, b2, mo
 class _LpLossRelFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, mean, std, eps, size_average):
+        e = "lp_loss_rel"
         _require_cuda(pred, "pred")
         _require_cuda(target, "target")
-        L = _lib.lib()
         B = pred.shape[0]
-        pred_c, tgt_c = pred.contiguous(), target.contiguous()
+        pred_c = pred.contiguous()
         n = pred_c.numel() // B
-        if tgt_c.numel() != pred_c.numel():
-            raise RuntimeError(f"fnoengine lp_loss_rel: pred {tuple(pred.shape)} vs target {tuple(target.shape)}")
-        stat_len = 1
-        for s in (mean, std):
-            if s is not None:
-                _require_cuda(s, "mean/std")
-                stat_len = s.numel()
-        if mean is not None and std is not None and mean.numel() != std.numel():
-            raise RuntimeError("fnoengine lp_loss_rel: mean and std must have the same number of elements")
-        mean_c = mean.contiguous() if mean is not None else None
-        std_c = std.contiguous() if std is not None else None
-        nws = L.fno_lploss_workspace_bytes(B)
+        if target.numel() != pred_c.numel():
+            raise RuntimeError(f"fnoengine {e}: pred {tuple(pred.shape)} vs target {tuple(target.shape)}")
+        tgt_c = _operand(e, "target", target, pred)
+        mean_c = _operand(e, "mean", mean, pred, optional=True)
+        std_c = _operand(e, "std", std, pred, optional=True)
+        if mean_c is not None and std_c is not None and mean_c.numel() != std_c.numel():
+            raise RuntimeError(f"fnoengine {e}: mean and std must have the same number of elements")
+        stat_len = std_c.numel() if std_c is not None else mean_c.numel() if mean_c is not None else 1
+        nws = _lib.lib().fno_lploss_workspace_bytes(B)
         ws = _bytes(nws, pred.device)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
-        _lib.check(L.fno_lploss_rel_forward(B, n, _ptr(pred_c), _ptr(tgt_c), _ptr(mean_c), _ptr(std_c), stat_len,
-                                            float(eps), int(bool(size_average)), _ptr(loss), _ptr(ws), nws, _stream()),
-                   "lploss_rel_forward")
+        _call("lploss_rel_forward", pred.device, "fno_lploss_rel_forward", B, n, pred_c, tgt_c, mean_c, std_c, stat_len,
+              float(eps), int(bool(size_average)), loss, ws, nws, STREAM)
         ctx.save_for_backward(pred_c, tgt_c, std_c if std_c is not None else pred_c.new_empty(0), ws)
         ctx.meta = (B, n, stat_len, float(eps), std_c is not None, nws, pred.shape)
         return loss
@@ -458,11 +541,10 @@ class _LpLossRelFn(torch.autograd.Function):
     def backward(ctx, gloss):
         pred_c, tgt_c, std_c, ws = ctx.saved_tensors
         B, n, stat_len, eps, has_std, nws, shape = ctx.meta
-        L = _lib.lib()
         dpred = torch.empty_like(pred_c)
-        g = gloss.contiguous().to(torch.float32)
-        _lib.check(L.fno_lploss_rel_backward(B, n, _ptr(pred_c), _ptr(tgt_c), _ptr(std_c if has_std else None), stat_len,
-                                             eps, _ptr(g), _ptr(dpred), _ptr(ws), nws, _stream()), "lploss_rel_backward")
+        g = _operand("lp_loss_rel backward", "gloss", gloss.contiguous().to(torch.float32), pred_c, numel=1)
+        _call("lploss_rel_backward", pred_c.device, "fno_lploss_rel_backward", B, n, pred_c, tgt_c, std_c if has_std else None,
+              stat_len, eps, g, dpred, ws, nws, STREAM)
         return dpred.view(shape), None, None, None, None, None
 
 
@@ -473,23 +555,30 @@ def lp_loss_rel(pred, target, mean=None, std=None, eps=1e-5, size_average=False)
     return _LpLossRelFn.apply(pred, target, mean, std, eps, size_average)
 
 
+def _adam_state(e, param, grad, exp_avg, exp_avg_sq, step_counter, scratch, compact=False):
+    """the buffers of an Adam update (all updated or read in place: dense, never copied); compact: the moments have a
+    size of their own (adam_step_runs)"""
+    _require_cuda(param, "param")
+    _operand(e, "grad", grad, param, numel=param.numel(), layout="dense")
+    _operand(e, "param", param, param, layout="dense")
+    _operand(e, "exp_avg", exp_avg, param, numel=None if compact else param.numel(), layout="dense")
+    _operand(e, "exp_avg_sq", exp_avg_sq, param, numel=exp_avg.numel(), layout="dense")
+    if step_counter is not None:
+        _operand(e, "step_counter", step_counter, param, dtype=torch.int32, numel=1, layout="dense")
+        _operand(e, "scratch", scratch, param, numel=2, layout="dense")
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
               step_counter=None, scratch=None):
     """One torch.optim.Adam update of a flat fp32 bucket, in place, one kernel.  With `step_counter`
     (int32 device tensor) the step count lives on the device (fno_adam_step_dev: graph-replayable)."""
-    for t, name in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _require_cuda(t, name)
-        if not t.is_contiguous() or t.numel() != param.numel():
-            raise RuntimeError(f"fnoengine adam_step: `{name}` must be contiguous with {param.numel()} elements")
+    _adam_state("adam_step", param, grad, exp_avg, exp_avg_sq, step_counter, scratch)
+    hp = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
     if step_counter is not None:
-        _lib.check(_lib.lib().fno_adam_step_dev(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                                float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                                float(weight_decay), _ptr(step_counter), _ptr(scratch), _stream()),
-                   "adam_step_dev")
+        _call("adam_step_dev", param.device, "fno_adam_step_dev", param.numel(), param, grad, exp_avg, exp_avg_sq, *hp,
+              step_counter, scratch, STREAM)
         return
-    _lib.check(_lib.lib().fno_adam_step(param.numel(), _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                        float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-                                        int(step), _stream()), "adam_step")
+    _call("adam_step", param.device, "fno_adam_step", param.numel(), param, grad, exp_avg, exp_avg_sq, *hp, int(step), STREAM)
 
 
 def adam_step_runs(runs, param, grad, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay, step_counter=None,
@@ -497,51 +586,43 @@ def adam_step_runs(runs, param, grad, exp_avg, exp_avg_sq, step, lr, betas, eps,
     """One Adam update of a bucket planned around dead last-dim slices (trainer.FusedAdam.skip_dead_slices): `runs` lists
     ("dense", offset, n, compact offset) ranges and ("rows", offset, rows, row_len, live_len, compact offset) blocks of
     `param` / `grad` (full layout); exp_avg / exp_avg_sq are compact.  One kernel per run, the dead part of a block untouched."""
-    L = _lib.lib()
-    for t, name in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _require_cuda(t, name)
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise RuntimeError(f"fnoengine adam_step_runs: `{name}` must be contiguous float32")
-    if grad.numel() != param.numel() or exp_avg.numel() != exp_avg_sq.numel():
-        raise RuntimeError("fnoengine adam_step_runs: param / grad and exp_avg / exp_avg_sq must pair up")
-    dyn = None
+    _adam_state("adam_step_runs", param, grad, exp_avg, exp_avg_sq, step_counter, scratch, compact=True)
+    dev = param.device
     if step_counter is not None:
-        _lib.check(L.fno_adam_prep_dev(_ptr(step_counter), _ptr(scratch), float(lr), float(betas[0]), float(betas[1]),
-                                       _stream()), "adam_prep_dev")
-        dyn = _ptr(scratch)
+        _call("adam_prep_dev", dev, "fno_adam_prep_dev", step_counter, scratch, float(lr), float(betas[0]), float(betas[1]),
+              STREAM)
     hp = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step))
+    dyn = scratch if step_counter is not None else None
+    # addresses of the runs inside the four checked buffers: each run is held against the buffers' extents below
     P, G, M, V = param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
     for run in runs:
         if run[0] == "dense":
             _, off, n, coff = run
-            if off + n > param.numel() or coff + n > exp_avg.numel():
+            if off < 0 or coff < 0 or off + n > param.numel() or coff + n > exp_avg.numel():
                 raise RuntimeError("fnoengine adam_step_runs: run outside the buffers")
-            _lib.check(L.fno_adam_step_range(n, P + 4 * off, G + 4 * off, M + 4 * coff, V + 4 * coff, *hp, dyn, _stream()),
-                       "adam_step_range")
+            _call("adam_step_range", dev, "fno_adam_step_range", n, P + 4 * off, G + 4 * off, M + 4 * coff, V + 4 * coff, *hp,
+                  dyn, STREAM)
         else:
             _, off, rows, row_len, live_len, coff = run
-            if off + rows * row_len > param.numel() or coff + rows * live_len > exp_avg.numel():
+            if off < 0 or coff < 0 or off + rows * row_len > param.numel() or coff + rows * live_len > exp_avg.numel():
                 raise RuntimeError("fnoengine adam_step_runs: block outside the buffers")
-            _lib.check(L.fno_adam_step_live(rows, row_len, live_len, P + 4 * off, G + 4 * off, M + 4 * coff, V + 4 * coff, *hp,
-                                            dyn, _stream()), "adam_step_live")
+            _call("adam_step_live", dev, "fno_adam_step_live", rows, row_len, live_len, P + 4 * off, G + 4 * off, M + 4 * coff,
+                  V + 4 * coff, *hp, dyn, STREAM)
 
 
 def adam_replay_scalars(step_from, nsteps, lr, betas, device, on_device=False):
     """(2 * nsteps,) device tensor: {lr / (1 - beta1^t), sqrt(1 - beta2^t)} for t = step_from .. step_from + nsteps - 1,
     derived as the stepping kernels' callers derive them: on the host in double (fno_adam_step), or - on_device - by the
     device arithmetic of the graph-replayable path (fno_adam_step_dev)."""
-    L = _lib.lib()
     if on_device:
         scal = torch.empty(2 * nsteps, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.fno_adam_replay_prep(_ptr(scal), int(step_from), int(nsteps), float(lr), float(betas[0]),
-                                              float(betas[1]), _stream()), "adam_replay_prep")
+        _call("adam_replay_prep", device, "fno_adam_replay_prep", scal, int(step_from), int(nsteps), float(lr), float(betas[0]),
+              float(betas[1]), STREAM)
         return scal
-    import ctypes
     host = torch.empty(2 * nsteps, dtype=torch.float32)
-    base = host.data_ptr()
+    base = host.data_ptr()                      # host memory, host-only call: nothing crosses to the device here
     for j in range(nsteps):
-        L.fno_adam_scalars(float(lr), float(betas[0]), float(betas[1]), int(step_from + j), ctypes.c_void_p(base + 8 * j))
+        _lib.lib().fno_adam_scalars(float(lr), float(betas[0]), float(betas[1]), int(step_from + j), C.c_void_p(base + 8 * j))
     return host.to(device)
 
 
@@ -549,71 +630,65 @@ def adam_replay_dead(rows, row_len, live_len, param_block, dead_m, dead_v, momen
     """Take the dead part of a row-sliced block (rows x row_len floats of `param_block`, dead = [live_len, row_len) of each
     row) through the Adam steps described by `scal` (adam_replay_scalars) with a zero gradient; dead_m / dead_v: compact
     dead moments, read unless moments_zero, always written."""
-    for t, name in ((param_block, "param"), (dead_m, "dead exp_avg"), (dead_v, "dead exp_avg_sq"), (scal, "scalars")):
-        _require_cuda(t, name)
-        if not t.is_contiguous() or t.dtype != torch.float32:
-            raise RuntimeError(f"fnoengine adam_replay_dead: `{name}` must be contiguous float32")
+    e = "adam_replay_dead"
+    _require_cuda(param_block, "param")
     nd = rows * (row_len - live_len)
-    if param_block.numel() != rows * row_len or dead_m.numel() != nd or dead_v.numel() != nd or scal.numel() % 2:
-        raise RuntimeError("fnoengine adam_replay_dead: buffer sizes do not match the block")
-    with torch.cuda.device(param_block.device):
-        _lib.check(_lib.lib().fno_adam_replay_dead(rows, row_len, live_len, _ptr(param_block), _ptr(dead_m), _ptr(dead_v),
-                                                   1 if moments_zero else 0, _ptr(scal), scal.numel() // 2, float(betas[0]),
-                                                   float(betas[1]), float(eps), float(weight_decay), _stream()),
-                   "adam_replay_dead")
+    for t, name, n in ((param_block, "param", rows * row_len), (dead_m, "dead exp_avg", nd), (dead_v, "dead exp_avg_sq", nd),
+                       (scal, "scalars", None)):
+        _operand(e, name, t, param_block, numel=n, layout="dense")
+    if scal.numel() % 2:
+        raise RuntimeError(f"fnoengine {e}: `scalars` holds two floats per step (got {scal.numel()} elements)")
+    _call(e, param_block.device, "fno_adam_replay_dead", rows, row_len, live_len, param_block, dead_m, dead_v,
+          1 if moments_zero else 0, scal, scal.numel() // 2, float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+          STREAM)
 
 
 # ----------------------------------------------------------------------------
 # fused block stack: y = B_{L-1}(...B_0(x)),  B_l(u) = [gelu](specconv_l(u) + conv1x1_l(u) + bias_l)
 # ----------------------------------------------------------------------------
+def _block_tail(relu_out, drop_p, seed, y):
+    """FnoBlockTail over checked tensors (seed: two int32 words on the device; y: the forward's output, backward only)"""
+    return _lib.FnoBlockTail(int(relu_out), float(drop_p), _ptr(seed), _ptr(y))
+
+
 class _FNOBlocksFn(torch.autograd.Function):
     """Tensor arguments: x, bias (L, C) or None, skip_w[0..L), spec_w[0..L*ncorner)."""
 
     @staticmethod
     def forward(ctx, cfg, x, bias, *rest):
-        n_layers, modes, norm, gelu_mask, direct = cfg[:5]
-        tail = cfg[5] if len(cfg) > 5 else None      # (relu_out, drop_p, seed tensor or None): fno_model_*_tail
+        n_layers, modes, norm, gelu_mask, direct, _, tail = cfg      # tail: fno_model_*_tail
+        e = "fno_blocks" if tail is None else "fno_block_tail"
         ctx.direct = direct
         _require_cuda(x, "x")
         x = x.contiguous()
         dims = tuple(x.shape[2:])
         ndim = len(dims)
         ncorner = 2 ** (ndim - 1)
-        skip_ws = [t.contiguous() for t in rest[:n_layers]]
-        spec_ws, planes = _weights_ready(rest[n_layers:])
-        ctx.planes = planes
-        assert len(spec_ws) == n_layers * ncorner
-        for t in skip_ws + spec_ws + ([bias] if bias is not None else []):
-            _require_cuda(t, "parameter")
-        sb = bias.contiguous() if bias is not None else None
+        assert len(rest) == n_layers + n_layers * ncorner
         B, c = x.shape[0], x.shape[1]
-        _check_corner_weights(spec_ws, c, c, modes, planes, "fno_blocks")
+        skip_ws = [_operand(e, f"skip weight {l}", t, x, numel=c * c) for l, t in enumerate(rest[:n_layers])]
+        spec_ws, planes = _check_corner_weights(e, rest[n_layers:], x, c, c, modes)
+        ctx.planes = planes
+        sb = _operand(e, "bias", bias, x, numel=n_layers * c, optional=True)
+        seed = None if tail is None else _operand(e, "seed", tail[2], x, dtype=torch.int32, numel=2, optional=True)
         L = _lib.lib()
         plan = model_plan(ndim, 0, c, 0, 0, n_layers, dims, modes, norm, gelu_mask, x.device, weight_planes=planes)
-        prm = _lib.FnoModelParams()
-        for l in range(n_layers):
-            prm.skip_w[l] = skip_ws[l].data_ptr()
-            for k in range(ncorner):
-                prm.spec_w[l][k] = spec_ws[l * ncorner + k].data_ptr()
-        prm.spec_bias = sb.data_ptr() if sb is not None else 0
+        prm = _fill_params(ncorner, skip_ws, spec_ws, sb)
         y = torch.empty_like(x)
         saved = _bytes(L.fno_model_saved_bytes(plan, B), x.device)
         nws = L.fno_model_workspace_bytes(plan, B)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            if tail is None:
-                _lib.check(L.fno_model_forward(plan, B, C.byref(prm), _ptr(x), _ptr(y), _ptr(saved), _ptr(ws), nws,
-                                               _stream()), "blocks_forward")
-            else:
-                relu_out, drop_p, seed = tail
-                t = _lib.FnoBlockTail(int(relu_out), float(drop_p), _ptr(seed), None)
-                _lib.check(L.fno_model_forward_tail(plan, B, C.byref(prm), _ptr(x), _ptr(y), _ptr(saved), _ptr(ws), nws,
-                                                    _stream(), C.byref(t)), "blocks_forward_tail")
+        if tail is None:
+            _call("blocks_forward", x.device, "fno_model_forward", plan, B, C.byref(prm), x, y, saved, ws, nws, STREAM)
+        else:
+            t = _block_tail(tail[0], tail[1], seed, None)
+            _call("blocks_forward_tail", x.device, "fno_model_forward_tail", plan, B, C.byref(prm), x, y, saved, ws, nws, STREAM,
+                  C.byref(t))
         ctx.plan, ctx.B, ctx.n_layers, ctx.ncorner, ctx.has_sb = plan, B, n_layers, ncorner, sb is not None
         ctx.tail = None if tail is None else (bool(tail[0]), float(tail[1]))
         extra = []
         if tail is not None:
-            extra = [y if tail[0] else x.new_empty(0), tail[2] if tail[2] is not None else x.new_empty(0)]
+            extra = [y if tail[0] else x.new_empty(0), seed if seed is not None else x.new_empty(0)]
         ctx.save_for_backward(x, saved, *skip_ws, *spec_ws, *([sb] if sb is not None else []), *extra)
         return y
 
@@ -622,56 +697,35 @@ class _FNOBlocksFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         x, saved = sv[:2]
         nl, nc = ctx.n_layers, ctx.ncorner
-        skip_ws = list(sv[2:2 + nl])
-        spec_ws = list(sv[2 + nl:2 + nl + nl * nc])
-        sb = sv[2 + nl + nl * nc] if ctx.has_sb else None
-        dy = dy.contiguous()
+        skip_ws, spec_ws, sb = _saved_params(sv, 2, nl, nc, ctx.has_sb)
+        dy = _operand("fno_blocks backward", "dy", dy, x)
         L = _lib.lib()
-        prm, grd = _lib.FnoModelParams(), _lib.FnoModelGrads()
         g_skip = [torch.empty_like(t) for t in skip_ws]
         g_spec = ctx.direct if ctx.direct is not None else _fresh_grads(spec_ws, ctx.planes)   # direct: the weights' own .grad storage
         g_sb = torch.empty_like(sb) if sb is not None else None
-        for l in range(nl):
-            prm.skip_w[l], grd.skip_w[l] = skip_ws[l].data_ptr(), g_skip[l].data_ptr()
-            for k in range(nc):
-                prm.spec_w[l][k], grd.spec_w[l][k] = spec_ws[l * nc + k].data_ptr(), g_spec[l * nc + k].data_ptr()
-        prm.spec_bias = sb.data_ptr() if sb is not None else 0
-        grd.spec_bias = g_sb.data_ptr() if g_sb is not None else 0
+        prm, grd = _fill_params(nc, skip_ws, spec_ws, sb), _fill_params(nc, g_skip, g_spec, g_sb)
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         nws = L.fno_model_workspace_bytes(ctx.plan, ctx.B)
         ws = _bytes(nws, dy.device)
-        with torch.cuda.device(dy.device):
-            if ctx.tail is None:
-                _lib.check(L.fno_model_backward_dx(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                   C.byref(grd), _ptr(dx), _ptr(ws), nws, _stream()), "blocks_backward")
-            else:
-                y_out, seed = sv[-2], sv[-1]
-                t = _lib.FnoBlockTail(int(ctx.tail[0]), ctx.tail[1], _ptr(seed) if seed.numel() else None,
-                                      _ptr(y_out) if y_out.numel() else None)
-                _lib.check(L.fno_model_backward_tail(ctx.plan, ctx.B, C.byref(prm), _ptr(x), _ptr(dy), _ptr(saved),
-                                                     C.byref(grd), _ptr(dx), _ptr(ws), nws, _stream(), C.byref(t)),
-                           "blocks_backward_tail")
+        common = (ctx.plan, ctx.B, C.byref(prm), x, dy, saved, C.byref(grd), dx, ws, nws, STREAM)
+        if ctx.tail is None:
+            _call("blocks_backward", dy.device, "fno_model_backward_dx", *common)
+        else:
+            y_out, seed = sv[-2], sv[-1]
+            t = _block_tail(ctx.tail[0], ctx.tail[1], seed if seed.numel() else None, y_out if y_out.numel() else None)
+            _call("blocks_backward_tail", dy.device, "fno_model_backward_tail", *common, C.byref(t))
         if ctx.direct is not None:
             _notify_direct(ctx.direct)
         return (None, dx, g_sb) + tuple(g_skip) + ((None,) * len(g_spec) if ctx.direct is not None else tuple(g_spec))
 
 
 def blocks_supported(x, n_layers=1, modes=None, norm="backward", gelu_mask=0):
-    """Shapes the fused block kernels cover (fno_model_plan_create): 32 / 64 channels, last dim a
-    multiple of 32 (<= 256), planes that tile by 128 (256) pixels; with `modes` the engine itself is asked
-    (tile + twiddle tables must fit LDS)."""
+    """Shapes the fused block kernels cover (fno_model_plan_create): 32 / 64 channels and a grid row_tiling() covers; with
+    `modes` the engine itself is asked (tile + twiddle tables must fit LDS)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() in (4, 5)):
         return False
-    c, w = x.shape[1], x.shape[-1]
-    pw = 1
-    for s in x.shape[2:]:
-        pw *= s
-    npx = 256 if w > 128 else 128
-    tiled = w % 32 == 0 and w <= 256 and npx % w == 0 and pw % npx == 0
-    # "loose rows" (any other last dim in 32..320, e.g. the PINO observers' padded time axis 73, or 96 / 160):
-    # 128-pixel tiles of the flattened plane, spectral rows gathered per tile (split-precision GEMM mode only)
-    loose = (not tiled) and 32 <= w <= 320 and pw % 128 == 0 and _lib.lib().fno_get_gemm_mode() == 1
-    if not (c in (32, 64) and (tiled or loose) and n_layers <= _lib.FNO_MAX_LAYERS):
+    c = x.shape[1]
+    if not (c in (32, 64) and row_tiling(x.shape[2:]) is not None and n_layers <= _lib.FNO_MAX_LAYERS):
         return False
     if modes is None:
         return True
@@ -684,8 +738,7 @@ def block_tail_supported(x, modes, norm):
     floats tiling 128-pixel tiles), in either GEMM mode."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
-    w, pw = x.shape[-1], x.shape[-1] * x.shape[-2]
-    if not (x.shape[1] in (32, 64) and w in (32, 64, 128) and pw % 128 == 0):
+    if not (x.shape[1] in (32, 64) and x.shape[-1] in (32, 64, 128) and plane_size(x.shape) % 128 == 0):
         return False
     return blocks_supported(x, 1, modes, norm)
 
@@ -699,8 +752,8 @@ def draw_dropout_seed(device):
 def dropout_scale(n, drop_p, seed, device):
     """The 0 / 1/(1-p) field the kernels regenerate from `seed` for a tensor of n elements (tests, oracles)."""
     out = torch.empty(n, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().fno_dropout_scale(n, float(drop_p), _ptr(seed), _ptr(out), _stream()), "dropout_scale")
+    seed = _operand("dropout_scale", "seed", seed, out, dtype=torch.int32, numel=2, optional=True)
+    _call("dropout_scale", device, "fno_dropout_scale", n, float(drop_p), seed, out, STREAM)
     return out
 
 
@@ -709,12 +762,12 @@ def fno_block_tail(x, skip_w, spec_ws, bias, modes, norm, relu_out=True, drop_p=
     y = relu(specconv(drop(x)) + skip_w x + bias).  `seed`: draw_dropout_seed() (required when drop_p > 0).  The ReLU, its
     derivative, the dropout mask (regenerated in the backward) and the accumulation of the two branches' input gradients
     all happen inside the engine kernels (fno_model_forward_tail / fno_model_backward_tail)."""
-    sw = [torch.view_as_real(t) if t.is_complex() else t for t in spec_ws]
     direct = _direct_views(direct_grads, spec_ws)
     if drop_p > 0 and seed is None:
         raise ValueError("fno_block_tail: drop_p > 0 needs a seed (draw_dropout_seed)")
-    cfg = (1, tuple(int(m) for m in modes), norm, 0, direct, (bool(relu_out), float(drop_p), seed if drop_p > 0 else None))
-    return _FNOBlocksFn.apply(cfg, x, bias, skip_w, *sw)
+    cfg = _Cfg(1, tuple(int(m) for m in modes), norm, 0, direct,
+               tail=(bool(relu_out), float(drop_p), seed if drop_p > 0 else None))
+    return _FNOBlocksFn.apply(cfg, x, bias, skip_w, *_real_views(spec_ws))
 
 
 def fno_blocks(x, skip_ws, spec_ws, bias, modes, norm, gelu_mask=0, direct_grads=False):
@@ -722,10 +775,9 @@ def fno_blocks(x, skip_ws, spec_ws, bias, modes, norm, gelu_mask=0, direct_grads
     convolution (corner weights `spec_ws`, layer-major, real view (C, C, m.., 2)), one 1x1 convolution
     (`skip_ws[l]`, (C, C) or (C, C, 1..)) and one bias row of `bias` (L, C); GELU after layer l iff bit l
     of `gelu_mask`.  Returns (B, C, ...); differentiable w.r.t. x and every parameter."""
-    sw = [torch.view_as_real(t) if t.is_complex() else t for t in spec_ws]
     direct = _direct_views(direct_grads, spec_ws, last_dim=x.shape[-1])       # backward WRITES dL/dW of the spectral weights into their existing .grad storage
-    cfg = (len(skip_ws), tuple(int(m) for m in modes), norm, int(gelu_mask), direct)
-    return _FNOBlocksFn.apply(cfg, x, bias, *skip_ws, *sw)
+    cfg = _Cfg(len(skip_ws), tuple(int(m) for m in modes), norm, int(gelu_mask), direct)
+    return _FNOBlocksFn.apply(cfg, x, bias, *skip_ws, *_real_views(spec_ws))
 
 
 # ----------------------------------------------------------------------------
@@ -739,38 +791,29 @@ class _FourierFanoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, *rest):
-        n, modes, norm = cfg[:3]
-        ctx.direct = cfg[3] if len(cfg) > 3 else None
+        e = "fourier_fanout"
+        n, modes, norm = cfg.n_layers, cfg.modes, cfg.norm
+        ctx.direct = cfg.direct
         _require_cuda(x, "x")
         x = x.contiguous()
         dims = tuple(x.shape[2:])
         ndim = len(dims)
         nc = 2 ** (ndim - 1)
-        skip_ws = [t.contiguous() for t in rest[:n]]
-        biases = [t.contiguous() for t in rest[n:2 * n]]
-        spec_ws, planes = _weights_ready(rest[2 * n:])
-        ctx.planes = planes
-        assert len(spec_ws) == n * nc and n <= FANOUT_MAX
-        for t in skip_ws + biases + spec_ws:
-            _require_cuda(t, "parameter")
+        assert len(rest) == 2 * n + n * nc and n <= FANOUT_MAX
         B, c = x.shape[0], x.shape[1]
-        _check_corner_weights(spec_ws, c, c, modes, planes, "fourier_fanout")
+        skip_ws = [_operand(e, f"skip weight {j}", t, x, numel=c * c) for j, t in enumerate(rest[:n])]
+        biases = [_operand(e, f"bias {j}", t, x, numel=c) for j, t in enumerate(rest[n:2 * n])]
+        spec_ws, planes = _check_corner_weights(e, rest[2 * n:], x, c, c, modes)
+        ctx.planes = planes
         L = _lib.lib()
         plan = model_plan(ndim, 0, c, 0, 0, FANOUT_MAX, dims, modes, norm, 0, x.device, weight_planes=planes)
-        prm = _lib.FnoModelParams()
-        for j in range(n):
-            prm.skip_w[j] = skip_ws[j].data_ptr()
-            for k in range(nc):
-                prm.spec_w[j][k] = spec_ws[j * nc + k].data_ptr()
+        prm = _fill_params(nc, skip_ws, spec_ws)
         ys = [torch.empty_like(x) for _ in range(n)]
-        bptr = (C.c_void_p * n)(*[b.data_ptr() for b in biases])
-        yptr = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
         saved = _bytes(L.fno_fanout_saved_bytes(plan, B, n), x.device)
         nws = L.fno_fanout_workspace_bytes(plan, B, n)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_fanout_forward(plan, B, n, C.byref(prm), bptr, _ptr(x), yptr, _ptr(saved), _ptr(ws), nws,
-                                            _stream()), "fanout_forward")
+        _call("fanout_forward", x.device, "fno_fanout_forward", plan, B, n, C.byref(prm), _ptr_array(biases), x, _ptr_array(ys),
+              saved, ws, nws, STREAM)
         ctx.plan, ctx.B, ctx.n, ctx.nc = plan, B, n, nc
         ctx.save_for_backward(x, saved, *skip_ws, *spec_ws)
         ctx.bias_shapes = [b.shape for b in rest[n:2 * n]]
@@ -781,25 +824,18 @@ class _FourierFanoutFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         x, saved = sv[:2]
         n, nc = ctx.n, ctx.nc
-        skip_ws, spec_ws = list(sv[2:2 + n]), list(sv[2 + n:])
-        dys = [torch.zeros_like(x) if d is None else d.contiguous() for d in dys]
+        skip_ws, spec_ws, _ = _saved_params(sv, 2, n, nc)
+        dys = [torch.zeros_like(x) if d is None else _operand("fourier_fanout backward", "dy", d, x, numel=x.numel()) for d in dys]
         L = _lib.lib()
-        prm, grd = _lib.FnoModelParams(), _lib.FnoModelGrads()
         g_skip = [torch.empty_like(t) for t in skip_ws]
         g_spec = ctx.direct if ctx.direct is not None else _fresh_grads(spec_ws, ctx.planes)     # direct: the weights' own .grad storage
         g_bias = [torch.empty(x.shape[1], dtype=torch.float32, device=x.device) for _ in range(n)]
-        for j in range(n):
-            prm.skip_w[j], grd.skip_w[j] = skip_ws[j].data_ptr(), g_skip[j].data_ptr()
-            for k in range(nc):
-                prm.spec_w[j][k], grd.spec_w[j][k] = spec_ws[j * nc + k].data_ptr(), g_spec[j * nc + k].data_ptr()
-        dyptr = (C.c_void_p * n)(*[d.data_ptr() for d in dys])
-        dbptr = (C.c_void_p * n)(*[b.data_ptr() for b in g_bias])
+        prm, grd = _fill_params(nc, skip_ws, spec_ws), _fill_params(nc, g_skip, g_spec)
         dx = torch.empty_like(x)
         nws = L.fno_fanout_workspace_bytes(ctx.plan, ctx.B, n)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_fanout_backward(ctx.plan, ctx.B, n, C.byref(prm), _ptr(x), dyptr, _ptr(saved), C.byref(grd), dbptr,
-                                             _ptr(dx), _ptr(ws), nws, _stream()), "fanout_backward")
+        _call("fanout_backward", x.device, "fno_fanout_backward", ctx.plan, ctx.B, n, C.byref(prm), x, _ptr_array(dys), saved,
+              C.byref(grd), _ptr_array(g_bias), dx, ws, nws, STREAM)
         g_bias = [g.view(sh) for g, sh in zip(g_bias, ctx.bias_shapes)]
         if ctx.direct is not None:
             _notify_direct(ctx.direct)
@@ -818,8 +854,7 @@ def fourier_fanout(x, skip_ws, biases, spec_ws, modes, norm, direct_grads=False)
     """[SpecConv_j(x) + conv1x1(x; skip_ws[j]) + biases[j] for j < n]: n <= 4 Fourier layers (rno.py:215-228) on ONE input,
     whose forward transforms run once and whose input gradients are summed inside the backward kernels
     (include/fnoengine.h, fno_fanout_*).  spec_ws is member-major: member j's corner weights at [j * ncorner, (j+1) * ncorner)."""
-    n = len(skip_ws)
-    cfg = (n, tuple(int(m) for m in modes), norm, _direct_views(direct_grads, spec_ws))
+    cfg = _Cfg(len(skip_ws), tuple(int(m) for m in modes), norm, 0, _direct_views(direct_grads, spec_ws))
     return _FourierFanoutFn.apply(cfg, x, *skip_ws, *biases, *spec_ws)
 
 
@@ -829,22 +864,20 @@ def fourier_fanout(x, skip_ws, biases, spec_ws, modes, norm, direct_grads=False)
 class _PinoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, u0, forcing, visc, t_interval):
-        for t, name in ((u, "u"), (u0, "u0"), (forcing, "forcing"), (visc, "visc")):
-            _require_cuda(t, name)
+        e = "pino_loss"
+        _require_cuda(u, "u")
         B, n, n2, nt = u.shape
         if n != n2:
-            raise RuntimeError(f"fnoengine pino_loss: square grids only (got {n} x {n2})")
-        u_c, u0_c = u.contiguous(), u0.reshape(B, n, n).contiguous()
-        f_c = forcing.reshape(n, n).contiguous()
-        v_c = visc.reshape(B).contiguous()
-        L = _lib.lib()
-        nws = L.fno_pino_loss_workspace_bytes(B, n, nt)
+            raise RuntimeError(f"fnoengine {e}: square grids only (got {n} x {n2})")
+        u_c = u.contiguous()
+        u0_c = _operand(e, "u0", u0, u, numel=B * n * n).reshape(B, n, n)
+        f_c = _operand(e, "forcing", forcing, u, numel=n * n).reshape(n, n)
+        v_c = _operand(e, "visc", visc, u, numel=B).reshape(B)
+        nws = _lib.lib().fno_pino_loss_workspace_bytes(B, n, nt)
         ws = _bytes(nws, u.device)
         losses = torch.empty(2, dtype=torch.float32, device=u.device)
-        with torch.cuda.device(u.device):
-            _lib.check(L.fno_pino_loss_forward(B, n, nt, _ptr(u_c), _ptr(u0_c), _ptr(f_c), _ptr(v_c), float(t_interval),
-                                               _ptr(losses[0:1]), _ptr(losses[1:2]), _ptr(ws), nws, _stream()),
-                       "pino_loss_forward")
+        _call("pino_loss_forward", u.device, "fno_pino_loss_forward", B, n, nt, u_c, u0_c, f_c, v_c, float(t_interval),
+              losses[0:1], losses[1:2], ws, nws, STREAM)
         ctx.save_for_backward(u_c, u0_c, f_c, v_c, ws)
         ctx.meta = (B, n, nt, float(t_interval), nws, u.shape)
         return losses[0], losses[1]
@@ -853,14 +886,11 @@ class _PinoLossFn(torch.autograd.Function):
     def backward(ctx, g_ic, g_f):
         u_c, u0_c, f_c, v_c, ws = ctx.saved_tensors
         B, n, nt, t_interval, nws, shape = ctx.meta
-        L = _lib.lib()
         du = torch.empty_like(u_c)
-        gi = g_ic.contiguous().to(torch.float32).reshape(1)
-        gf = g_f.contiguous().to(torch.float32).reshape(1)
-        with torch.cuda.device(du.device):
-            _lib.check(L.fno_pino_loss_backward(B, n, nt, _ptr(u_c), _ptr(u0_c), _ptr(f_c), _ptr(v_c), t_interval,
-                                                _ptr(gi), _ptr(gf), _ptr(du), _ptr(ws), nws, _stream()),
-                       "pino_loss_backward")
+        gi = _operand("pino_loss backward", "g_ic", g_ic.contiguous().to(torch.float32), u_c, numel=1).reshape(1)
+        gf = _operand("pino_loss backward", "g_f", g_f.contiguous().to(torch.float32), u_c, numel=1).reshape(1)
+        _call("pino_loss_backward", du.device, "fno_pino_loss_backward", B, n, nt, u_c, u0_c, f_c, v_c, t_interval, gi, gf, du,
+              ws, nws, STREAM)
         return du.view(shape), None, None, None, None
 
 
@@ -928,39 +958,38 @@ def chanflow_rhs(grid, U, V, W, dPdx):
     """Fu, Fv, Fw = NSControlEnvMatlab.compute_rhs_py(U, V, W, dPdx) (libs/envs/control_env.py:429-530) for a batch of
     fields: U, W (B, Nx, Ny+1, Nz), V (B, Nx, Ny, Nz), fp32 or fp64; dPdx a float or a (B,) tensor.  Not differentiable
     (the reference uses it under autograd only through pde_loss -> chanflow_pde_loss)."""
-    grid._check_fields(U, V, W, "chanflow_rhs")
-    if U.dtype not in (torch.float32, torch.float64) or V.dtype != U.dtype or W.dtype != U.dtype:
-        raise RuntimeError("fnoengine chanflow_rhs: U, V, W must share one dtype, float32 or float64")
-    U, V, W = U.contiguous(), V.contiguous(), W.contiguous()
+    e = "chanflow_rhs"
+    grid._check_fields(U, V, W, e)
+    if U.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"fnoengine {e}: U, V, W must share one dtype, float32 or float64")
+    U, V, W = (_operand(e, n, t, U, dtype=U.dtype) for n, t in (("U", U), ("V", V), ("W", W)))
     B = U.shape[0]
     dp, dflt = None, 0.0
     if torch.is_tensor(dPdx) and dPdx.numel() > 1:
-        dp = dPdx.to(device=U.device, dtype=U.dtype).reshape(B).contiguous()
+        dp = _operand(e, "dPdx", dPdx.to(device=U.device, dtype=U.dtype), U, dtype=U.dtype, numel=B).reshape(B)
     else:
         dflt = float(dPdx)
     Fu, Fv, Fw = torch.empty_like(U), torch.empty_like(V), torch.empty_like(W)
     g = grid.desc()
-    with torch.cuda.device(U.device):
-        _lib.check(_lib.lib().fno_chanflow_rhs(C.byref(g), B, 0 if U.dtype == torch.float32 else 1, _ptr(grid.metrics(U.device)),
-                                               _ptr(U), _ptr(V), _ptr(W), _ptr(dp), dflt, _ptr(Fu), _ptr(Fv), _ptr(Fw),
-                                               _stream()), "chanflow_rhs")
+    m = _operand(e, "grid metrics", grid.metrics(U.device), U, dtype=torch.float64, numel=3 * (grid.Ny + 2))
+    _call(e, U.device, "fno_chanflow_rhs", C.byref(g), B, 0 if U.dtype == torch.float32 else 1, m, U, V, W, dp, dflt, Fu, Fv, Fw,
+          STREAM)
     return Fu, Fv, Fw
 
 
 class _ChanflowPdeLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid, U, Vgt, V, W):
+        e = "chanflow_pde_loss"
         B = U.shape[0]
-        U, Vgt, V, W = U.contiguous(), Vgt.contiguous(), V.contiguous(), W.contiguous()
-        L = _lib.lib()
+        U, Vgt, V, W = (_operand(e, n, t, U) for n, t in (("U", U), ("Vgt", Vgt), ("V", V), ("W", W)))
         g = grid.desc()
-        nws = L.fno_chanflow_pde_loss_workspace_bytes(C.byref(g), B)
+        nws = _lib.lib().fno_chanflow_pde_loss_workspace_bytes(C.byref(g), B)
         ws = _bytes(nws, U.device)
         loss = torch.empty(1, dtype=torch.float32, device=U.device)
-        m = grid.metrics(U.device)
-        with torch.cuda.device(U.device):
-            _lib.check(L.fno_chanflow_pde_loss_forward(C.byref(g), B, _ptr(m), _ptr(U), _ptr(Vgt), _ptr(V), _ptr(W), _ptr(loss),
-                                                       _ptr(ws), nws, _stream()), "chanflow_pde_loss_forward")
+        m = _operand(e, "grid metrics", grid.metrics(U.device), U, dtype=torch.float64, numel=3 * (grid.Ny + 2))
+        _call("chanflow_pde_loss_forward", U.device, "fno_chanflow_pde_loss_forward", C.byref(g), B, m, U, Vgt, V, W, loss, ws,
+              nws, STREAM)
         ctx.save_for_backward(U, Vgt, V, W, ws, m)
         ctx.meta = (grid, B, nws)
         return loss[0]
@@ -971,11 +1000,9 @@ class _ChanflowPdeLossFn(torch.autograd.Function):
         grid, B, nws = ctx.meta
         g = grid.desc()
         dV = torch.empty_like(V)
-        glc = gl.contiguous().to(torch.float32).reshape(1)
-        with torch.cuda.device(V.device):
-            _lib.check(_lib.lib().fno_chanflow_pde_loss_backward(C.byref(g), B, _ptr(m), _ptr(U), _ptr(Vgt), _ptr(V), _ptr(W),
-                                                                 _ptr(glc), _ptr(dV), _ptr(ws), nws, _stream()),
-                       "chanflow_pde_loss_backward")
+        glc = _operand("chanflow_pde_loss backward", "gl", gl.contiguous().to(torch.float32), V, numel=1).reshape(1)
+        _call("chanflow_pde_loss_backward", V.device, "fno_chanflow_pde_loss_backward", C.byref(g), B, m, U, Vgt, V, W, glc, dV,
+              ws, nws, STREAM)
         return None, None, None, dV, None
 
 
@@ -986,8 +1013,7 @@ def chanflow_pde_loss(grid, U, Vgt, V, W):
     grid._check_fields(U, V, W, "chanflow_pde_loss")
     if tuple(Vgt.shape) != tuple(V.shape):
         raise RuntimeError(f"fnoengine chanflow_pde_loss: Vgt {tuple(Vgt.shape)} must match V {tuple(V.shape)}")
-    for t, n in ((U, "U"), (Vgt, "Vgt"), (V, "V"), (W, "W")):
-        _require_cuda(t, n)
+    _require_cuda(U, "U")
     return _ChanflowPdeLossFn.apply(grid, U, Vgt, V, W)
 
 
@@ -999,29 +1025,31 @@ def gates_supported(*tensors):
     return all(t.is_cuda and t.dtype == torch.float32 and t.shape == t0.shape for t in tensors) and t0.numel() % 4 == 0
 
 
+def _gate_operands(e, h, fields, scalars):
+    """the operands of an RNO gate: `fields` (name -> tensor) of the state's shape, `scalars` (name -> tensor) one float each"""
+    _require_cuda(h, "h")
+    return ([_operand(e, n, t, h, shape=h.shape) for n, t in fields] + [h.contiguous()],
+            [_operand(e, n, t, h, numel=1) for n, t in scalars])
+
+
 class _RnoResetGateFn(torch.autograd.Function):
     """rh = sigmoid(a3 + a4 + b2) * h."""
 
     @staticmethod
     def forward(ctx, a3, a4, b2, h):
-        if not (a3.shape == a4.shape == h.shape):
-            raise RuntimeError(f"fnoengine rno_reset_gate: operands of shapes {tuple(a3.shape)}, {tuple(a4.shape)}, {tuple(h.shape)}")
-        a3, a4, h = a3.contiguous(), a4.contiguous(), h.contiguous()
+        (a3, a4, h), (b2,) = _gate_operands("rno_reset_gate", h, (("a3", a3), ("a4", a4)), (("b2", b2),))
         r, rh = torch.empty_like(h), torch.empty_like(h)
-        _lib.check(_lib.lib().fno_rno_reset_gate_forward(h.numel(), _ptr(a3), _ptr(a4), _ptr(b2), _ptr(h), _ptr(r), _ptr(rh),
-                                                         _stream()), "rno_reset_gate_forward")
+        _call("rno_reset_gate_forward", h.device, "fno_rno_reset_gate_forward", h.numel(), a3, a4, b2, h, r, rh, STREAM)
         ctx.save_for_backward(r, h)
         return rh
 
     @staticmethod
     def backward(ctx, d_rh):
         r, h = ctx.saved_tensors
-        L = _lib.lib()
-        d_rh = d_rh.contiguous()
+        d_rh = _operand("rno_reset_gate backward", "d_rh", d_rh, h, shape=h.shape)
         ds, dh = torch.empty_like(h), torch.empty_like(h)
-        part = torch.empty(L.fno_rno_gate_partials(), dtype=torch.float64, device=h.device)
-        _lib.check(L.fno_rno_reset_gate_backward(h.numel(), _ptr(d_rh), _ptr(r), _ptr(h), _ptr(ds), _ptr(dh), _ptr(part),
-                                                 _stream()), "rno_reset_gate_backward")
+        part = torch.empty(_lib.lib().fno_rno_gate_partials(), dtype=torch.float64, device=h.device)
+        _call("rno_reset_gate_backward", h.device, "fno_rno_reset_gate_backward", h.numel(), d_rh, r, h, ds, dh, part, STREAM)
         return ds, ds, part.sum().float().reshape(()), dh
 
 
@@ -1030,26 +1058,24 @@ class _RnoOutputGateFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a1, a2, b1, a7, a8, b4, a5, a6, b3, h):
-        if any(t.shape != h.shape for t in (a1, a2, a7, a8, a5, a6)):
-            raise RuntimeError(f"fnoengine rno_output_gate: operands must all have the state's shape {tuple(h.shape)}")
-        a1, a2, a7, a8, a5, a6, h = [t.contiguous() for t in (a1, a2, a7, a8, a5, a6, h)]
+        (a1, a2, a7, a8, a5, a6, h), (b1, b4, b3) = _gate_operands(
+            "rno_output_gate", h, (("a1", a1), ("a2", a2), ("a7", a7), ("a8", a8), ("a5", a5), ("a6", a6)),
+            (("b1", b1), ("b4", b4), ("b3", b3)))
         z, z2, s3, hn = (torch.empty_like(h) for _ in range(4))
-        _lib.check(_lib.lib().fno_rno_output_gate_forward(h.numel(), _ptr(a1), _ptr(a2), _ptr(b1), _ptr(a7), _ptr(a8), _ptr(b4),
-                                                          _ptr(a5), _ptr(a6), _ptr(b3), _ptr(h), _ptr(z), _ptr(z2), _ptr(s3),
-                                                          _ptr(hn), _stream()), "rno_output_gate_forward")
+        _call("rno_output_gate_forward", h.device, "fno_rno_output_gate_forward", h.numel(), a1, a2, b1, a7, a8, b4, a5, a6, b3, h,
+              z, z2, s3, hn, STREAM)
         ctx.save_for_backward(z, z2, s3, h)
         return hn
 
     @staticmethod
     def backward(ctx, g):
         z, z2, s3, h = ctx.saved_tensors
-        L = _lib.lib()
-        g = g.contiguous()
+        g = _operand("rno_output_gate backward", "g", g, h, shape=h.shape)
         d1, d7, d3, dh = (torch.empty_like(h) for _ in range(4))
-        P = L.fno_rno_gate_partials()
+        P = _lib.lib().fno_rno_gate_partials()
         part = torch.empty(3, P, dtype=torch.float64, device=h.device)
-        _lib.check(L.fno_rno_output_gate_backward(h.numel(), _ptr(g), _ptr(z), _ptr(z2), _ptr(s3), _ptr(h), _ptr(d1), _ptr(d7),
-                                                  _ptr(d3), _ptr(dh), _ptr(part), _stream()), "rno_output_gate_backward")
+        _call("rno_output_gate_backward", h.device, "fno_rno_output_gate_backward", h.numel(), g, z, z2, s3, h, d1, d7, d3, dh,
+              part, STREAM)
         db = part.sum(dim=1).float()
         return d1, d1, db[0].reshape(()), d7, d7, db[1].reshape(()), d3, d3, db[2].reshape(()), dh
 
@@ -1068,30 +1094,22 @@ def rno_output_gate(a1, a2, b1, a7, a8, b4, a5, a6, b3, h):
 def pointwise_supported(x):
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3):
         return False
-    pw = 1
-    for s in x.shape[2:]:
-        pw *= s
-    return x.shape[1] in (32, 64) and pw % 128 == 0
+    return x.shape[1] in (32, 64) and plane_size(x.shape) % 128 == 0
 
 
 class _PointwiseAddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, addend):
+        e = "pointwise_conv_add"
         _require_cuda(x, "x")
         x = x.contiguous()
         B, Cc = x.shape[0], x.shape[1]
         pw = x.numel() // (B * Cc)
-        w2 = w.reshape(Cc, Cc).contiguous()
-        if addend is not None and addend.shape != x.shape:
-            raise RuntimeError(f"fnoengine pointwise_conv_add: addend of shape {tuple(addend.shape)} for x of shape {tuple(x.shape)}")
-        if bias is not None and bias.numel() != Cc:
-            raise RuntimeError(f"fnoengine pointwise_conv_add: bias of {bias.numel()} elements for {Cc} channels")
-        add_c = addend.contiguous() if addend is not None else None
-        b_c = bias.contiguous() if bias is not None else None
+        w2 = _operand(e, "w", w, x, numel=Cc * Cc).reshape(Cc, Cc)
+        add_c = _operand(e, "addend", addend, x, shape=x.shape, optional=True)
+        b_c = _operand(e, "bias", bias, x, numel=Cc, optional=True)
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().fno_pointwise_forward(B, Cc, pw, _ptr(x), _ptr(w2), _ptr(b_c), _ptr(add_c), 0, _ptr(y),
-                                                        _stream()), "pointwise_forward")
+        _call("pointwise_forward", x.device, "fno_pointwise_forward", B, Cc, pw, x, w2, b_c, add_c, 0, y, STREAM)
         ctx.save_for_backward(x, w2)
         ctx.meta = (B, Cc, pw, w.shape, bias is not None, addend is not None)
         return y
@@ -1100,16 +1118,13 @@ class _PointwiseAddFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w2 = ctx.saved_tensors
         B, Cc, pw, wshape, has_b, has_add = ctx.meta
-        L = _lib.lib()
-        dy = dy.contiguous()
+        dy = _operand("pointwise_conv_add backward", "dy", dy, x, numel=x.numel())
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w2)
         db = torch.empty(Cc, dtype=torch.float32, device=x.device) if has_b else None
-        nws = L.fno_pointwise_workspace_bytes(Cc)
+        nws = _lib.lib().fno_pointwise_workspace_bytes(Cc)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_pointwise_backward(B, Cc, pw, _ptr(x), _ptr(w2), _ptr(dy), None, 0, _ptr(dx), _ptr(dw), _ptr(db),
-                                                _ptr(ws), nws, _stream()), "pointwise_backward")
+        _call("pointwise_backward", x.device, "fno_pointwise_backward", B, Cc, pw, x, w2, dy, None, 0, dx, dw, db, ws, nws, STREAM)
         return dx, dw.view(wshape), db, (dy if has_add else None)
 
 
@@ -1126,18 +1141,16 @@ class _PointwisePerSampleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias):
+        e = "pointwise_conv_per_sample_bias"
         _require_cuda(x, "x")
         x = x.contiguous()
         B, Cc = x.shape[0], x.shape[1]
         pw = x.numel() // (B * Cc)
-        w2 = w.reshape(Cc, Cc).contiguous()
-        bc = bias.contiguous()
+        w2 = _operand(e, "w", w, x, numel=Cc * Cc).reshape(Cc, Cc)
+        bc = _operand(e, "bias", bias, x, shape=(B, Cc))
         y = torch.empty_like(x)
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            for b in range(B):
-                _lib.check(L.fno_pointwise_forward(1, Cc, pw, _ptr(x[b]), _ptr(w2), _ptr(bc[b]), None, 0, _ptr(y[b]), _stream()),
-                           "pointwise_forward")
+        for b in range(B):
+            _call("pointwise_forward", x.device, "fno_pointwise_forward", 1, Cc, pw, x[b], w2, bc[b], None, 0, y[b], STREAM)
         ctx.save_for_backward(x, w2)
         ctx.meta = (B, Cc, pw, w.shape)
         return y
@@ -1146,18 +1159,15 @@ class _PointwisePerSampleFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w2 = ctx.saved_tensors
         B, Cc, pw, wshape = ctx.meta
-        L = _lib.lib()
-        dy = dy.contiguous()
+        dy = _operand("pointwise_conv_per_sample_bias backward", "dy", dy, x, numel=x.numel())
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dws = torch.empty((B, Cc, Cc), dtype=torch.float32, device=x.device)
         dbs = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
-        nws = L.fno_pointwise_workspace_bytes(Cc)
+        nws = _lib.lib().fno_pointwise_workspace_bytes(Cc)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            for b in range(B):
-                _lib.check(L.fno_pointwise_backward(1, Cc, pw, _ptr(x[b]), _ptr(w2), _ptr(dy[b]), None, 0,
-                                                    _ptr(dx[b]) if dx is not None else None, _ptr(dws[b]), _ptr(dbs[b]), _ptr(ws), nws,
-                                                    _stream()), "pointwise_backward")
+        for b in range(B):
+            _call("pointwise_backward", x.device, "fno_pointwise_backward", 1, Cc, pw, x[b], w2, dy[b], None, 0,
+                  dx[b] if dx is not None else None, dws[b], dbs[b], ws, nws, STREAM)
         return dx, dws.sum(0).view(wshape), dbs
 
 
@@ -1166,26 +1176,36 @@ def pointwise_conv_per_sample_bias(x, w, bias):
     return _PointwisePerSampleFn.apply(x, w, bias)
 
 
+# ----------------------------------------------------------------------------
+# lifting layer  y = W x + b,  (B, Cin <= 4, ...) -> (B, C, ...); bias one row (C) or one row per sample (B, C)
+# ----------------------------------------------------------------------------
+def lifting_supported(x, c_out):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and 1 <= x.shape[1] <= 4 and c_out in (32, 64)):
+        return False
+    return plane_size(x.shape) % 128 == 0
+
+
+def _lifting_operands(e, x, w, bias, per_sample):
+    """-> x contiguous, (B, cin, cout, pw), w (cout, cin), bias (None allowed unless per_sample)"""
+    _require_cuda(x, "x")
+    if x.requires_grad:
+        raise RuntimeError("fnoengine lifting: the input field is data (no gradient is produced for it)")
+    x = x.contiguous()
+    B, cin, cout = x.shape[0], x.shape[1], w.shape[0]
+    wc = _operand(e, "w", w, x, numel=cout * cin).reshape(cout, cin)
+    bc = _operand(e, "bias", bias, x, shape=(B, cout)) if per_sample else _operand(e, "bias", bias, x, numel=cout, optional=True)
+    return x, (B, cin, cout, x.numel() // (B * cin)), wc, bc
+
+
 class _LiftingPerSampleFn(torch.autograd.Function):
     """lifting with a per-sample bias row (B, C): one fno_lifting_* call per sample (see _PointwisePerSampleFn)."""
 
     @staticmethod
     def forward(ctx, x, w, bias):
-        _require_cuda(x, "x")
-        if x.requires_grad:
-            raise RuntimeError("fnoengine lifting: the input field is data (no gradient is produced for it)")
-        x = x.contiguous()
-        B, cin = x.shape[0], x.shape[1]
-        cout = w.shape[0]
-        pw = x.numel() // (B * cin)
-        wc = w.reshape(cout, cin).contiguous()
-        bc = bias.contiguous()
+        x, (B, cin, cout, pw), wc, bc = _lifting_operands("lifting_per_sample_bias", x, w, bias, True)
         y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            for b in range(B):
-                _lib.check(L.fno_lifting_forward(1, cin, cout, pw, _ptr(x[b]), _ptr(wc), _ptr(bc[b]), _ptr(y[b]), _stream()),
-                           "lifting_forward")
+        for b in range(B):
+            _call("lifting_forward", x.device, "fno_lifting_forward", 1, cin, cout, pw, x[b], wc, bc[b], y[b], STREAM)
         ctx.save_for_backward(x)
         ctx.meta = (B, cin, cout, pw, w.shape)
         return y
@@ -1194,22 +1214,48 @@ class _LiftingPerSampleFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         B, cin, cout, pw, wshape = ctx.meta
-        L = _lib.lib()
-        dy = dy.contiguous()
+        dy = _operand("lifting_per_sample_bias backward", "dy", dy, x, numel=B * cout * pw)
         dws = torch.empty((B, cout, cin), dtype=torch.float32, device=x.device)
         dbs = torch.empty((B, cout), dtype=torch.float32, device=x.device)
-        nws = L.fno_lifting_workspace_bytes(cout)
+        nws = _lib.lib().fno_lifting_workspace_bytes(cout)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            for b in range(B):
-                _lib.check(L.fno_lifting_backward(1, cin, cout, pw, _ptr(x[b]), _ptr(dy[b]), _ptr(dws[b]), _ptr(dbs[b]), _ptr(ws), nws,
-                                                  _stream()), "lifting_backward")
+        for b in range(B):
+            _call("lifting_backward", x.device, "fno_lifting_backward", 1, cin, cout, pw, x[b], dy[b], dws[b], dbs[b], ws, nws,
+                  STREAM)
         return None, dws.sum(0).view(wshape), dbs
 
 
 def lifting_per_sample_bias(x, w, bias):
     """y[b] = conv1x1(x[b]; w) + bias[b]: x (B, Cin <= 4, ...) data, w (C, Cin), bias (B, C)."""
     return _LiftingPerSampleFn.apply(x, w, bias)
+
+
+class _LiftingFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        x, (B, cin, cout, pw), wc, bc = _lifting_operands("lifting", x, w, bias, False)
+        y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        _call("lifting_forward", x.device, "fno_lifting_forward", B, cin, cout, pw, x, wc, bc, y, STREAM)
+        ctx.save_for_backward(x)
+        ctx.meta = (B, cin, cout, pw, w.shape, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        B, cin, cout, pw, wshape, has_b = ctx.meta
+        dy = _operand("lifting backward", "dy", dy, x, numel=B * cout * pw)
+        dw = torch.empty(cout, cin, dtype=torch.float32, device=x.device)
+        db = torch.empty(cout, dtype=torch.float32, device=x.device) if has_b else None
+        nws = _lib.lib().fno_lifting_workspace_bytes(cout)
+        ws = _bytes(nws, x.device)
+        _call("lifting_backward", x.device, "fno_lifting_backward", B, cin, cout, pw, x, dy, dw, db, ws, nws, STREAM)
+        return None, dw.view(wshape), db
+
+
+def lifting(x, w, bias=None):
+    """conv1x1 from <= 4 input channels: x (B, Cin, ...) data, w (C, Cin[, 1..]), bias (C)."""
+    return _LiftingFn.apply(x, w, bias)
 
 
 class _ZeroLastPadsFn(torch.autograd.Function):
@@ -1250,15 +1296,8 @@ def spectral_layer_supported(u, n_spec_weights, modes, norm, weight_last_extent,
     if not pointwise_supported(u) or n_spec_weights != 2 ** (u.dim() - 3):
         return False
     key = ("layer", u.dim() - 2, u.shape[1], tuple(u.shape[2:]), tuple(modes), weight_last_extent, norm, u.device.index, bool(input_gelu))
-    ok = _spec_plans.get(key)
-    if ok is None:
-        try:
-            spec_plan(u.dim() - 2, u.shape[1], u.shape[1], tuple(u.shape[2:]), modes, weight_last_extent, norm, u.device, input_gelu)
-            ok = True
-        except RuntimeError:
-            ok = False
-        _spec_plans[key] = ok
-    return ok
+    return _plan_available(_spec_plans, key, spec_plan, u.dim() - 2, u.shape[1], u.shape[1], tuple(u.shape[2:]), modes,
+                           weight_last_extent, norm, u.device, input_gelu)
 
 
 class _SpectralLayerFn(torch.autograd.Function):
@@ -1268,27 +1307,27 @@ class _SpectralLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, w, bias, modes, norm, wle, input_gelu, direct, *spec_ws):
+        e = "spectral_pointwise_layer"
         _require_cuda(u, "u")
         u = u.contiguous()
         B, Cc = u.shape[0], u.shape[1]
         dims = tuple(u.shape[2:])
         pw = u.numel() // (B * Cc)
-        ws_list, planes = _weights_ready(spec_ws)
+        if len(spec_ws) != 2 ** (len(dims) - 1) or len(modes) != len(dims):
+            raise RuntimeError(f"fnoengine {e}: {len(spec_ws)} corner weights / {len(modes)} mode counts for {len(dims)}-d data")
+        ws_list, planes = _check_corner_weights(e, spec_ws, u, Cc, Cc, modes, last=wle)
         ctx.planes = planes
+        w2 = _operand(e, "w", w, u, numel=Cc * Cc).reshape(Cc, Cc)
+        b_c = _operand(e, "bias", bias, u, numel=Cc, optional=True)
         L = _lib.lib()
         plan = spec_plan(len(dims), Cc, Cc, dims, modes, wle, norm, u.device, input_gelu, weight_planes=planes)
         sp = torch.empty_like(u)
         xhat = _bytes(L.fno_spec_xhat_bytes(plan, B), u.device)
         nws = L.fno_spec_workspace_bytes(plan, B)
         ws = _bytes(nws, u.device)
-        wp = (C.c_void_p * 4)(*[t.data_ptr() for t in ws_list] + [0] * (4 - len(ws_list)))
-        w2 = w.reshape(Cc, Cc).contiguous()
-        b_c = bias.contiguous() if bias is not None else None
         y = torch.empty_like(u)
-        with torch.cuda.device(u.device):
-            _lib.check(L.fno_spec_forward(plan, B, _ptr(u), wp, None, _ptr(sp), _ptr(xhat), _ptr(ws), nws, _stream()), "spec_forward")
-            _lib.check(L.fno_pointwise_forward(B, Cc, pw, _ptr(u), _ptr(w2), _ptr(b_c), _ptr(sp), 1 if input_gelu else 0, _ptr(y),
-                                               _stream()), "pointwise_forward")
+        _call("spec_forward", u.device, "fno_spec_forward", plan, B, u, _ptr_array(ws_list, 4), None, sp, xhat, ws, nws, STREAM)
+        _call("pointwise_forward", u.device, "fno_pointwise_forward", B, Cc, pw, u, w2, b_c, sp, 1 if input_gelu else 0, y, STREAM)
         ctx.plan, ctx.meta, ctx.direct = plan, (B, Cc, pw, w.shape, bias is not None, bool(input_gelu)), direct
         ctx.save_for_backward(u, w2, xhat, *ws_list)
         return y
@@ -1298,7 +1337,7 @@ class _SpectralLayerFn(torch.autograd.Function):
         u, w2, xhat, *ws_list = ctx.saved_tensors
         B, Cc, pw, wshape, has_b, input_gelu = ctx.meta
         L = _lib.lib()
-        dy = dy.contiguous()
+        dy = _operand("spectral_pointwise_layer backward", "dy", dy, u, numel=u.numel())
         need_du = ctx.needs_input_grad[0]
         need_dws = any(ctx.needs_input_grad[8:])
         direct = ctx.direct if need_dws else None
@@ -1311,12 +1350,10 @@ class _SpectralLayerFn(torch.autograd.Function):
         ws = _bytes(nws, u.device)
         nws2 = L.fno_pointwise_workspace_bytes(Cc)
         ws2 = _bytes(nws2, u.device)
-        dwp = (C.c_void_p * 4)(*[t.data_ptr() for t in dws] + [0] * (4 - len(dws))) if need_dws else None
-        with torch.cuda.device(u.device):
-            _lib.check(L.fno_spec_backward(ctx.plan, B, _ptr(dy), _ptr(xhat), None, _ptr(da), dwp, None, _ptr(ws), nws, _stream()),
-                       "spec_backward")
-            _lib.check(L.fno_pointwise_backward(B, Cc, pw, _ptr(u), _ptr(w2), _ptr(dy), _ptr(da), 1 if input_gelu else 0, _ptr(du),
-                                                _ptr(dw), _ptr(db), _ptr(ws2), nws2, _stream()), "pointwise_backward")
+        _call("spec_backward", u.device, "fno_spec_backward", ctx.plan, B, dy, xhat, None, da, _ptr_array(dws, 4), None, ws, nws,
+              STREAM)
+        _call("pointwise_backward", u.device, "fno_pointwise_backward", B, Cc, pw, u, w2, dy, da, 1 if input_gelu else 0, du, dw,
+              db, ws2, nws2, STREAM)
         gw = (None,) * len(ws_list) if (direct is not None or not need_dws) else tuple(dws)
         if direct is not None:
             _notify_direct(direct)
@@ -1328,7 +1365,7 @@ def spectral_pointwise_layer(u, spec_weights, modes, norm, w, bias, input_gelu=F
     """y = SpectralConv(a) + Conv1d_{k=1}(a; w) + bias with a = gelu(u) if input_gelu else u: one layer of the observer
     stacks (libs/models/pino_models/pinobserver.py:221-226) with the PREVIOUS layer's activation applied while u is
     loaded, so a stack is chained on pre-activation tensors.  Check spectral_layer_supported() first."""
-    sw = [torch.view_as_real(t) if t.is_complex() else t for t in spec_weights]
+    sw = _real_views(spec_weights)
     wle = int(weight_last_extent) if weight_last_extent is not None else int(sw[0].shape[-2])
     direct = _direct_views(direct_grads, spec_weights, last_dim=u.shape[-1])
     return _SpectralLayerFn.apply(u, w, bias, tuple(int(m) for m in modes), norm, wle, bool(input_gelu), direct, *sw)
@@ -1338,6 +1375,7 @@ def spectral_pointwise_layer(u, spec_weights, modes, norm, w, bias, input_gelu=F
 # projection head  y = W2 gelu(W1 x + b1) + b2  on (B, C, ...) tensors
 # ----------------------------------------------------------------------------
 PROJ_MAXCO = 4        # k_projection.h
+_ACT_CODES = {"gelu": 0, "relu": 1}      # FNO_ACT_* (include/fnoengine.h)
 
 
 def projection_supported(x, hidden, cout, act="gelu"):
@@ -1346,25 +1384,22 @@ def projection_supported(x, hidden, cout, act="gelu"):
             and act in _ACT_CODES)
 
 
-_ACT_CODES = {"gelu": 0, "relu": 1}      # FNO_ACT_* (include/fnoengine.h)
-
-
 class _ProjectionHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, act=0):
+        e = "projection_head"
         _require_cuda(x, "x")
         x = x.contiguous()
         B, Cc = x.shape[0], x.shape[1]
         pw = x.numel() // (B * Cc)
         hid, co = w1.shape[0], w2.shape[0]
-        w1c, b1c = w1.reshape(hid, Cc).contiguous(), b1.contiguous()
-        w2c, b2c = w2.reshape(co, hid).contiguous(), b2.contiguous()
-        if b1c.numel() != hid or b2c.numel() != co:
-            raise RuntimeError(f"fnoengine projection_head: biases of {b1c.numel()} / {b2c.numel()} elements for {hid} hidden and {co} output channels")
+        w1c = _operand(e, "w1", w1, x, numel=hid * Cc).reshape(hid, Cc)
+        b1c = _operand(e, "b1", b1, x, numel=hid)
+        w2c = _operand(e, "w2", w2, x, numel=co * hid).reshape(co, hid)
+        b2c = _operand(e, "b2", b2, x, numel=co)
         y = torch.empty((B, co) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().fno_projection_forward_act(B, Cc, hid, co, pw, _ptr(x), _ptr(w1c), _ptr(b1c), _ptr(w2c),
-                                                             _ptr(b2c), act, _ptr(y), _stream()), "projection_forward")
+        _call("projection_forward", x.device, "fno_projection_forward_act", B, Cc, hid, co, pw, x, w1c, b1c, w2c, b2c, act, y,
+              STREAM)
         ctx.save_for_backward(x, w1c, b1c, w2c)
         ctx.meta = (B, Cc, hid, pw, w1.shape, w2.shape, act, co)
         return y
@@ -1373,17 +1408,14 @@ class _ProjectionHeadFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w1c, b1c, w2c = ctx.saved_tensors
         B, Cc, hid, pw, w1shape, w2shape, act, co = ctx.meta
-        L = _lib.lib()
-        dy = dy.contiguous()
+        dy = _operand("projection_head backward", "dy", dy, x, numel=B * co * pw)
         dx = torch.empty_like(x)
         dw1, db1, dw2 = torch.empty_like(w1c), torch.empty_like(b1c), torch.empty_like(w2c)
         db2 = torch.empty(co, dtype=torch.float32, device=x.device)
-        nws = L.fno_projection_workspace_bytes(Cc, hid)
+        nws = _lib.lib().fno_projection_workspace_bytes(Cc, hid)
         ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_projection_backward_act(B, Cc, hid, co, pw, _ptr(x), _ptr(w1c), _ptr(b1c), _ptr(w2c), _ptr(dy), act,
-                                                     _ptr(dx), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ws), nws,
-                                                     _stream()), "projection_backward")
+        _call("projection_backward", x.device, "fno_projection_backward_act", B, Cc, hid, co, pw, x, w1c, b1c, w2c, dy, act, dx,
+              dw1, db1, dw2, db2, ws, nws, STREAM)
         return dx, dw1.view(w1shape), db1, dw2.view(w2shape), db2, None
 
 
@@ -1392,56 +1424,3 @@ def projection_head(x, w1, b1, w2, b2, act="gelu"):
     (FNO projection, PINO observer tails; Cout <= 4: PlanePredHead's out_dim * plane_num, pinobserver.py:257-273) or 'relu'
     (RNO2d's regressor head, rno.py:171-175; hidden 256, Cout 1)."""
     return _ProjectionHeadFn.apply(x, w1, b1, w2, b2, _ACT_CODES[act])
-
-
-# ----------------------------------------------------------------------------
-# lifting layer  y = W x + b,  (B, Cin <= 4, ...) -> (B, C, ...)
-# ----------------------------------------------------------------------------
-def lifting_supported(x, c_out):
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and 1 <= x.shape[1] <= 4 and c_out in (32, 64)):
-        return False
-    pw = 1
-    for s in x.shape[2:]:
-        pw *= s
-    return pw % 128 == 0
-
-
-class _LiftingFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, bias):
-        _require_cuda(x, "x")
-        if x.requires_grad:
-            raise RuntimeError("fnoengine lifting: the input field is data (no gradient is produced for it)")
-        x = x.contiguous()
-        B, cin = x.shape[0], x.shape[1]
-        cout = w.shape[0]
-        pw = x.numel() // (B * cin)
-        wc = w.reshape(cout, cin).contiguous()
-        bc = bias.contiguous() if bias is not None else None
-        y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().fno_lifting_forward(B, cin, cout, pw, _ptr(x), _ptr(wc), _ptr(bc), _ptr(y), _stream()),
-                       "lifting_forward")
-        ctx.save_for_backward(x)
-        ctx.meta = (B, cin, cout, pw, w.shape, bias is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        B, cin, cout, pw, wshape, has_b = ctx.meta
-        L = _lib.lib()
-        dy = dy.contiguous()
-        dw = torch.empty(cout, cin, dtype=torch.float32, device=x.device)
-        db = torch.empty(cout, dtype=torch.float32, device=x.device) if has_b else None
-        nws = L.fno_lifting_workspace_bytes(cout)
-        ws = _bytes(nws, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.fno_lifting_backward(B, cin, cout, pw, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, _stream()),
-                       "lifting_backward")
-        return None, dw.view(wshape), db
-
-
-def lifting(x, w, bias=None):
-    """conv1x1 from <= 4 input channels: x (B, Cin, ...) data, w (C, Cin[, 1..]), bias (C)."""
-    return _LiftingFn.apply(x, w, bias)

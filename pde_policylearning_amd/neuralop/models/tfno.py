@@ -85,22 +85,12 @@ class FNO(nn.Module):
         160 x 160, 192 x 192 grids ...; split-precision GEMM mode)."""
         if self.fno_blocks.convs.separable or self.fno_blocks.convs.output_scaling_factor is not None:
             return False           # torch compositions (SpectralConv._torch_composition): layer by layer
-        w = x.shape[-1]
-        npx = 256 if w > 128 else 128
-        plane = 1
-        for s in x.shape[2:]:
-            plane *= s
-        tiled = w % 32 == 0 and w <= 256 and npx % w == 0 and plane % npx == 0
-        loose = (not tiled) and 32 <= w <= 320 and plane % 128 == 0 and F._lib.lib().fno_get_gemm_mode() == 1
         if not (self.hidden_channels in (32, 64) and self.in_channels <= 4 and self.out_channels <= 4
-                and self.projection_channels == 256 and (tiled or loose) and x.is_cuda
+                and self.projection_channels == 256 and x.is_cuda and F.row_tiling(tuple(x.shape[2:])) is not None
                 and (not x.requires_grad or self.in_channels <= 4)):
             return False
         # the engine has the last word (e.g. 256-pixel tiles with many kept modes do not fit LDS)
-        gelu_mask = 0
-        for l in range(self.n_layers):
-            if l < self.n_layers - l:
-                gelu_mask |= 1 << l
+        gelu_mask = F.default_gelu_mask(self.n_layers)
         return F.model_plan_available(self.n_dim, self.in_channels, self.hidden_channels, self.out_channels,
                                       self.projection_channels, self.n_layers, tuple(x.shape[2:]),
                                       tuple(m // 2 for m in self.n_modes), self.fft_norm, gelu_mask, x.device)

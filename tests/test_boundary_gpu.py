@@ -327,6 +327,112 @@ def test_corner_weight_of_the_wrong_extent_is_an_error_not_a_fault(dev):
         F.fno_blocks(x, skip, small, bias, modes, "ortho")
 
 
+
+def _refusal_cases(dev):
+    """name -> (call, good operands, the ONE operand that is wrong, what the message names).  One case per entry point whose
+    operands reached the device unchecked before functional._operand (DESIGN.md, "The Python bridge": the table of refusals);
+    the last rows hand a CPU operand to a GPU call (the device rule needs one GPU only)."""
+    from pde_policylearning_amd import functional as F
+    g = torch.Generator().manual_seed(5)
+
+    def r(*shape, s=0.1, dtype=torch.float32, device=dev):
+        return (s * torch.randn(*shape, generator=g)).to(device=device, dtype=dtype)
+    C, m = 32, (8, 8)
+    x, h = r(2, C, 64, 64, s=1.0), r(2, C, 64, 64, s=1.0)
+    xin = r(2, 3, 64, 64, s=1.0)
+    corner = lambda: [r(C, C, *m, 2, s=0.05) for _ in range(2)]
+    cases = {}
+
+    def add(name, call, good, bad, names):
+        cases[name] = (call, good, bad, names)
+    add("spectral_layer:corner_extent",
+        lambda w, cw, b: F.spectral_pointwise_layer(x, cw, m, "backward", w, b),
+        dict(w=r(C, C, 1), cw=corner(), b=r(C)), dict(cw=[t[:, :, :4, :4].contiguous() for t in corner()]),
+        ("spectral_pointwise_layer", "spectral weight 0"))
+    add("spectral_layer:w_dtype",
+        lambda w, cw, b: F.spectral_pointwise_layer(x, cw, m, "backward", w, b),
+        dict(w=r(C, C, 1), cw=corner(), b=r(C)), dict(w=r(C, C, 1, dtype=torch.float64)), ("spectral_pointwise_layer", "`w`"))
+    add("fno_blocks:skip_extent",
+        lambda sk, b: F.fno_blocks(x, [sk], corner(), b, m, "ortho"),
+        dict(sk=r(C, C, 1), b=r(1, C)), dict(sk=r(C, C // 2, 1)), ("fno_blocks", "skip weight 0"))
+    add("fno_blocks:bias_extent",
+        lambda sk, b: F.fno_blocks(x, [sk], corner(), b, m, "ortho"),
+        dict(sk=r(C, C, 1), b=r(1, C)), dict(b=r(1, C // 2)), ("fno_blocks", "`bias`"))
+    L = 2
+    model = dict(lift_w=r(C, 3, 1, 1), lift_b=r(C), skip_ws=[r(C, C, 1, 1) for _ in range(L)],
+                 spec_ws=[r(C, C, *m, 2, s=0.05) for _ in range(2 * L)], spec_bias=r(L, C, 1, 1), w1=r(256, C, 1, 1), b1=r(256),
+                 w2=r(1, 256, 1, 1), b2=r(1))
+    add("fno_model:spec_bias_extent", lambda **p: F.fno_model(xin, modes=m, **p), model, dict(spec_bias=r(1, C, 1, 1)),
+        ("fno_model", "spectral bias"))
+    fan = dict(sk=[r(C, C, 1) for _ in range(3)], bs=[r(C) for _ in range(3)], cw=[r(C, C, *m, 2, s=0.05) for _ in range(6)])
+    add("fourier_fanout:bias_extent", lambda sk, bs, cw: F.fourier_fanout(x, sk, bs, cw, m, "ortho"), fan,
+        dict(bs=[r(C), r(C // 2), r(C)]), ("fourier_fanout", "bias 1"))
+    add("fourier_fanout:skip_extent", lambda sk, bs, cw: F.fourier_fanout(x, sk, bs, cw, m, "ortho"), fan,
+        dict(sk=[r(C, C, 1), r(C, C, 1), r(C, 1, 1)]), ("fourier_fanout", "skip weight 2"))
+    add("pointwise_conv_add:addend_dtype", lambda w, b, a: F.pointwise_conv_add(x, w, b, a),
+        dict(w=r(C, C, 1), b=r(C), a=h), dict(a=h.double()), ("pointwise_conv_add", "addend"))
+    add("pointwise_per_sample:bias_shape", lambda w, b: F.pointwise_conv_per_sample_bias(x, w, b),
+        dict(w=r(C, C, 1), b=r(2, C)), dict(b=r(C, 2)), ("pointwise_conv_per_sample_bias", "`bias`"))
+    add("lifting:bias_extent", lambda w, b: F.lifting(xin, w, b), dict(w=r(C, 3, 1, 1), b=r(C)), dict(b=r(C // 2)),
+        ("lifting", "`bias`"))
+    add("lifting_per_sample:bias_shape", lambda w, b: F.lifting_per_sample_bias(xin, w, b),
+        dict(w=r(C, 3), b=r(2, C)), dict(b=r(1, C)), ("lifting_per_sample_bias", "`bias`"))
+    proj = dict(w1=r(256, C, 1, 1), b1=r(256), w2=r(1, 256, 1, 1), b2=r(1))
+    add("projection_head:w2_dtype", lambda **p: F.projection_head(x, **p), proj, dict(w2=r(1, 256, 1, 1, dtype=torch.float16)),
+        ("projection_head", "`w2`"))
+    add("rno_reset_gate:a4_dtype", lambda a3, a4, b2: F.rno_reset_gate(a3, a4, b2, h), dict(a3=x, a4=r(2, C, 64, 64), b2=r(1)),
+        dict(a4=x.double()), ("rno_reset_gate", "`a4`"))
+    og = dict(a1=x, a2=h, b1=r(1), a7=x, a8=h, b4=r(1), a5=x, a6=h, b3=r(1))
+    add("rno_output_gate:b4_extent", lambda **p: F.rno_output_gate(h=h, **p), og, dict(b4=r(2)), ("rno_output_gate", "`b4`"))
+    seed = F.draw_dropout_seed(torch.device(dev))
+    add("fno_block_tail:seed_dtype",
+        lambda sd: F.fno_block_tail(x, r(C, C, 1), corner(), r(1, C), m, "ortho", relu_out=True, drop_p=0.25, seed=sd),
+        dict(sd=seed), dict(sd=seed.to(torch.int64)), ("fno_block_tail", "`seed`"))
+    # the same-device rule: an operand on the CPU against an anchor on the GPU
+    add("device:projection_head_b1", lambda **p: F.projection_head(x, **p), proj, dict(b1=r(256, device="cpu")),
+        ("projection_head", "`b1`", "GPU"))
+    add("device:fno_blocks_bias", lambda sk, b: F.fno_blocks(x, [sk], corner(), b, m, "ortho"),
+        dict(sk=r(C, C, 1), b=r(1, C)), dict(b=r(1, C, device="cpu")), ("fno_blocks", "`bias`", "GPU"))
+    add("device:rno_reset_gate_b2", lambda a3, a4, b2: F.rno_reset_gate(a3, a4, b2, h), dict(a3=x, a4=r(2, C, 64, 64), b2=r(1)),
+        dict(b2=r(1, device="cpu")), ("rno_reset_gate", "`b2`", "GPU"))
+    return cases
+
+
+REFUSALS = ["spectral_layer:corner_extent", "spectral_layer:w_dtype", "fno_blocks:skip_extent", "fno_blocks:bias_extent",
+            "fno_model:spec_bias_extent", "fourier_fanout:bias_extent", "fourier_fanout:skip_extent",
+            "pointwise_conv_add:addend_dtype", "pointwise_per_sample:bias_shape", "lifting:bias_extent",
+            "lifting_per_sample:bias_shape", "projection_head:w2_dtype", "rno_reset_gate:a4_dtype", "rno_output_gate:b4_extent",
+            "fno_block_tail:seed_dtype", "device:projection_head_b1", "device:fno_blocks_bias", "device:rno_reset_gate_b2"]
+
+
+@pytest.mark.parametrize("case", REFUSALS)
+def test_wrong_operand_is_refused_before_any_launch(dev, case):
+    """Every operand passes functional._operand before its address is taken: one of the wrong device, dtype or extent is a
+    RuntimeError naming entry point and operand, raised before the engine launches anything (the per-launch profile,
+    include/fnoengine.h:338-342, stays empty).  The entry point runs once with good operands first."""
+    import re
+    from pde_policylearning_amd import _lib
+    cases = _refusal_cases(dev)
+    assert sorted(cases) == sorted(REFUSALS)
+    call, good, bad, names = cases[case]
+    out = call(**good)
+    assert all(torch.isfinite(t).all() for t in (out if isinstance(out, tuple) else (out,)))
+    torch.cuda.synchronize()
+    L = _lib.lib()
+    L.fno_profile_reset()
+    L.fno_profile_enable(1)
+    try:
+        with pytest.raises(RuntimeError, match=re.escape(names[0])) as ei:
+            call(**dict(good, **bad))
+        torch.cuda.synchronize()
+        launched = _lib.profile_summary()
+    finally:
+        L.fno_profile_enable(0)
+        L.fno_profile_reset()
+    assert all(n in str(ei.value) for n in names), str(ei.value)
+    assert launched == [], launched
+
+
 def test_split2_low_mixed_precision_fma_is_bit_identical(tmp_path):
     """fno_dev.h::split2_low forms the low term of every two-term fp16 split with v_fma_mixlo_f16 / v_fma_mixhi_f16 (hipcc does
     not select them by itself).  tools/mix_split_test.hip compares it bit for bit with the compiler's form (v_cvt_f32_f16,
