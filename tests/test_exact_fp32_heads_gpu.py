@@ -216,6 +216,29 @@ def _counted_step(model, run, mode):
     return tc.n, ec.n
 
 
+def _head_decisions(head, a):
+    """The decisions of the fused ReLU head (nn.Sequential(fc1, ReLU, fc2)) on its channels-first input `a`, as the kernel takes
+    them in the exact-fp32 mode: (B, X, Y, hidden) bool on the CPU.  One hidden unit per call: second layer e_k, no bias."""
+    from pde_policylearning_amd import _lib
+    from pde_policylearning_amd import functional as F
+    fc1 = head[0]
+    hid = fc1.out_features
+    L = _lib.lib()
+    prev = L.fno_get_gemm_mode()
+    L.fno_set_gemm_mode(0)
+    try:
+        out = torch.empty(a.shape[0], a.shape[2], a.shape[3], hid, dtype=torch.bool, device=a.device)
+        b2 = torch.zeros(1, device=a.device)
+        with torch.no_grad():
+            for k in range(hid):
+                w2 = torch.zeros(1, hid, device=a.device)
+                w2[0, k] = 1.0
+                out[..., k] = F.projection_head(a, fc1.weight.detach(), fc1.bias.detach(), w2, b2, act="relu")[:, 0] > 0
+    finally:
+        L.fno_set_gemm_mode(prev)
+    return out.cpu()
+
+
 def _compare(model, y, y64, g64, g32, gcond, slack):
     """As the full-size cfg-3 check: output within TOL_Y; every gradient within 1e-5 or slack x the larger of the float32
     oracle's and the conditioning floor (a one-number parameter is held to the worst floor of the model)."""
@@ -234,7 +257,16 @@ def test_rno2d_exact_mode_train_step_engine_only_vs_float64(dev):
     """RNO2d observer (BASELINE config 3's model: modes 12, width 64, one layer) at 128 x 128, batch 2, training mode with the
     regressor's dropout: in the exact mode the regressor's two Fourier layers (fused tails) and its ReLU head run on the engine,
     so the step makes no more torch layer calls than the default mode; and the exact-mode step matches float64 (the oracle takes
-    the engine's dropout fields, from the same seed words, and its ReLU decisions)."""
+    the engine's dropout fields, from the same seed words, and its ReLU decisions).
+
+    ALL of its ReLU decisions, the fused head's 2 x 128 x 128 x 256 included: that kernel never materialises its hidden tensor,
+    so they are read out of it, one hidden unit per call, with a one-hot second layer (y = relu(hidden_k)).  Until round 10 the
+    head was left to each evaluation's own decisions, and the comparison measured ties instead of arithmetic: torch's float32
+    on the CPU decides 2 of the 8.4 M head inputs otherwise than float64, which alone puts 2e-5 .. 2e-4 on every gradient
+    upstream of the head (and nothing on regressor.2), the exact-fp32 engine used to take the same two and so sat on the
+    float32 oracle's figures to four digits, and a SELU that is 1e-5 more accurate (expm1) moved it to other ties and out of the
+    budget.  With the head conditioned too, all three evaluations differentiate one function; how many
+    of the engine's decisions differ from float64's own is bounded as in tests/test_fullsize_gpu.py."""
     from pde_policylearning_amd import functional as F
     from pde_policylearning_amd.libs.models.rno_models import RNO2dObserver
     torch.manual_seed(0)
@@ -254,13 +286,14 @@ def test_rno2d_exact_mode_train_step_engine_only_vs_float64(dev):
     n1, e1 = _counted_step(model, step, 1)
     assert e1 == {"fno_block_tail": 2, "projection_head": 1}, e1
     # the exact-mode step, with its dropout seeds and ReLU decisions recorded for the oracle
-    seeds, masks = [], {}
+    seeds, masks, head_in = [], {}, {}
     orig_seed = F.draw_dropout_seed
     F.draw_dropout_seed = lambda d: seeds.append(orig_seed(d)) or seeds[-1]
     for j, layer in enumerate(model.regressor.spectral_conv):
         def wrapped(a, _f=layer.forward_channels_first, _j=j):
             o = _f(a)
             masks[f"regressor.spectral_conv.{_j}"] = (o.detach() > 0).permute(0, 2, 3, 1).cpu()
+            head_in[_j] = o.detach().clone()
             return o
         layer.forward_channels_first = wrapped
     try:
@@ -274,6 +307,7 @@ def test_rno2d_exact_mode_train_step_engine_only_vs_float64(dev):
     assert sum(n0.values()) == 0, n0
     _assert_exact(terms)
     assert len(seeds) == 2 and len(masks) == 2
+    masks["regressor.head"] = _head_decisions(model.regressor.regressor, head_in[1])
 
     scales = [F.dropout_scale(2 * 64 * 128 * 128, 0.3, s, dev).view(2, 64, 128, 128).permute(0, 2, 3, 1).cpu() for s in seeds]
     orig_layer = OO.spectral_conv_with_fc
@@ -288,7 +322,7 @@ def test_rno2d_exact_mode_train_step_engine_only_vs_float64(dev):
 
     def oracle(prm, xin, dtype):
         pc = {k: (v.to(dtype) if v.is_floating_point() else v).clone().requires_grad_(True) for k, v in prm.items()}
-        OO.RELU_HOOK = OO.ReluMasks(impose=masks)
+        OO.RELU_HOOK = hooks[dtype] = OO.ReluMasks(impose=masks)
         OO.spectral_conv_with_fc = layer_with_dropout
         try:
             y = OO.rno2d_forward(pc, xin.to(dtype), 12, 12, 64, 0, 1)
@@ -298,7 +332,12 @@ def test_rno2d_exact_mode_train_step_engine_only_vs_float64(dev):
             OO.spectral_conv_with_fc = orig_layer
         return y.detach().numpy(), {k: v.grad.numpy() for k, v in pc.items()}
 
+    hooks = {}
     y64, g64 = oracle(params, x, torch.float64)
+    # the oracle adopts the ENGINE's decisions, so the decisions themselves are checked (as tests/test_fullsize_gpu.py does)
+    flips = {t: int((torch.cat(seen) != masks[t]).sum()) for t, seen in hooks[torch.float64].seen.items()}
+    print("ReLU decisions of the engine that differ from the float64 oracle's own:", flips, "of", {t: m.numel() for t, m in masks.items()})
+    assert set(flips) == set(masks) and sum(flips.values()) <= 1e-6 * sum(m.numel() for m in masks.values()), flips
     _, g32 = oracle(params, x, torch.float32)
     gen = torch.Generator().manual_seed(1)
     move = lambda v: v.double() * (1 + (torch.rand(v.shape, generator=gen, dtype=torch.float64) * 2 - 1) * 2.0 ** -24)

@@ -700,7 +700,8 @@ def test_fused_lploss_upstream_scale_and_zero_difference(dev):
 
 
 def test_fused_adam_matches_torch_adam(dev):
-    """fno_adam_step on the flat bucket vs torch.optim.Adam(lr, weight_decay) for 6 steps, ragged sizes."""
+    """fno_adam_step on the flat bucket vs torch.optim.Adam(lr, weight_decay) for 6 steps, ragged sizes: parameters and both
+    moments."""
     from pde_policylearning_amd.trainer import FlatGradBucket, FusedAdam
     torch.manual_seed(11)
     shapes = [(7, 5), (33,), (4, 4, 3, 3, 2), (1,), (129,)]
@@ -718,9 +719,12 @@ def test_fused_adam_matches_torch_adam(dev):
             q.grad.copy_(g)
         ref_opt.step()
         opt.step()
-        for p, q in zip(ref_p, my_p):
-            assert rel_l2(_cpu(torch.view_as_real(q.data) if q.is_complex() else q.data),
-                          _cpu(torch.view_as_real(p.data) if p.is_complex() else p.data)) < 1e-6, step
+        real = lambda t: _cpu(torch.view_as_real(t) if t.is_complex() else t)      # noqa: E731
+        for p, q, m, v in zip(ref_p, my_p, bucket.views(opt.exp_avg), bucket.views(opt.exp_avg_sq)):
+            assert rel_l2(real(q.data), real(p.data)) < 1e-6, step
+            # the two moments, in the bucket's layout (sizes, magnitudes and float64: tests/test_step_tail_gpu.py)
+            assert rel_l2(real(m), real(ref_opt.state[p]["exp_avg"])) < 1e-6, step
+            assert rel_l2(real(v), real(ref_opt.state[p]["exp_avg_sq"])) < 1e-6, step
     assert all(q.data.data_ptr() >= opt.flat_param.data_ptr() for q in my_p)
 
 
