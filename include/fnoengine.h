@@ -410,6 +410,39 @@ int fno_chanflow_pde_loss_backward(const FnoChanflowGrid* grid, int batch, const
                                    const float* Vgt, const float* V, const float* W, const float* gloss, float* dV, void* ws,
                                    size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Channel-flow environment step in float64: NSControlEnvMatlab.time_advance_RK3_py (libs/envs/control_env.py:533-580),
+ * compute_projection_step (:582-613), compute_pressure_py / get_boundary_pressures (:196-229, :423-427) and the scores
+ * (:186-303).  State layout as above with `batch` independent environments; dtype must be 1 (fp64: the (0,0) Poisson
+ * system has condition number ~7e6, fp32 cannot hold the project's 1e-5 line).  Nx, Nz in 2..128, Ny >= 3.
+ *   fno_chanflow_poisson_table_bytes / _pack: HOST helper.  Twiddles, the trapezoid weights of the bulk velocity and, for every
+ *     wavenumber pair (kx, kz <= Nz/2), the Thomas factors of DD + (kxx[kx] + kzz[kz]) I (the (0,0) system with D[0,0] * 1.5):
+ *     reciprocal pivots and forward multipliers.  The caller copies the table to the device once (16-byte aligned) and passes
+ *     it with its size; a table of another grid is refused.
+ *   fno_chanflow_project: U, V, W <- compute_projection_step(U, V, W), then the U, W ghost rows by reflection; in place.
+ *   fno_chanflow_wall_pressure: p1, p2 (batch, Nx, Nz) = get_boundary_pressures(); P (batch, Nx, Ny-1, Nz) too unless NULL.
+ *   fno_chanflow_rk3_step: one step_rk3(opV1, opV2) in place; opV1, opV2 (batch, Nx, Nz); dpdx (batch) in/out; meanU0 (batch).
+ *   fno_chanflow_diagnostics: out (batch, 12) = sum(div), mean|U|, mean|V|, mean|W|, ||U||, ||V||, ||W||, |wall shear stress|,
+ *     bulk velocity, mean(p2), finite-difference dPdx of p2, signed wall shear stress; p2 may be NULL (entries 9, 10 = 0).
+ * All device work goes to `stream`: no allocation, no synchronisation, so a step can be captured into a graph.
+ * ---------------------------------------------------------------------- */
+#define FNO_CHANFLOW_DIAG_COUNT 12
+size_t fno_chanflow_poisson_table_bytes(const FnoChanflowGrid* grid);
+int fno_chanflow_poisson_pack(const FnoChanflowGrid* grid, const double* y, const double* ym, const double* yg, double* packed,
+                              size_t packed_bytes);
+size_t fno_chanflow_step_workspace_bytes(const FnoChanflowGrid* grid, int batch);
+int fno_chanflow_project(const FnoChanflowGrid* grid, int batch, int dtype, const double* metrics, const double* table,
+                         size_t table_bytes, void* U, void* V, void* W, void* ws, size_t ws_bytes, void* stream);
+int fno_chanflow_wall_pressure(const FnoChanflowGrid* grid, int batch, int dtype, const double* metrics, const double* table,
+                               size_t table_bytes, const void* U, const void* V, const void* W, const void* dpdx, void* p1,
+                               void* p2, void* P, void* ws, size_t ws_bytes, void* stream);
+int fno_chanflow_rk3_step(const FnoChanflowGrid* grid, int batch, int dtype, const double* metrics, const double* table,
+                          size_t table_bytes, void* U, void* V, void* W, const void* opV1, const void* opV2, void* dpdx,
+                          const void* meanU0, double dt, void* ws, size_t ws_bytes, void* stream);
+int fno_chanflow_diagnostics(const FnoChanflowGrid* grid, int batch, int dtype, const double* metrics, const double* table,
+                             size_t table_bytes, const void* U, const void* V, const void* W, const void* p2, void* out,
+                             void* stream);
+
 /* Names and average device time (ms, HIP events on `stream`) of the kernels launched
  * by the last fno_model_* call made with profiling enabled; used by bench.py for the
  * roofline line.  fno_profile_enable(1) makes every launch event-bracketed (slow path). */

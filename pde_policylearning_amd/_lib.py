@@ -148,6 +148,15 @@ def lib():
     L.fno_chanflow_pde_loss_workspace_bytes.restype = sz
     L.fno_chanflow_pde_loss_forward.argtypes = [gp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.fno_chanflow_pde_loss_backward.argtypes = [gp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.fno_chanflow_poisson_table_bytes.argtypes = [gp]
+    L.fno_chanflow_poisson_table_bytes.restype = sz
+    L.fno_chanflow_poisson_pack.argtypes = [gp, dp, dp, dp, dp, sz]
+    L.fno_chanflow_step_workspace_bytes.argtypes = [gp, ci]
+    L.fno_chanflow_step_workspace_bytes.restype = sz
+    L.fno_chanflow_project.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.fno_chanflow_wall_pressure.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.fno_chanflow_rk3_step.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, sz, vp]
+    L.fno_chanflow_diagnostics.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.fno_pino_loss_workspace_bytes.argtypes = [ci, ci, ci]
     L.fno_pino_loss_workspace_bytes.restype = sz
     L.fno_pino_loss_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, fl, vp, vp, vp, sz, vp]
@@ -198,6 +207,8 @@ EXPORTED_SYMBOLS = [
     "fno_pino_loss_workspace_bytes", "fno_pino_loss_forward", "fno_pino_loss_backward",
     "fno_chanflow_pack_metrics", "fno_chanflow_rhs", "fno_chanflow_pde_loss_workspace_bytes",
     "fno_chanflow_pde_loss_forward", "fno_chanflow_pde_loss_backward",
+    "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",
+    "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
     "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
 ]
 

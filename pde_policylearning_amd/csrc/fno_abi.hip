@@ -17,6 +17,7 @@
 #include "k_block_bwd.h"
 #include "k_block_bwd2.h"
 #include "k_chanflow.h"
+#include "k_chanflow_step.h"
 #include "k_pointwise.h"
 #include "k_block_fwd2.h"
 #include "k_block_fwd3.h"
@@ -2296,6 +2297,237 @@ extern "C" int fno_chanflow_pde_loss_backward(const FnoChanflowGrid* grid, int B
   a.gloss = gloss; a.dV = dV;
   return launch("k_chanflow_diff_bwd", k_chanflow_diff_bwd, dim3((unsigned)(B * grid->Nx), chanflow_ysplit(B, grid->Nx)), dim3(256), 0, (hipStream_t)stream,
                 geo, a);
+}
+
+// ===========================================================================
+// Channel-flow environment step, fp64 (libs/envs/control_env.py:533-613 RK3 + projection, :196-229 pressure, :186-303 scores)
+// ===========================================================================
+struct CfTabLayout { int twx, twz, wgt, trap, sub, fac, ntile; size_t total; };
+static CfTabLayout cf_tab_layout(int Nx, int Ny, int Nz) {
+  auto even = [](int n) { return (n + 1) & ~1; };
+  CfTabLayout l;
+  const int Nzh = Nz / 2 + 1, n = Ny - 1;
+  l.twx = 0;
+  l.twz = l.twx + 2 * Nx;
+  l.wgt = l.twz + 2 * Nz;
+  l.trap = l.wgt + even(Nzh);
+  l.sub = l.trap + even(n);
+  l.fac = l.sub + even(n);
+  l.ntile = (Nx * Nzh + kCfTile - 1) / kCfTile;
+  l.total = ((size_t)l.fac + (size_t)l.ntile * n * kCfTile * 2) * sizeof(double);
+  return l;
+}
+// LDS of the transform kernels: spectrum plane + twiddles (+ c2r weights) + a chunk of `xc` (+ halo) real rows
+static size_t cf_plane_lds(int Nx, int Nz, int xc, bool inverse) {
+  const int Nzh = Nz / 2 + 1;
+  size_t d = (size_t)Nx * Nzh * 2 + 2 * (size_t)(Nx + Nz);
+  if (inverse) d += ((Nzh + 1) & ~1) + (size_t)(xc + 1) * (Nz + 1);
+  else d += (size_t)xc * (Nz + 1);
+  return d * sizeof(double);
+}
+static int cf_chunk(int Nx, int Nz, bool inverse) {
+  int xc = std::min(Nx, 16);
+  while (xc > 1 && cf_plane_lds(Nx, Nz, xc, inverse) > FNO_LDS_MAX) xc >>= 1;
+  return xc;
+}
+// LDS of the solve kernel: per row 32 complex right-hand sides, 32 factor pairs and the sub-diagonal entry
+static size_t cf_solve_lds(int n) { return (size_t)n * (4 * kCfTile + 1) * sizeof(double); }
+static int cf_grid_check(const FnoChanflowGrid* g, int B) {
+  if (!g) return fail(FNO_EINVAL, "chanflow step: null grid");
+  if (B < 1 || B > 65535) return fail(FNO_EINVAL, "chanflow step: batch must be in 1..65535 (got %d)", B);
+  if (g->Nx < 2 || g->Nx > 128 || g->Nz < 2 || g->Nz > 128)
+    return fail(FNO_EUNSUPPORTED, "chanflow step: Nx and Nz must be in 2..128, the range of the in-LDS transforms (got Nx=%d, Nz=%d)",
+                g->Nx, g->Nz);
+  if (g->Ny < 3 || cf_solve_lds(g->Ny - 1) > FNO_LDS_MAX)
+    return fail(FNO_EUNSUPPORTED, "chanflow step: Ny must be in 3..%d, a solve tile of all rows and its factors have to fit LDS (got %d)",
+                (int)(FNO_LDS_MAX / cf_solve_lds(1)) + 1, g->Ny);
+  if (!(g->dx > 0) || !(g->dz > 0)) return fail(FNO_EINVAL, "chanflow step: dx and dz must be positive");
+  if (cf_plane_lds(g->Nx, g->Nz, 1, true) > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "chanflow step: plane does not fit LDS");
+  return FNO_OK;
+}
+extern "C" size_t fno_chanflow_poisson_table_bytes(const FnoChanflowGrid* grid) {
+  if (cf_grid_check(grid, 1) != FNO_OK) return 0;
+  return cf_tab_layout(grid->Nx, grid->Ny, grid->Nz).total;
+}
+extern "C" int fno_chanflow_poisson_pack(const FnoChanflowGrid* grid, const double* y, const double* ym, const double* yg,
+                                         double* packed, size_t packed_bytes) {
+  LAUNCHCHK(cf_grid_check(grid, 1));
+  if (!y || !ym || !yg || !packed) return fail(FNO_EINVAL, "fno_chanflow_poisson_pack: null array");
+  const int Nx = grid->Nx, Ny = grid->Ny, Nz = grid->Nz, Nzh = Nz / 2 + 1, n = Ny - 1;
+  const CfTabLayout l = cf_tab_layout(Nx, Ny, Nz);
+  if (packed_bytes < l.total) return fail(FNO_ENOMEM, "fno_chanflow_poisson_pack: table needs %zu bytes, have %zu", l.total, packed_bytes);
+  const double pi = 3.14159265358979323846;
+  for (int m = 0; m < Nx; ++m) { packed[l.twx + 2 * m] = cos(2 * pi * m / Nx); packed[l.twx + 2 * m + 1] = -sin(2 * pi * m / Nx); }
+  for (int m = 0; m < Nz; ++m) { packed[l.twz + 2 * m] = cos(2 * pi * m / Nz); packed[l.twz + 2 * m + 1] = -sin(2 * pi * m / Nz); }
+  for (int k = 0; k < Nzh + 1 && l.wgt + k < l.trap; ++k) packed[l.wgt + k] = 0.0;
+  for (int k = 0; k < Nzh; ++k) packed[l.wgt + k] = (k == 0 || 2 * k == Nz) ? 1.0 : 2.0;
+  // trapezoid over [0, ym, 2] of the xz-mean profile, / 2 (control_env.py:249-259), as weights on the xz-SUMS of U rows 1..Ny-1
+  for (int j = 0; j < l.sub - l.trap; ++j) packed[l.trap + j] = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double lo = j ? ym[j - 1] : 0.0, hi = (j + 1 < n) ? ym[j + 1] : 2.0;
+    packed[l.trap + j] = 0.5 * (hi - lo) / 2.0 / ((double)Nx * Nz);
+  }
+  // DD (control_env.py:66-77): row j couples rows j-1 (sub) and j+1 (sup)
+  std::vector<double> dg(n), sup(n);
+  for (int j = 0; j < l.fac - l.sub; ++j) packed[l.sub + j] = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double hy = y[j + 1] - y[j], gu = yg[j + 2] - yg[j + 1], gl = yg[j + 1] - yg[j];
+    dg[j] = -1.0 / hy * (1.0 / gu + 1.0 / gl);
+    sup[j] = (j + 1 < n) ? 1.0 / hy / gu : 0.0;
+    packed[l.sub + j] = j ? 1.0 / hy / gl : 0.0;
+  }
+  dg[0] += 1.0 / (y[1] - y[0]) / (yg[1] - yg[0]);
+  dg[n - 1] += 1.0 / (y[Ny - 1] - y[Ny - 2]) / (yg[Ny] - yg[Ny - 1]);
+  auto kmod = [pi](int k, int N, double d) {      // modified wavenumbers (:53-64)
+    const int s = (k <= N / 2) ? k : k - N;
+    return 2.0 * (cos(2 * pi * s / N) - 1.0) / (d * d);
+  };
+  double* fac = packed + l.fac;
+  for (int c = 0; c < l.ntile * kCfTile; ++c) {
+    const int tile = c / kCfTile, cl = c % kCfTile;
+    const bool live = c < Nx * Nzh;
+    const double kk = live ? kmod(c / Nzh, Nx, grid->dx) + kmod(c % Nzh, Nz, grid->dz) : 0.0;
+    double cp = 0.0;
+    for (int j = 0; j < n; ++j) {
+      double* f = fac + (((size_t)tile * n + j) * kCfTile + cl) * 2;
+      if (!live) { f[0] = 1.0; f[1] = 0.0; continue; }
+      double d = dg[j] + kk;
+      if (c == 0 && j == 0) d *= 1.5;                       // regularisation of the singular (0,0) system (:223-224)
+      const double piv = d - packed[l.sub + j] * cp;
+      f[0] = 1.0 / piv;
+      cp = sup[j] / piv;
+      f[1] = cp;
+      if (!std::isfinite(f[0]) || !std::isfinite(f[1])) return fail(FNO_EINVAL, "fno_chanflow_poisson_pack: singular system (column %d, row %d)", c, j);
+    }
+  }
+  return FNO_OK;
+}
+
+struct CfWs { double *F1[3], *Fs[3], *Xs[3]; double2* H; double* rowsum; size_t total; bool ok; };
+static CfWs carve_cf(const FnoChanflowGrid* g, int B, void* ws, size_t ws_bytes) {
+  CfWs w;
+  const size_t su = (size_t)B * g->Nx * (g->Ny + 1) * g->Nz, sv = (size_t)B * g->Nx * g->Ny * g->Nz;
+  auto up = [](size_t n) { return (n + 31) & ~(size_t)31; };
+  double* p = (double*)ws;
+  for (double** f : {w.F1, w.Fs, w.Xs}) {
+    f[0] = p; p += up(su);
+    f[1] = p; p += up(sv);
+    f[2] = p; p += up(su);
+  }
+  w.H = (double2*)p; p += up((size_t)B * (g->Ny - 1) * g->Nx * (g->Nz / 2 + 1) * 2);
+  w.rowsum = p; p += up((size_t)B * (g->Ny - 1));
+  w.total = (size_t)((char*)p - (char*)ws);
+  w.ok = ws_bytes >= w.total;
+  return w;
+}
+extern "C" size_t fno_chanflow_step_workspace_bytes(const FnoChanflowGrid* grid, int B) {
+  if (cf_grid_check(grid, B) != FNO_OK) return 0;
+  return carve_cf(grid, B, nullptr, 0).total;
+}
+// everything the step entry points share: grid, dtype, table size, alignment, workspace
+struct CfCall { ChanflowGeo geo; ChanflowTab tab; CfWs w; hipStream_t st; int ncol; };
+static int cf_prepare(const char* who, const FnoChanflowGrid* g, int B, int dtype, const double* metrics, const double* table,
+                      size_t table_bytes, std::initializer_list<const void*> need, std::initializer_list<const void*> opt, void* ws,
+                      size_t ws_bytes, bool use_ws, void* stream, CfCall* c) {
+  LAUNCHCHK(cf_grid_check(g, B));
+  if (dtype != 1) return fail(FNO_EINVAL, "%s: the stepper's state is float64 only (dtype must be 1, got %d)", who, dtype);
+  LAUNCHCHK(chanflow_geo(g, B, metrics, &c->geo));
+  const CfTabLayout l = cf_tab_layout(g->Nx, g->Ny, g->Nz);
+  if (!table || table_bytes != l.total)
+    return fail(FNO_EINVAL, "%s: Poisson table of %zu bytes does not belong to this grid (%d x %d x %d needs %zu)", who, table_bytes,
+                g->Nx, g->Ny, g->Nz, l.total);
+  if (((uintptr_t)table & 15) || ((uintptr_t)metrics & 7)) return fail(FNO_EINVAL, "%s: table must be 16-byte aligned", who);
+  for (const void* p : need)
+    if (!p || ((uintptr_t)p & 7)) return fail(FNO_EINVAL, "%s: null or misaligned (8 B) tensor", who);
+  for (const void* p : opt)
+    if ((uintptr_t)p & 7) return fail(FNO_EINVAL, "%s: misaligned (8 B) tensor", who);
+  c->tab = ChanflowTab{table, l.twx, l.twz, l.wgt, l.trap, l.sub, l.fac};
+  c->ncol = g->Nx * (g->Nz / 2 + 1);
+  c->st = (hipStream_t)stream;
+  if (use_ws) {
+    if (!ws || ((uintptr_t)ws & 15)) return fail(FNO_EINVAL, "%s: null or misaligned (16 B) workspace", who);
+    c->w = carve_cf(g, B, ws, ws_bytes);
+    if (!c->w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", c->w.total, ws_bytes);
+  }
+  return FNO_OK;
+}
+static ChanflowCFields cf_const(double* const* f) { return ChanflowCFields{f[0], f[1], f[2]}; }
+static ChanflowFields cf_mut(double* const* f) { return ChanflowFields{f[0], f[1], f[2]}; }
+// divergence of (X0 + ca F1 + cb Fs) -> h -> p_hat; writes the stage state to `out` when given
+static int cf_poisson(const CfCall& c, ChanflowCFields X0, ChanflowCFields F1, ChanflowCFields Fs, double ca, double cb,
+                      ChanflowFields out, const double* opV1, const double* opV2) {
+  const ChanflowGeo& g = c.geo;
+  ChanflowStageArgs a;
+  a.X0 = X0; a.F1 = F1; a.Fs = Fs; a.out = out; a.opV1 = opV1; a.opV2 = opV2; a.ca = ca; a.cb = cb; a.h = c.w.H;
+  a.xc = cf_chunk(g.Nx, g.Nz, false);
+  LAUNCHCHK(launch("k_chanflow_stage", k_chanflow_stage, dim3(g.Ny - 1, g.B), dim3(256), cf_plane_lds(g.Nx, g.Nz, a.xc, false), c.st,
+                   g, c.tab, a));
+  return launch("k_chanflow_solve", k_chanflow_solve, dim3((c.ncol + kCfTile - 1) / kCfTile, g.B), dim3(256),
+                cf_solve_lds(g.Ny - 1), c.st, g.Ny - 1, c.ncol, c.tab, c.w.H);
+}
+static int cf_correct(const CfCall& c, ChanflowCFields in, ChanflowFields out, double* rowsum) {
+  const ChanflowGeo& g = c.geo;
+  ChanflowCorrectArgs a;
+  a.in = in; a.out = out; a.ph = c.w.H; a.rowsum = rowsum; a.xc = cf_chunk(g.Nx, g.Nz, true);
+  return launch("k_chanflow_correct", k_chanflow_correct, dim3(g.Ny - 1, g.B), dim3(256), cf_plane_lds(g.Nx, g.Nz, a.xc, true), c.st,
+                g, c.tab, a);
+}
+extern "C" int fno_chanflow_project(const FnoChanflowGrid* grid, int B, int dtype, const double* metrics, const double* table,
+                                    size_t table_bytes, void* U, void* V, void* W, void* ws, size_t ws_bytes, void* stream) {
+  CfCall c;
+  LAUNCHCHK(cf_prepare("fno_chanflow_project", grid, B, dtype, metrics, table, table_bytes, {U, V, W}, {}, ws, ws_bytes, true, stream, &c));
+  const ChanflowCFields X{(const double*)U, (const double*)V, (const double*)W}, none{nullptr, nullptr, nullptr};
+  LAUNCHCHK(cf_poisson(c, X, none, none, 0.0, 0.0, ChanflowFields{nullptr, nullptr, nullptr}, nullptr, nullptr));
+  return cf_correct(c, X, ChanflowFields{(double*)U, (double*)V, (double*)W}, nullptr);
+}
+extern "C" int fno_chanflow_wall_pressure(const FnoChanflowGrid* grid, int B, int dtype, const double* metrics, const double* table,
+                                          size_t table_bytes, const void* U, const void* V, const void* W, const void* dpdx,
+                                          void* p1, void* p2, void* P, void* ws, size_t ws_bytes, void* stream) {
+  CfCall c;
+  LAUNCHCHK(cf_prepare("fno_chanflow_wall_pressure", grid, B, dtype, metrics, table, table_bytes, {U, V, W, dpdx, p1, p2}, {P}, ws,
+                       ws_bytes, true, stream, &c));
+  const ChanflowCFields none{nullptr, nullptr, nullptr};
+  LAUNCHCHK(chanflow_rhs_t<double>(c.geo, U, V, W, dpdx, 0.0, c.w.Fs[0], c.w.Fs[1], c.w.Fs[2], c.st));
+  LAUNCHCHK(cf_poisson(c, cf_const(c.w.Fs), none, none, 0.0, 0.0, ChanflowFields{nullptr, nullptr, nullptr}, nullptr, nullptr));
+  const int xc = cf_chunk(grid->Nx, grid->Nz, true);
+  return launch("k_chanflow_pressure", k_chanflow_pressure, dim3(2 + (P ? grid->Ny - 1 : 0), B), dim3(256),
+                cf_plane_lds(grid->Nx, grid->Nz, xc, true), c.st, c.geo, c.tab, (const double2*)c.w.H, (double*)p1, (double*)p2,
+                (double*)P, xc);
+}
+extern "C" int fno_chanflow_rk3_step(const FnoChanflowGrid* grid, int B, int dtype, const double* metrics, const double* table,
+                                     size_t table_bytes, void* U, void* V, void* W, const void* opV1, const void* opV2, void* dpdx,
+                                     const void* meanU0, double dt, void* ws, size_t ws_bytes, void* stream) {
+  CfCall c;
+  LAUNCHCHK(cf_prepare("fno_chanflow_rk3_step", grid, B, dtype, metrics, table, table_bytes, {U, V, W, opV1, opV2, dpdx, meanU0}, {},
+                       ws, ws_bytes, true, stream, &c));
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(FNO_EINVAL, "fno_chanflow_rk3_step: dt must be positive and finite");
+  const ChanflowCFields X{(const double*)U, (const double*)V, (const double*)W}, none{nullptr, nullptr, nullptr};
+  const ChanflowFields Xo{(double*)U, (double*)V, (double*)W};
+  const double *v1 = (const double*)opV1, *v2 = (const double*)opV2;
+  const CfWs& w = c.w;
+  // stage 1: X0 + dt 8/15 F(X0)
+  LAUNCHCHK(chanflow_rhs_t<double>(c.geo, U, V, W, dpdx, 0.0, w.F1[0], w.F1[1], w.F1[2], c.st));
+  LAUNCHCHK(cf_poisson(c, X, cf_const(w.F1), none, dt * 8 / 15, 0.0, cf_mut(w.Xs), v1, v2));
+  LAUNCHCHK(cf_correct(c, cf_const(w.Xs), cf_mut(w.Xs), nullptr));
+  // stage 2: X0 + dt (1/4 F1 + 5/12 F(X1))
+  LAUNCHCHK(chanflow_rhs_t<double>(c.geo, w.Xs[0], w.Xs[1], w.Xs[2], dpdx, 0.0, w.Fs[0], w.Fs[1], w.Fs[2], c.st));
+  LAUNCHCHK(cf_poisson(c, X, cf_const(w.F1), cf_const(w.Fs), dt * (1.0 / 4), dt * (5.0 / 12), cf_mut(w.Xs), v1, v2));
+  LAUNCHCHK(cf_correct(c, cf_const(w.Xs), cf_mut(w.Xs), nullptr));
+  // stage 3: X0 + dt (1/4 F1 + 3/4 F(X2)), corrected straight into the caller's state
+  LAUNCHCHK(chanflow_rhs_t<double>(c.geo, w.Xs[0], w.Xs[1], w.Xs[2], dpdx, 0.0, w.Fs[0], w.Fs[1], w.Fs[2], c.st));
+  LAUNCHCHK(cf_poisson(c, X, cf_const(w.F1), cf_const(w.Fs), dt * (1.0 / 4), dt * (3.0 / 4), cf_mut(w.Xs), v1, v2));
+  LAUNCHCHK(cf_correct(c, cf_const(w.Xs), Xo, w.rowsum));
+  return launch("k_chanflow_bulk", k_chanflow_bulk, dim3(grid->Nx, B), dim3(256), 0, c.st, c.geo, c.tab, (const double*)w.rowsum,
+                (const double*)meanU0, dt, (double*)U, (double*)dpdx);
+}
+extern "C" int fno_chanflow_diagnostics(const FnoChanflowGrid* grid, int B, int dtype, const double* metrics, const double* table,
+                                        size_t table_bytes, const void* U, const void* V, const void* W, const void* p2, void* out,
+                                        void* stream) {
+  CfCall c;
+  LAUNCHCHK(cf_prepare("fno_chanflow_diagnostics", grid, B, dtype, metrics, table, table_bytes, {U, V, W, out}, {p2}, nullptr, 0, false,
+                       stream, &c));
+  return launch("k_chanflow_diag", k_chanflow_diag, dim3(B), dim3(256), 0, c.st, c.geo, c.tab,
+                ChanflowCFields{(const double*)U, (const double*)V, (const double*)W}, (const double*)p2, (double*)out);
 }
 
 // ===========================================================================

@@ -1018,6 +1018,177 @@ def chanflow_pde_loss(grid, U, Vgt, V, W):
 
 
 # ----------------------------------------------------------------------------
+# channel-flow environment step, float64 (libs/envs/control_env.py:533-613, 196-229, 186-303)
+# ----------------------------------------------------------------------------
+CHANFLOW_DIAG = ("sum_div", "mean_abs_U", "mean_abs_V", "mean_abs_W", "norm_U", "norm_V", "norm_W", "shear_stress", "bulk_velocity",
+                 "p2_mean", "dpdx_finite_difference", "shear_stress_signed")      # columns of chanflow_diagnostics
+
+
+class ChannelPoisson:
+    """The Poisson table of a ChannelGrid (fno_chanflow_poisson_pack): twiddles, bulk-velocity weights and the Thomas
+    factors of every wavenumber pair's wall-normal system.  Built once on the host, one device copy per GPU."""
+
+    def __init__(self, grid):
+        import numpy as np
+        self.grid = grid
+        g = grid.desc()
+        self.nbytes = int(_lib.lib().fno_chanflow_poisson_table_bytes(C.byref(g)))
+        if self.nbytes == 0:
+            raise RuntimeError("fnoengine ChannelPoisson: " + _lib.lib().fno_last_error().decode("utf-8", "replace"))
+        self.packed = np.zeros(self.nbytes // 8, dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        _lib.check(_lib.lib().fno_chanflow_poisson_pack(C.byref(g), grid.y.ctypes.data_as(dp), grid.ym.ctypes.data_as(dp),
+                                                        grid.yg.ctypes.data_as(dp), self.packed.ctypes.data_as(dp), self.nbytes),
+                   "chanflow_poisson_pack")
+        self._dev = {}
+
+    def table(self, device):
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.packed).to(device)
+        return self._dev[device]
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st["_dev"] = {}
+        return st
+
+
+def chanflow_step_workspace(grid, B, device):
+    """an uninitialised workspace for `B` environments (every step entry point takes one; a graph holds on to its own)"""
+    g = grid.desc()
+    n = _lib.lib().fno_chanflow_step_workspace_bytes(C.byref(g), B)
+    if n == 0:
+        raise RuntimeError("fnoengine chanflow step: " + _lib.lib().fno_last_error().decode("utf-8", "replace"))
+    return _bytes(n, device)
+
+
+def _chanflow_step_operands(e, grid, poisson, U, V, W, ws, layout):
+    """checked state, metrics, table and workspace of a step entry point.  dtype code 1 = float64; any other dtype and a table
+    built for another grid reach the engine as they are, which refuses both before it launches anything"""
+    grid._check_fields(U, V, W, e)
+    dt = U.dtype
+    code = {torch.float64: 1, torch.float32: 0}.get(dt, -1)
+    U, V, W = (_operand(e, n, t, U, dtype=dt, layout=layout) for n, t in (("U", U), ("V", V), ("W", W)))
+    m = _operand(e, "grid metrics", grid.metrics(U.device), U, dtype=torch.float64, numel=3 * (grid.Ny + 2))
+    tab = _operand(e, "Poisson table", poisson.table(U.device), U, dtype=torch.float64)
+    B = U.shape[0]
+    if ws is None:
+        ws = chanflow_step_workspace(grid, B, U.device)
+    ws = _operand(e, "workspace", ws, U, dtype=torch.uint8, layout="dense")
+    return B, code, U, V, W, m, tab, ws
+
+
+def chanflow_project(grid, poisson, U, V, W, ws=None):
+    """The fractional-step projection (compute_projection_step, control_env.py:582-613) of a batch of float64 states,
+    IN PLACE: divergence, Poisson solve per wavenumber pair, gradient correction of the interior rows, then the U, W ghost
+    rows by reflection (V's wall rows are left as they are).  Returns U, V, W."""
+    e = "chanflow_project"
+    B, code, U, V, W, m, tab, ws = _chanflow_step_operands(e, grid, poisson, U, V, W, ws, "dense")
+    g = grid.desc()
+    _call(e, U.device, "fno_chanflow_project", C.byref(g), B, code, m, tab, tab.numel() * 8, U, V, W, ws, ws.numel(), STREAM)
+    return U, V, W
+
+
+def _per_sample(e, name, v, U):
+    B = U.shape[0]
+    if not torch.is_tensor(v):
+        v = torch.full((B,), float(v), dtype=torch.float64, device=U.device)
+    return _operand(e, name, v, U, dtype=torch.float64, numel=B, layout="dense")
+
+
+def chanflow_wall_pressure(grid, poisson, U, V, W, dPdx, full=False, ws=None, out=None):
+    """p1, p2 (B, Nx, Nz) of get_boundary_pressures (control_env.py:423-427): the Poisson solve on the divergence of the
+    right-hand side (:196-229), observed at the two walls; with full=True also P (B, Nx, Ny-1, Nz).  dPdx: float or (B,)
+    float64 tensor.  `out` = (p1, p2[, P]) to write into existing tensors."""
+    e = "chanflow_wall_pressure"
+    B, code, U, V, W, m, tab, ws = _chanflow_step_operands(e, grid, poisson, U, V, W, ws, "copy")
+    dp = _per_sample(e, "dPdx", dPdx, U)
+    shp = (B, grid.Nx, grid.Nz)
+    if out is None:
+        out = [torch.empty(shp, dtype=torch.float64, device=U.device) for _ in range(2)]
+        if full:
+            out.append(torch.empty((B, grid.Nx, grid.Ny - 1, grid.Nz), dtype=torch.float64, device=U.device))
+    p1, p2 = (_operand(e, n, t, U, dtype=torch.float64, shape=shp, layout="dense") for n, t in zip(("p1", "p2"), out))
+    P = _operand(e, "P", out[2], U, dtype=torch.float64, shape=(B, grid.Nx, grid.Ny - 1, grid.Nz), layout="dense") if full else None
+    g = grid.desc()
+    _call(e, U.device, "fno_chanflow_wall_pressure", C.byref(g), B, code, m, tab, tab.numel() * 8, U, V, W, dp, p1, p2, P, ws,
+          ws.numel(), STREAM)
+    return (p1, p2, P) if full else (p1, p2)
+
+
+def chanflow_rk3_step(grid, poisson, U, V, W, opV1, opV2, dPdx, meanU0, dt, ws=None):
+    """One boundary-controlled RK3 step (time_advance_RK3_py, control_env.py:533-580) of a batch of float64 states, IN PLACE
+    on U, V, W and on dPdx, a (B,) float64 tensor; opV1, opV2 (B, Nx, Nz) are the wall-normal velocities imposed at the two
+    walls, meanU0 (B,) the bulk velocity the pressure gradient holds.  Nothing is read back: the step never synchronises."""
+    e = "chanflow_rk3_step"
+    B, code, U, V, W, m, tab, ws = _chanflow_step_operands(e, grid, poisson, U, V, W, ws, "dense")
+    shp = (B, grid.Nx, grid.Nz)
+    v1, v2 = (_operand(e, n, t, U, dtype=torch.float64, shape=shp) for n, t in (("opV1", opV1), ("opV2", opV2)))
+    if not torch.is_tensor(dPdx):
+        raise _refuse(e, "dPdx", "be a (B,) float64 tensor (it is updated in place)", type(dPdx).__name__)
+    dp, mu = _per_sample(e, "dPdx", dPdx, U), _per_sample(e, "meanU0", meanU0, U)
+    g = grid.desc()
+    _call(e, U.device, "fno_chanflow_rk3_step", C.byref(g), B, code, m, tab, tab.numel() * 8, U, V, W, v1, v2, dp, mu, float(dt), ws,
+          ws.numel(), STREAM)
+    return U, V, W, dp
+
+
+def chanflow_diagnostics(grid, poisson, U, V, W, p2=None, out=None):
+    """(B, 12) float64, columns CHANFLOW_DIAG: the scalars of the environment's `info` (control_env.py:186-303) in one launch;
+    p2 (B, Nx, Nz) feeds the two pressure columns (0 without it)."""
+    e = "chanflow_diagnostics"
+    grid._check_fields(U, V, W, e)
+    dt = U.dtype
+    U, V, W = (_operand(e, n, t, U, dtype=dt) for n, t in (("U", U), ("V", V), ("W", W)))
+    B = U.shape[0]
+    m = _operand(e, "grid metrics", grid.metrics(U.device), U, dtype=torch.float64, numel=3 * (grid.Ny + 2))
+    tab = _operand(e, "Poisson table", poisson.table(U.device), U, dtype=torch.float64)
+    p2 = _operand(e, "p2", p2, U, dtype=torch.float64, shape=(B, grid.Nx, grid.Nz), optional=True)
+    if out is None:
+        out = torch.empty((B, len(CHANFLOW_DIAG)), dtype=torch.float64, device=U.device)
+    out = _operand(e, "out", out, U, dtype=torch.float64, shape=(B, len(CHANFLOW_DIAG)), layout="dense")
+    g = grid.desc()
+    _call(e, U.device, "fno_chanflow_diagnostics", C.byref(g), B, {torch.float64: 1, torch.float32: 0}.get(dt, -1), m, tab,
+          tab.numel() * 8, U, V, W, p2, out, STREAM)
+    return out
+
+
+class GraphedChannelStep:
+    """chanflow_rk3_step + chanflow_wall_pressure of a fixed batch replayed as ONE graph.  The state, the controls, dPdx and
+    the observations live in tensors the graph owns: write `opV1` / `opV2` (copy_), call step(), read `p1` / `p2`."""
+
+    def __init__(self, grid, poisson, U, V, W, dPdx, meanU0, dt):
+        self.grid, self.poisson, self.dt = grid, poisson, float(dt)
+        self.U, self.V, self.W = (t.detach().clone().contiguous() for t in (U, V, W))
+        B, dev = self.U.shape[0], self.U.device
+        self.dPdx, self.meanU0 = _per_sample("GraphedChannelStep", "dPdx", dPdx, self.U).clone(), _per_sample("GraphedChannelStep", "meanU0", meanU0, self.U).clone()
+        self.opV1 = torch.zeros((B, grid.Nx, grid.Nz), dtype=torch.float64, device=dev)
+        self.opV2 = torch.zeros_like(self.opV1)
+        self.p1, self.p2 = torch.zeros_like(self.opV1), torch.zeros_like(self.opV1)
+        self.ws = chanflow_step_workspace(grid, B, dev)
+        saved = [t.clone() for t in (self.U, self.V, self.W, self.dPdx)]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                      # one eager run loads the code objects before the capture
+            self._body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._body()
+        for t, s in zip((self.U, self.V, self.W, self.dPdx), saved):
+            t.copy_(s)
+
+    def _body(self):
+        chanflow_rk3_step(self.grid, self.poisson, self.U, self.V, self.W, self.opV1, self.opV2, self.dPdx, self.meanU0, self.dt,
+                          ws=self.ws)
+        chanflow_wall_pressure(self.grid, self.poisson, self.U, self.V, self.W, self.dPdx, ws=self.ws, out=(self.p1, self.p2))
+
+    def step(self):
+        self.graph.replay()
+        return self.p1, self.p2
+
+
+# ----------------------------------------------------------------------------
 # RNO cell gates (neuralop/models/rno.py:254-260)
 # ----------------------------------------------------------------------------
 def gates_supported(*tensors):

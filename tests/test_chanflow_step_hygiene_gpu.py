@@ -1,0 +1,84 @@
+"""Poisoned-buffer and guard-band cases for the channel-flow step entry points (tests/hygiene.py): workspace and outputs
+pre-filled with 0x00 / 0xFF (NaN) / 0x7F patterns, inputs inside NaN-filled guarded buffers.  Every output is bitwise equal
+across the runs and finite, the guard bands are intact, inputs that are not declared in-place come back unchanged: no
+output depends on what the workspace held before, no kernel reads or writes past a tensor.
+
+Safety (hygiene.py's rule: poison only data): the step's workspace holds float64 fields, the complex spectrum and the row
+sums; the Poisson table and the grid metrics are built by the host and are not poisoned; nothing a kernel turns into an
+address lives in a poisoned buffer."""
+import numpy as np
+import pytest
+import torch
+
+from tests import chanflow_step_reference as R
+from tests import hygiene as H
+
+pytestmark = pytest.mark.gpu
+DT = 1e-3
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from pde_policylearning_amd import _lib
+    _lib.lib()
+    return torch.device("cuda:0")
+
+
+def _case(dev, Nx, Ny, Nz, B):
+    from pde_policylearning_amd import functional as F
+    g = R.Grid(Nx, Ny, Nz)
+    grid = F.ChannelGrid(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, g.yg, g.nu)
+    U, V, W = (torch.from_numpy(a).to(dev) for a in R.analytic_state(g, 7 + B, noise=0.1, B=B))
+    inputs = {"U": U, "V": V, "W": W, "opV1": -V[:, :, 2, :].contiguous(), "opV2": -V[:, :, -2, :].contiguous(),
+              "dp": torch.full((B,), R.DPDX0, dtype=torch.float64, device=dev),
+              "mu": torch.tensor([R.bulk_velocity(g, U[b].cpu().numpy()) for b in range(B)], dtype=torch.float64, device=dev)}
+    return F, grid, F.ChannelPoisson(grid), inputs
+
+
+SHAPES = [(6, 7, 10, 1), (8, 10, 6, 3), (32, 130, 32, 2)]
+
+
+def _run(case, fn, inputs, mutable=()):
+    out, findings = H.run_case(fn, inputs, mutable)
+    assert not findings, "\n".join([case] + findings[:40])
+    return out
+
+
+@pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
+def test_project(dev, Nx, Ny, Nz, B):
+    F, grid, poisson, inputs = _case(dev, Nx, Ny, Nz, B)
+
+    def fn(inp, after_forward):
+        F.chanflow_project(grid, poisson, inp["U"], inp["V"], inp["W"])
+        after_forward()
+        return {k: inp[k] for k in "UVW"}
+    _run(f"chanflow_project {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W"))
+
+
+@pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
+def test_wall_pressure(dev, Nx, Ny, Nz, B):
+    F, grid, poisson, inputs = _case(dev, Nx, Ny, Nz, B)
+
+    def fn(inp, after_forward):
+        p1, p2 = F.chanflow_wall_pressure(grid, poisson, inp["U"], inp["V"], inp["W"], inp["dp"])
+        after_forward()
+        q1, q2, P = F.chanflow_wall_pressure(grid, poisson, inp["U"], inp["V"], inp["W"], inp["dp"], full=True)
+        return {"p1": p1, "p2": p2, "q1": q1, "q2": q2, "P": P}
+    out = _run(f"chanflow_wall_pressure {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
+    assert torch.equal(out["p1"], out["q1"]) and torch.equal(out["p2"], out["q2"])
+
+
+@pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
+def test_rk3_step_and_diagnostics(dev, Nx, Ny, Nz, B):
+    F, grid, poisson, inputs = _case(dev, Nx, Ny, Nz, B)
+
+    def fn(inp, after_forward):
+        d0 = F.chanflow_diagnostics(grid, poisson, inp["U"], inp["V"], inp["W"])
+        F.chanflow_rk3_step(grid, poisson, inp["U"], inp["V"], inp["W"], inp["opV1"], inp["opV2"], inp["dp"], inp["mu"], DT)
+        after_forward()
+        p2 = F.chanflow_wall_pressure(grid, poisson, inp["U"], inp["V"], inp["W"], inp["dp"])[1]
+        d1 = F.chanflow_diagnostics(grid, poisson, inp["U"], inp["V"], inp["W"], p2)
+        return {"U": inp["U"], "V": inp["V"], "W": inp["W"], "dp": inp["dp"], "d0": d0, "d1": d1}
+    out = _run(f"chanflow_rk3_step {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W", "dp"))
+    assert np.all(out["d0"][:, 9:11].cpu().numpy() == 0)        # no p2 given: the two pressure columns are 0
