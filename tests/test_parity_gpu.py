@@ -1175,6 +1175,18 @@ def test_pino_residual_fields_vs_oracle(dev):
     ue = u.to(dev).requires_grad_(True)
     eic, ef = F.pino_loss(ue, u0.to(dev), f.to(dev), visc.to(dev), 1.0)
     assert abs(float(eic) - float(lic)) < 1e-5 * float(lic) and abs(float(ef) - float(lf)) < 1e-5 * float(lf)
+    # the field: Du - f as the forward call stored it, every (sample, time level) plane against the oracle in float64 within
+    # the budget of the oracle's own float32 error (tests/pino_loss_cases.py)
+    from tests import pino_loss_cases as C
+    stored = C.stored_field(ef, B, n, nt).cpu()
+    f_rep = f.repeat(B, 1, 1, nt - 2)
+    du32 = C.planes_of(P.ns_vorticity_residual(u, visc, 1.0) - f_rep)
+    du64 = C.planes_of(P.ns_vorticity_residual(u.double(), visc.double(), 1.0) - f_rep.double())
+    assert rel_l2(stored.numpy(), du32.numpy()) < 1e-5
+    bad = [C.judge("pino fields_vs_oracle n=64 B=3 nt=7 t=1", "field", C.rel_err(stored, du64), C.rel_err(du32, du64)),
+           C.judge("pino fields_vs_oracle n=64 B=3 nt=7 t=1", "field/plane", C.worst_slice_err(stored, du64, (2, 3)),
+                   C.worst_slice_err(du32, du64, (2, 3)))]
+    assert not any(bad), bad
     (eic + 2.0 * ef).backward()
     assert rel_l2(_cpu(ue.grad), uo.grad.numpy()) < 1e-5
 

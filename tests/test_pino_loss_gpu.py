@@ -1,0 +1,169 @@
+"""The PINO residual loss on the GPU (k_pino_loss.h: one workgroup per plane at 32 / 64 / 128; k_pino_loss2.h: row / column /
+row slab passes at 256) against oracle/pino_loss_oracle.py in float64.  Families, references, comparison and the error table:
+tests/pino_loss_cases.py (the criterion is shown to bite, and to be passable, on the CPU in
+tests/test_pino_loss_reference.py).  Every (case, quantity) adds a row to the file $PINO_LOSS_ERROR_LOG names
+(profiles/r12_pino_loss_errors.txt).
+
+  budget    white / smooth / steady(0.1) / steady(0.01; 0.03 at 256) x (n, B, nt) = (32, 3, 3), (64, 2, 5), (128, 2, 4), (256, 2, 4):
+            stored field, worst plane, max error, both losses, gradient overall and worst time level
+  slabs     256 x 256 with 64, 65, 66 and 129 planes (one chunk exactly; a last chunk of one plane; a sample boundary inside
+            chunk 0 and a partial last chunk, whose gridDim.y is the S2 field stride; three chunks and three viscosities), and
+            the 66-plane case at 128 through fno_debug_pino_twopass
+  edges     T = 3, B = 1, t_interval 0.37 / 2.0, one-sided and negative upstream weights, a second backward, two forwards
+            before either backward
+  exact     const-in-space and zero inputs bit for bit, u0 == u[..., 0]
+  floor     the exact steady solution: the engine's float32 noise floor of loss_f against plain float32's"""
+import pytest
+import torch
+
+from tests import pino_loss_cases as C
+
+pytestmark = pytest.mark.gpu
+
+BUDGET_CASES = [(fam, d, n, B, nt) for n, B, nt in C.BUDGET_SHAPES for fam, d in C.budget_families(n)]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    from pde_policylearning_amd import _lib
+    _lib.lib()   # fails loudly when the HIP library is absent
+    return torch.device("cuda:0")
+
+
+def _forward(inp, dev, t_interval):
+    """(u leaf, loss_ic, loss_f, {"loss_ic", "loss_f", "field"} on the CPU)"""
+    from pde_policylearning_amd import functional as F
+    B, n, _, nt = inp["u"].shape
+    u = inp["u"].to(dev).requires_grad_(True)
+    lic, lf = F.pino_loss(u, inp["u0"].to(dev), inp["f"].to(dev), inp["visc"].to(dev), t_interval)
+    return u, lic, lf, {"loss_ic": lic.detach().cpu(), "loss_f": lf.detach().cpu(), "field": C.stored_field(lf, B, n, nt).cpu()}
+
+
+def _engine(inp, dev, t_interval=C.T_INTERVAL, g_ic=C.IC_WEIGHT, g_f=1.0):
+    u, lic, lf, out = _forward(inp, dev, t_interval)
+    (g_ic * lic + g_f * lf).backward()
+    out["grad"] = u.grad.cpu()
+    assert all(bool(torch.isfinite(v).all()) for v in out.values())
+    return out
+
+
+def _all_rows(name, got, refs, floor_case=False):
+    inp, ref64, ref32, ref32n = refs
+    return C.forward_failures(name, got, ref32, ref64, inp["f"], floor_case=floor_case) \
+        + C.grad_failures(name, got["grad"], ref32n, ref32, ref64, floor_case=floor_case)
+
+
+@pytest.mark.parametrize("case", BUDGET_CASES, ids=lambda c: C.case_name(*c).replace(" ", "_"))
+def test_budget_across_regimes(dev, case):
+    fam, d, n, B, nt = case
+    refs = C.references(fam, d, n, B, nt)
+    bad = _all_rows(C.case_name(fam, d, n, B, nt), _engine(refs[0], dev), refs)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("B,nt", C.SLAB_SHAPES)
+def test_slab_chunks_at_256_vs_float64(dev, B, nt):
+    """per-plane and per-level maxima are judged: one wrong plane among 129 is not diluted"""
+    refs = C.references("white", None, 256, B, nt, C.SLAB_T_INTERVAL)
+    bad = _all_rows(C.case_name("white", None, 256, B, nt, C.SLAB_T_INTERVAL), _engine(refs[0], dev, C.SLAB_T_INTERVAL), refs)
+    assert not bad, "\n".join(bad)
+
+
+def test_slab_chunks_forced_at_128_vs_float64(dev):
+    """the (2, 35) case - 66 planes, a sample boundary inside chunk 0, a last chunk of two planes - through the 128-point
+    instantiation of the slab kernels"""
+    from pde_policylearning_amd import _lib
+    refs = C.references("white", None, 128, 2, 35, C.SLAB_T_INTERVAL)
+    L = _lib.lib()
+    L.fno_debug_pino_twopass(1)
+    try:
+        got = _engine(refs[0], dev, C.SLAB_T_INTERVAL)
+        torch.cuda.synchronize()
+    finally:
+        L.fno_debug_pino_twopass(0)
+    bad = _all_rows(C.case_name("white", None, 128, 2, 35, C.SLAB_T_INTERVAL) + " twopass", got, refs)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("t_interval", (0.37, 2.0))
+@pytest.mark.parametrize("n", C.GRIDS)
+def test_edges(dev, n, t_interval):
+    """B = 1, T = 3 (one interior level: levels 0, 1 = T - 2 and T - 1 of k_pino_assemble and nothing else)"""
+    refs = C.references("white", None, n, 1, 3, t_interval)
+    inp, ref64 = refs[0], refs[1]
+    name = C.case_name("white", None, n, 1, 3, t_interval)
+    bad = _all_rows(name, _engine(inp, dev, t_interval), refs)
+    # upstream weights: loss_ic alone, loss_f alone, and (-2.5, 3) against float64 and against the combination of the two
+    g10, g01 = _engine(inp, dev, t_interval, 1.0, 0.0)["grad"], _engine(inp, dev, t_interval, 0.0, 1.0)["grad"]
+    gm = _engine(inp, dev, t_interval, -2.5, 3.0)["grad"]
+    r64, r32n = (C.oracle_eval(inp, dt, t_interval, -2.5, 3.0, norms64=dt == torch.float32)["grad"] for dt in (torch.float64, torch.float32))
+    bad.append(C.judge(name, "grad(-2.5,3)", C.rel_err(gm, r64), C.rel_err(r32n, r64)))
+    bad.append(C.judge(name, "grad combo", C.rel_err(gm, -2.5 * g10.double() + 3.0 * g01.double()), 0.0))
+    ic64 = C.oracle_eval(inp, torch.float64, t_interval, 1.0, 0.0)["grad"]
+    ic32 = C.oracle_eval(inp, torch.float32, t_interval, 1.0, 0.0, norms64=True)["grad"]
+    bad.append(C.judge(name, "grad(1,0)", C.rel_err(g10, ic64), C.rel_err(ic32, ic64)))
+    assert not bool(g10[..., 1:].any()), "loss_ic reaches level 0 alone"
+    bad = [b for b in bad if b]
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("n", C.GRIDS)
+def test_backward_twice_and_two_forwards(dev, n):
+    """backward must not disturb what forward stored: a second backward(retain_graph=True) gives the same bits, and two
+    forwards before either backward each give their own gradient"""
+    a, b = C.make_inputs("white", 2, n, 4), C.make_inputs("smooth", 2, n, 4)
+    alone = [_engine(x, dev)["grad"] for x in (a, b)]
+    ua, lica, lfa, fwd_a = _forward(a, dev, C.T_INTERVAL)
+    ub, licb, lfb, _ = _forward(b, dev, C.T_INTERVAL)
+    live_a = C.stored_field(lfa, 2, n, 4, copy=False)
+    (C.IC_WEIGHT * lica + lfa).backward(retain_graph=True)
+    first = ua.grad.clone()
+    ua.grad = None
+    (C.IC_WEIGHT * licb + lfb).backward()
+    (C.IC_WEIGHT * lica + lfa).backward()
+    assert C.same_bits(first.cpu(), alone[0]) and C.same_bits(ua.grad.cpu(), alone[0])
+    assert C.same_bits(ub.grad.cpu(), alone[1])
+    assert C.same_bits(live_a.cpu(), fwd_a["field"])
+
+
+@pytest.mark.parametrize("n", C.GRIDS)
+def test_const_in_space_is_exact(dev, n):
+    """every butterfly difference is an exact zero and only the mean mode is left, where the reference's Laplacian entry is
+    1: the stored field is fma(nu, c, (u[t+1] - u[t-1]) * float32((T - 1) / (2 t_interval))) - f bit for bit
+    (pino_loss_cases.const_expected)"""
+    inp = C.make_inputs("const", 3, n, 6)
+    got = _engine(inp, dev, 0.37)
+    assert C.same_bits(got["field"], C.const_expected(inp, 0.37))
+
+
+@pytest.mark.parametrize("n", C.GRIDS)
+def test_zero_input_is_exact(dev, n):
+    inp = C.make_inputs("zero", 2, n, 5)
+    got = _engine(inp, dev)
+    minus_f = (-inp["f"].reshape(1, 1, n, n)).expand(2, 3, n, n)
+    assert C.same_bits(got["field"], minus_f.contiguous())
+    assert abs(float(got["loss_f"]) - 1.0) <= 2e-6
+
+
+@pytest.mark.parametrize("n", C.GRIDS)
+def test_matching_initial_condition(dev, n):
+    """u0 == u[..., 0]: loss_ic is exactly zero and the gradient is the one with g_ic = 0, bit for bit"""
+    inp = C.make_inputs("smooth", 2, n, 4)
+    inp["u0"] = inp["u"][..., 0].clone()
+    got = _engine(inp, dev)
+    assert float(got["loss_ic"]) == 0.0
+    assert C.same_bits(got["grad"], _engine(inp, dev, g_ic=0.0)["grad"])
+
+
+@pytest.mark.parametrize("n,B,nt", C.BUDGET_SHAPES)
+def test_noise_floor_at_the_steady_solution(dev, n, B, nt):
+    """steady(0): in float64 the residual of the float32-rounded steady solution is 1e-6 .. 1e-5 of the forcing; what a
+    float32 evaluation reports instead is its own rounding noise.  The engine's must not be above 1.75 x plain float32's."""
+    refs = C.references("steady", 0.0, n, B, nt)
+    name = C.case_name("steady", 0.0, n, B, nt)
+    got = _engine(refs[0], dev)
+    _all_rows(name, got, refs, floor_case=True)                       # logged
+    lf, lf32, lf64 = float(got["loss_f"]), float(refs[2]["loss_f"]), float(refs[1]["loss_f"])
+    C.log_value(name, "loss_f", f"engine {lf:10.3e}   ref32 {lf32:10.3e}   ref64 {lf64:10.3e}")
+    assert lf <= C.BUDGET_SLACK * max(lf32, lf64), (lf, lf32, lf64)
