@@ -443,6 +443,40 @@ int fno_chanflow_diagnostics(const FnoChanflowGrid* grid, int batch, int dtype, 
                              size_t table_bytes, const void* U, const void* V, const void* W, const void* p2, void* out,
                              void* stream);
 
+/* ----------------------------------------------------------------------
+ * Closed-loop control (run_control.py): everything between the fp64 channel-flow state and the fp32 observers stays on the device.
+ *   fno_ctrl_encode: x[b * x_batch_stride + i] = (float)((p[b][i] - mean[i]) / (std[i] + eps)), i < plane: fp64 arithmetic with
+ *     a true division, one rounding to fp32 (NormalizerGivenMeanStd.encode, then .float()).  The stride lets the call write
+ *     channel 0 of an NCHW (batch, 3, Nx, Nz) observer input (stride 3 * plane) or an RNO input (stride plane).
+ *   fno_ctrl_decode: opV2[b][i] = (double)y[b * y_batch_stride + i] * (std[i] + eps) + mean[i] (product and sum rounded
+ *     separately), then * scale, clamp to +-clip (0 = off), minus the sample's own plane mean (zero_mean != 0), in this order;
+ *     the mean is a fixed-order sum inside one workgroup.  opV1 (may be NULL) is zero-filled.
+ *   fno_chanflow_diagnostics2: the twelve entries of fno_chanflow_diagnostics and dpdx[b] as the thirteenth, written to
+ *     out + b * out_stride (doubles; out_stride >= 13): one row of a (T, batch, 13) log.  Two launches: a workgroup per
+ *     (wall-normal row, sample) leaves partial sums in `ws` (fno_chanflow_diagnostics2_workspace_bytes, exactly), a workgroup per
+ *     sample adds them in a fixed order.  Run-to-run and batch-position invariant.
+ *   fno_ctrl_stats_update: Welford update of per-point mean and M2 (double) with one more snapshot x of each field;
+ *     `count` = number of snapshots including this one (count == 1 initialises mean and M2 without reading them).
+ *     std = sqrt(M2 / count), the population form.  The table is passed by value to the kernel.
+ * No allocation, no synchronisation: every call can be captured into a graph.
+ * ---------------------------------------------------------------------- */
+#define FNO_CTRL_STATS_MAX 8
+typedef struct FnoCtrlStats {
+  const double* x[FNO_CTRL_STATS_MAX];
+  double* mean[FNO_CTRL_STATS_MAX];
+  double* m2[FNO_CTRL_STATS_MAX];
+  size_t n[FNO_CTRL_STATS_MAX];      /* points per field */
+} FnoCtrlStats;
+int fno_ctrl_encode(int batch, size_t plane, const double* p, const double* mean, const double* std_, double eps, float* x,
+                    size_t x_batch_stride, void* stream);
+int fno_ctrl_decode(int batch, size_t plane, const float* y, size_t y_batch_stride, const double* mean, const double* std_,
+                    double eps, double scale, double clip, int zero_mean, double* opV1, double* opV2, void* stream);
+size_t fno_chanflow_diagnostics2_workspace_bytes(const FnoChanflowGrid* grid, int batch);
+int fno_chanflow_diagnostics2(const FnoChanflowGrid* grid, int batch, int dtype, const double* metrics, const double* table,
+                              size_t table_bytes, const void* U, const void* V, const void* W, const void* p2, const void* dpdx,
+                              void* out, size_t out_stride, void* ws, size_t ws_bytes, void* stream);
+int fno_ctrl_stats_update(const FnoCtrlStats* table, int nfields, long long count, void* stream);
+
 /* Names and average device time (ms, HIP events on `stream`) of the kernels launched
  * by the last fno_model_* call made with profiling enabled; used by bench.py for the
  * roofline line.  fno_profile_enable(1) makes every launch event-bracketed (slow path). */

@@ -49,6 +49,15 @@ FnoModelGrads = FnoModelParams   # same layout, mutable pointers
 class FnoChanflowGrid(C.Structure):
     _fields_ = [("Nx", C.c_int), ("Ny", C.c_int), ("Nz", C.c_int), ("dx", C.c_double), ("dz", C.c_double), ("nu", C.c_double)]
 
+
+FNO_CTRL_STATS_MAX = 8
+
+
+class FnoCtrlStats(C.Structure):         # include/fnoengine.h: the pointer table of fno_ctrl_stats_update
+    _fields_ = [("x", C.c_void_p * FNO_CTRL_STATS_MAX), ("mean", C.c_void_p * FNO_CTRL_STATS_MAX),
+                ("m2", C.c_void_p * FNO_CTRL_STATS_MAX), ("n", C.c_size_t * FNO_CTRL_STATS_MAX)]
+
+
 _lib = None
 
 
@@ -157,6 +166,12 @@ def lib():
     L.fno_chanflow_wall_pressure.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.fno_chanflow_rk3_step.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, sz, vp]
     L.fno_chanflow_diagnostics.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.fno_ctrl_encode.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, sz, vp]
+    L.fno_ctrl_decode.argtypes = [ci, sz, vp, sz, vp, vp, C.c_double, C.c_double, C.c_double, ci, vp, vp, vp]
+    L.fno_chanflow_diagnostics2_workspace_bytes.argtypes = [gp, ci]
+    L.fno_chanflow_diagnostics2_workspace_bytes.restype = sz
+    L.fno_chanflow_diagnostics2.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
+    L.fno_ctrl_stats_update.argtypes = [C.POINTER(FnoCtrlStats), ci, C.c_longlong, vp]
     L.fno_pino_loss_workspace_bytes.argtypes = [ci, ci, ci]
     L.fno_pino_loss_workspace_bytes.restype = sz
     L.fno_pino_loss_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, fl, vp, vp, vp, sz, vp]
@@ -209,6 +224,8 @@ EXPORTED_SYMBOLS = [
     "fno_chanflow_pde_loss_forward", "fno_chanflow_pde_loss_backward",
     "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",
     "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
+    "fno_ctrl_encode", "fno_ctrl_decode", "fno_chanflow_diagnostics2_workspace_bytes", "fno_chanflow_diagnostics2",
+    "fno_ctrl_stats_update",
     "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
 ]
 

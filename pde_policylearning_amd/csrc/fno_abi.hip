@@ -18,6 +18,7 @@
 #include "k_block_bwd2.h"
 #include "k_chanflow.h"
 #include "k_chanflow_step.h"
+#include "k_control_loop.h"
 #include "k_pointwise.h"
 #include "k_block_fwd2.h"
 #include "k_block_fwd3.h"
@@ -2528,6 +2529,75 @@ extern "C" int fno_chanflow_diagnostics(const FnoChanflowGrid* grid, int B, int 
                        stream, &c));
   return launch("k_chanflow_diag", k_chanflow_diag, dim3(B), dim3(256), 0, c.st, c.geo, c.tab,
                 ChanflowCFields{(const double*)U, (const double*)V, (const double*)W}, (const double*)p2, (double*)out);
+}
+
+// ===========================================================================
+// Closed-loop control (run_control.py): observation / action bridges, two-level diagnostics, running statistics
+// ===========================================================================
+static int ctrl_plane_check(const char* who, int B, size_t plane, size_t stride) {
+  if (B < 1 || B > 65535) return fail(FNO_EINVAL, "%s: batch must be in 1..65535 (got %d)", who, B);
+  if (plane < 1 || plane > 0x3fffffffull) return fail(FNO_EINVAL, "%s: plane of %zu points", who, plane);
+  if (stride < plane) return fail(FNO_EINVAL, "%s: batch stride %zu is shorter than the plane (%zu)", who, stride, plane);
+  return FNO_OK;
+}
+extern "C" int fno_ctrl_encode(int B, size_t plane, const double* p, const double* mean, const double* std_, double eps, float* x,
+                               size_t x_batch_stride, void* stream) {
+  LAUNCHCHK(ctrl_plane_check("fno_ctrl_encode", B, plane, x_batch_stride));
+  if (!p || !mean || !std_ || !x) return fail(FNO_EINVAL, "fno_ctrl_encode: null argument");
+  if (((uintptr_t)p | (uintptr_t)mean | (uintptr_t)std_) & 7 || ((uintptr_t)x & 3)) return fail(FNO_EINVAL, "fno_ctrl_encode: misaligned tensor");
+  return launch("k_ctrl_encode", k_ctrl_encode, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, plane, p, mean,
+                std_, eps, x, x_batch_stride);
+}
+extern "C" int fno_ctrl_decode(int B, size_t plane, const float* y, size_t y_batch_stride, const double* mean, const double* std_,
+                               double eps, double scale, double clip, int zero_mean, double* opV1, double* opV2, void* stream) {
+  LAUNCHCHK(ctrl_plane_check("fno_ctrl_decode", B, plane, y_batch_stride));
+  if (!y || !mean || !std_ || !opV2) return fail(FNO_EINVAL, "fno_ctrl_decode: null argument");
+  if (((uintptr_t)opV1 | (uintptr_t)opV2 | (uintptr_t)mean | (uintptr_t)std_) & 7 || ((uintptr_t)y & 3))
+    return fail(FNO_EINVAL, "fno_ctrl_decode: misaligned tensor");
+  if (!std::isfinite(scale) || !(clip >= 0)) return fail(FNO_EINVAL, "fno_ctrl_decode: scale must be finite and clip >= 0 (0 = off)");
+  CtrlDecodeArgs a;
+  a.y = y; a.y_stride = y_batch_stride; a.plane = plane; a.mean = mean; a.sd = std_; a.eps = eps; a.scale = scale; a.clip = clip;
+  a.use_scale = scale != 1.0; a.zero_mean = zero_mean ? 1 : 0; a.opV1 = opV1; a.opV2 = opV2;
+  return launch("k_ctrl_decode", k_ctrl_decode, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+}
+static size_t cf_diag2_bytes(const FnoChanflowGrid* g, int B) { return (size_t)B * (g->Ny + 1) * kCtrlDiagPart * sizeof(double); }
+extern "C" size_t fno_chanflow_diagnostics2_workspace_bytes(const FnoChanflowGrid* grid, int B) {
+  if (cf_grid_check(grid, B) != FNO_OK) return 0;
+  return cf_diag2_bytes(grid, B);
+}
+extern "C" int fno_chanflow_diagnostics2(const FnoChanflowGrid* grid, int B, int dtype, const double* metrics, const double* table,
+                                         size_t table_bytes, const void* U, const void* V, const void* W, const void* p2,
+                                         const void* dpdx, void* out, size_t out_stride, void* ws, size_t ws_bytes, void* stream) {
+  CfCall c;
+  LAUNCHCHK(cf_prepare("fno_chanflow_diagnostics2", grid, B, dtype, metrics, table, table_bytes, {U, V, W, dpdx, out, ws}, {p2}, nullptr, 0,
+                       false, stream, &c));
+  if (out_stride < (size_t)kCtrlDiagOut) return fail(FNO_EINVAL, "fno_chanflow_diagnostics2: out stride %zu is shorter than a row (%d)", out_stride, kCtrlDiagOut);
+  if (ws_bytes != cf_diag2_bytes(grid, B))
+    return fail(FNO_EINVAL, "fno_chanflow_diagnostics2: workspace of %zu bytes does not belong to this grid and batch (%d x %d x %d, batch %d needs %zu)",
+                ws_bytes, grid->Nx, grid->Ny, grid->Nz, B, cf_diag2_bytes(grid, B));
+  LAUNCHCHK(launch("k_chanflow_diag_part", k_chanflow_diag_part, dim3(grid->Ny + 1, B), dim3(256), 0, c.st, c.geo, c.tab,
+                   ChanflowCFields{(const double*)U, (const double*)V, (const double*)W}, (const double*)p2, (double*)ws));
+  return launch("k_chanflow_diag_finish", k_chanflow_diag_finish, dim3(B), dim3(256), 0, c.st, c.geo, (const double*)ws, (const double*)dpdx,
+                (double*)out, out_stride);
+}
+extern "C" int fno_ctrl_stats_update(const FnoCtrlStats* tab, int nfields, long long count, void* stream) {
+  static_assert(FNO_CTRL_STATS_MAX == kCtrlStatsMax, "statistics table size");
+  if (!tab) return fail(FNO_EINVAL, "fno_ctrl_stats_update: null table");
+  if (nfields < 1 || nfields > kCtrlStatsMax)
+    return fail(FNO_EINVAL, "fno_ctrl_stats_update: 1..%d fields per launch (got %d)", kCtrlStatsMax, nfields);
+  if (count < 1) return fail(FNO_EINVAL, "fno_ctrl_stats_update: count is the number of snapshots including this one (got %lld)", count);
+  CtrlStatsTab t;
+  size_t most = 0;
+  for (int f = 0; f < kCtrlStatsMax; ++f) {
+    const bool on = f < nfields;
+    t.x[f] = on ? tab->x[f] : nullptr; t.mean[f] = on ? tab->mean[f] : nullptr; t.m2[f] = on ? tab->m2[f] : nullptr; t.n[f] = on ? tab->n[f] : 0;
+    if (!on) continue;
+    if (!t.x[f] || !t.mean[f] || !t.m2[f] || (((uintptr_t)t.x[f] | (uintptr_t)t.mean[f] | (uintptr_t)t.m2[f]) & 7) || t.n[f] < 1)
+      return fail(FNO_EINVAL, "fno_ctrl_stats_update: field %d is null, misaligned or empty", f);
+    most = std::max(most, t.n[f]);
+  }
+  const unsigned gx = (unsigned)std::min<size_t>((most + 255) / 256, 4096);
+  return launch("k_ctrl_stats", k_ctrl_stats, dim3(gx, nfields), dim3(256), 0, (hipStream_t)stream, t, (double)count);
 }
 
 // ===========================================================================

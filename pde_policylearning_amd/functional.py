@@ -965,7 +965,7 @@ def chanflow_rhs(grid, U, V, W, dPdx):
     U, V, W = (_operand(e, n, t, U, dtype=U.dtype) for n, t in (("U", U), ("V", V), ("W", W)))
     B = U.shape[0]
     dp, dflt = None, 0.0
-    if torch.is_tensor(dPdx) and dPdx.numel() > 1:
+    if torch.is_tensor(dPdx) and (dPdx.numel() > 1 or (dPdx.is_cuda and B == 1)):      # a device value is read on the device
         dp = _operand(e, "dPdx", dPdx.to(device=U.device, dtype=U.dtype), U, dtype=U.dtype, numel=B).reshape(B)
     else:
         dflt = float(dPdx)
@@ -1186,6 +1186,170 @@ class GraphedChannelStep:
     def step(self):
         self.graph.replay()
         return self.p1, self.p2
+
+
+# ----------------------------------------------------------------------------
+# closed-loop control (run_control.py): observation / action bridges, two-level diagnostics, running statistics
+# ----------------------------------------------------------------------------
+CONTROL_LOG = CHANFLOW_DIAG + ("dPdx",)      # columns of chanflow_diagnostics2: one row of a (T, B, 13) control log
+STATS_MAX_FIELDS = _lib.FNO_CTRL_STATS_MAX
+
+
+def _gpu_anchor(e, name, t):
+    """the first operand of a float64 entry point (_require_cuda is the float32 one): a GPU tensor, or a refusal"""
+    if not torch.is_tensor(t):
+        raise _refuse(e, name, "be a tensor", type(t).__name__)
+    if not t.is_cuda:
+        raise _refuse(e, name, "live on the GPU (the engine has no CPU path)", t.device)
+    return t
+
+
+def _plane_stats(e, mean, std, anchor, plane):
+    return (_operand(e, "mean", mean, anchor, dtype=torch.float64, numel=plane),
+            _operand(e, "std", std, anchor, dtype=torch.float64, numel=plane))
+
+
+def _strided_rows(e, name, t, anchor, B, plane, stride):
+    """a dense float32 tensor read or written as B rows of `plane` floats, `stride` floats apart"""
+    t = _operand(e, name, t, anchor, dtype=torch.float32, layout="dense")
+    if stride < plane or t.numel() < (B - 1) * stride + plane:
+        raise _refuse(e, name, f"hold {B} planes of {plane} floats {stride} apart", f"{t.numel()} elements, shape {tuple(t.shape)}")
+    return t
+
+
+def ctrl_encode(p, mean, std, eps=1e-5, out=None, batch_stride=None):
+    """out[b * batch_stride + i] = float32((p[b].flatten()[i] - mean[i]) / (std[i] + eps)): NormalizerGivenMeanStd.encode on the
+    float64 observation followed by .float() (run_control.py:139-141), in one launch.  p (B, Nx, Nz) float64; mean, std float64
+    with Nx * Nz elements.  `out`: a dense float32 tensor, e.g. the persistent (B, 3, Nx, Nz) observer input with
+    batch_stride = 3 * Nx * Nz (channel 0 is written, the grid channels are left alone); None: a new (B, Nx, Nz)."""
+    e = "ctrl_encode"
+    _gpu_anchor(e, "p", p)
+    if p.dim() < 2:
+        raise _refuse(e, "p", "be (B, Nx, Nz)", tuple(p.shape))
+    B, plane = p.shape[0], p[0].numel()
+    p = _operand(e, "p", p, p, dtype=torch.float64)
+    mean, std = _plane_stats(e, mean, std, p, plane)
+    if out is None:
+        out, batch_stride = torch.empty(p.shape, dtype=torch.float32, device=p.device), plane
+    stride = plane if batch_stride is None else int(batch_stride)
+    out = _strided_rows(e, "out", out, p, B, plane, stride)
+    _call(e, p.device, "fno_ctrl_encode", B, plane, p, mean, std, float(eps), out, stride, STREAM)
+    return out
+
+
+def ctrl_decode(y, mean, std, eps=1e-5, shape=None, batch_stride=None, scale=1.0, clip=0.0, zero_mean=False, out=None):
+    """opV1, opV2 (B, Nx, Nz) float64 from the float32 model output: opV2 = y.double() * (std + eps) + mean
+    (NormalizerGivenMeanStd.decode), then * scale, clamp to +-clip (0 = off) and, with zero_mean, minus each sample's own plane
+    mean (run_control.py:223), in this order; opV1 = 0 (one-sided control, :154).  y: dense float32 holding B planes
+    `batch_stride` floats apart (default: the plane); `shape` = (B, Nx, Nz) unless `out` = (opV1, opV2) gives it."""
+    e = "ctrl_decode"
+    _gpu_anchor(e, "y", y)
+    if out is not None:
+        shape = tuple(out[1].shape)
+    if shape is None:
+        raise _refuse(e, "shape", "be given as (B, Nx, Nz), or `out`", None)
+    shape = tuple(int(v) for v in shape)
+    B, plane = shape[0], math.prod(shape[1:])
+    stride = plane if batch_stride is None else int(batch_stride)
+    y = _strided_rows(e, "y", y, y, B, plane, stride)
+    mean, std = _plane_stats(e, mean, std, y, plane)
+    if out is None:
+        out = (torch.empty(shape, dtype=torch.float64, device=y.device), torch.empty(shape, dtype=torch.float64, device=y.device))
+    v1, v2 = (_operand(e, n, t, y, dtype=torch.float64, shape=shape, layout="dense") for n, t in zip(("opV1", "opV2"), out))
+    _call(e, y.device, "fno_ctrl_decode", B, plane, y, stride, mean, std, float(eps), float(scale), float(clip), int(bool(zero_mean)),
+          v1, v2, STREAM)
+    return v1, v2
+
+
+def chanflow_diagnostics2_workspace(grid, B, device):
+    """the partial-sum workspace of chanflow_diagnostics2 for `B` environments on this grid (its size is checked exactly)"""
+    g = grid.desc()
+    n = _lib.lib().fno_chanflow_diagnostics2_workspace_bytes(C.byref(g), B)
+    if n == 0:
+        raise RuntimeError("fnoengine chanflow_diagnostics2: " + _lib.lib().fno_last_error().decode("utf-8", "replace"))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def chanflow_diagnostics2(grid, poisson, U, V, W, p2, dPdx, out=None, ws=None):
+    """(B, 13) float64, columns CONTROL_LOG: chanflow_diagnostics and dPdx as a two-level reduction (a workgroup per wall-normal
+    row and sample, then one per sample in a fixed order), written straight into `out`: a (B, 13) tensor or one row log[r] of a
+    (T, B, 13) device log.  dPdx: the (B,) float64 device tensor of the step.  `ws`: chanflow_diagnostics2_workspace of this
+    grid and batch."""
+    e = "chanflow_diagnostics2"
+    grid._check_fields(U, V, W, e)
+    dt = U.dtype
+    U, V, W = (_operand(e, n, t, U, dtype=dt) for n, t in (("U", U), ("V", V), ("W", W)))
+    B, ncol = U.shape[0], len(CONTROL_LOG)
+    m = _operand(e, "grid metrics", grid.metrics(U.device), U, dtype=torch.float64, numel=3 * (grid.Ny + 2))
+    tab = _operand(e, "Poisson table", poisson.table(U.device), U, dtype=torch.float64)
+    p2 = _operand(e, "p2", p2, U, dtype=torch.float64, shape=(B, grid.Nx, grid.Nz), optional=True)
+    if not torch.is_tensor(dPdx):
+        raise _refuse(e, "dPdx", "be a (B,) float64 tensor", type(dPdx).__name__)
+    dp = _per_sample(e, "dPdx", dPdx, U)
+    if out is None:
+        out = torch.empty((B, ncol), dtype=torch.float64, device=U.device)
+    out = _operand(e, "out", out, U, dtype=torch.float64, shape=(B, ncol), layout="keep")
+    stride = out.stride(0) if B > 1 else ncol
+    if out.stride(1) != 1 or stride < ncol:
+        raise _refuse(e, "out", "have unit-stride rows at least 13 apart", f"strides {out.stride()}")
+    g = grid.desc()
+    need = _lib.lib().fno_chanflow_diagnostics2_workspace_bytes(C.byref(g), B)
+    if ws is None:
+        ws = chanflow_diagnostics2_workspace(grid, B, U.device)
+    ws = _operand(e, "workspace", ws, U, dtype=torch.uint8, layout="dense")
+    if ws.numel() != need:
+        raise _refuse(e, "workspace", f"be the {need} bytes of this grid and a batch of {B}", f"{ws.numel()} bytes")
+    _call(e, U.device, "fno_chanflow_diagnostics2", C.byref(g), B, {torch.float64: 1, torch.float32: 0}.get(dt, -1), m, tab,
+          tab.numel() * 8, U, V, W, p2, dp, out, stride, ws, ws.numel(), STREAM)
+    return out
+
+
+def running_stats_update(fields, means, m2s, count):
+    """One more snapshot into the running per-point statistics of up to eight fields, in ONE launch (the reference recomputes
+    np.array(all_so_far).mean(0) / .std(0) on every collected step, run_control.py:245-293).  fields[k], means[k], m2s[k]:
+    float64 tensors of one size per k, updated in place (Welford); `count`: snapshots including this one (1 initialises).
+    std = sqrt(M2 / count), the population form like np.std."""
+    e = "running_stats_update"
+    fields, means, m2s = list(fields), list(means), list(m2s)
+    if not 1 <= len(fields) <= STATS_MAX_FIELDS:
+        raise _refuse(e, "fields", f"be 1..{STATS_MAX_FIELDS} tensors per launch", len(fields))
+    if len(means) != len(fields) or len(m2s) != len(fields):
+        raise _refuse(e, "means / m2s", f"have one tensor per field ({len(fields)})", (len(means), len(m2s)))
+    if int(count) < 1:
+        raise _refuse(e, "count", "be the number of snapshots including this one (>= 1)", count)
+    anchor = _gpu_anchor(e, "fields[0]", fields[0])
+    tab, keep = _lib.FnoCtrlStats(), []
+    for k, (x, mu, m2) in enumerate(zip(fields, means, m2s)):
+        x = _operand(e, f"fields[{k}]", x, anchor, dtype=torch.float64)
+        mu = _operand(e, f"means[{k}]", mu, anchor, dtype=torch.float64, numel=x.numel(), layout="dense")
+        m2 = _operand(e, f"m2s[{k}]", m2, anchor, dtype=torch.float64, numel=x.numel(), layout="dense")
+        tab.x[k], tab.mean[k], tab.m2[k], tab.n[k] = _ptr(x), _ptr(mu), _ptr(m2), x.numel()
+        keep.append(x)
+    _call(e, anchor.device, "fno_ctrl_stats_update", C.byref(tab), len(fields), int(count), STREAM)
+
+
+class GraphedControlLoop:
+    """One control iteration (action from the observation, RK3 step, wall pressure, diagnostics) replayed as ONE graph, captured
+    on one stream with no forked branches, like GraphedChannelStep.  `body`: a callable that runs the iteration on persistent
+    tensors; `state`: the tensors it updates in place, restored after the eager run that loads the code objects."""
+
+    def __init__(self, body, state, device):
+        saved = [t.clone() for t in state]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream(device).wait_stream(side)
+        for t, s in zip(state, saved):
+            t.copy_(s)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            body()
+        for t, s in zip(state, saved):
+            t.copy_(s)
+
+    def replay(self):
+        self.graph.replay()
 
 
 # ----------------------------------------------------------------------------

@@ -1,0 +1,135 @@
+"""Closed-loop control on the engine: the counterpart of the reference's run_control.py.
+
+  python -m pde_policylearning_amd.run_control --control_yaml configs/base_control.yaml [--ensemble B] [--graph] [--tanh-channel]
+
+The reference's YAMLs drop in: the file is merged over the flags exactly as train_observer does (yaml.safe_load, the YAML's keys
+win).  Keys read: policy_name, model_name, load_model_name, modes, width, x_range, y_range, control_timestep, detect_plane,
+noise_scale, collect_data, DATA_FOLDER, state_path_name, output_dir, exp_name, Re; visualisation and W&B keys are carried in the
+plan and ignored.  The loop runs control_timestep + 1 iterations (run_control.py:133).  --ensemble B steps B environments under
+one policy (each with its own noise draw when noise_scale > 0), --graph replays the iteration as one graph, --tanh-channel starts
+from an analytic state on a tanh grid when there is no `.mat` initial condition."""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .control import Collector, ControlLoop, make_policy
+from .train_observer import load_train_yaml
+
+_KEYS = ("policy_name", "model_name", "load_model_name", "modes", "width", "x_range", "y_range", "control_timestep", "detect_plane",
+         "noise_scale", "collect_data", "DATA_FOLDER", "state_path_name", "output_dir", "exp_name", "Re")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--control_yaml", "--control-yaml", dest="control_yaml", default=None, help="a reference YAML: its keys win over the flags")
+    ap.add_argument("--policy_name", default="gt", help="gt | unmanipulated | fno | rno")
+    ap.add_argument("--model_name", default="FNO2dObserver")
+    ap.add_argument("--load_model_name", default=None, help="whole pickled module under output_dir (train_observer's save_if_best)")
+    ap.add_argument("--modes", type=int, default=12)
+    ap.add_argument("--width", type=int, default=32)
+    ap.add_argument("--x_range", type=int, default=32)
+    ap.add_argument("--y_range", type=int, default=32)
+    ap.add_argument("--control_timestep", type=int, default=200)
+    ap.add_argument("--detect_plane", type=int, default=-10)
+    ap.add_argument("--noise_scale", type=float, default=0.0)
+    ap.add_argument("--collect_data", action="store_true")
+    ap.add_argument("--collect_start", type=int, default=0)
+    ap.add_argument("--DATA_FOLDER", default=None, help="the dataset whose statistics normalise a neural policy")
+    ap.add_argument("--state_path_name", default=None, help="`.mat` initial condition")
+    ap.add_argument("--output_dir", default="./outputs")
+    ap.add_argument("--exp_name", default="control")
+    ap.add_argument("--Re", type=float, default=-1.0)
+    ap.add_argument("--ensemble", type=int, default=1, help="environments stepped under the one policy")
+    ap.add_argument("--graph", action="store_true", help="replay the iteration as one graph")
+    ap.add_argument("--tanh-channel", dest="tanh_channel", action="store_true", help="analytic start state on a tanh grid")
+    ap.add_argument("--check_every", type=int, default=50)
+    ap.add_argument("--seed", type=int, default=0)
+    return ap
+
+
+def plan_from_yaml(args, yaml_dict=None):
+    """flags + (optionally) a reference YAML -> the run plan, with merge_args_with_yaml's semantics (libs/arguments.py:16-26).
+    Returns a new namespace with `steps`, `collect_folder` and the policy checked; `args` is not modified."""
+    plan = dict(vars(args))
+    if yaml_dict is None and plan.get("control_yaml"):
+        yaml_dict = load_train_yaml(plan["control_yaml"])
+    plan.update(dict(yaml_dict or {}))
+    ns = argparse.Namespace(**plan)
+    if ns.policy_name in ("rand", "optimal-observer", "optimal-policy-observer"):
+        make_policy(ns.policy_name)                                      # raises NotImplementedError with the reason
+    if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno"):
+        raise RuntimeError("Not supported policy name.")
+    if ns.policy_name not in ("gt", "unmanipulated"):
+        ns.collect_data = False                                          # run_control.py:45-46
+    ns.steps = int(ns.control_timestep) + 1                              # :133
+    ns.collect_folder = os.path.join(ns.output_dir, ns.exp_name) if ns.collect_data else None      # :112-114
+    ns.ensemble = max(int(getattr(ns, "ensemble", 1)), 1)
+    if ns.policy_name in ("fno", "rno") and not ns.load_model_name:
+        raise ValueError("run_control: a neural policy needs load_model_name (a model saved by train_observer)")
+    if not ns.state_path_name and not getattr(ns, "tanh_channel", False):
+        raise ValueError("run_control: no initial condition (state_path_name, or --tanh-channel)")
+    return ns
+
+
+def analytic_state(rhs, B, seed, noise=0.05):
+    """a parabolic streamwise profile plus seeded noise on the grid of `rhs` (a ChannelFlowRHS), B samples"""
+    rng = np.random.default_rng(seed)
+    yc = np.concatenate(([rhs.yg[0]], rhs.ym, [rhs.yg[-1]]))
+    su, sv = (B, rhs.Nx, rhs.Ny + 1, rhs.Nz), (B, rhs.Nx, rhs.Ny, rhs.Nz)
+    U = (1.5 * yc * (2 - yc))[None, None, :, None] * np.ones(su) + noise * rng.standard_normal(su)
+    V = noise * rng.standard_normal(sv)
+    V -= V.mean(axis=(1, 3), keepdims=True)            # no net flux through any plane: opposition control then carries none either
+    return U, V, noise * rng.standard_normal(su)
+
+
+def make_env(plan, device="cuda"):
+    from .libs.envs.control_env import ChannelFlowEnv, ChannelFlowRHS, load_state_mat
+    B = plan.ensemble
+    kw = dict(Re=plan.Re, detect_plane=abs(int(plan.detect_plane)), device=device)
+    if plan.state_path_name and os.path.exists(plan.state_path_name):
+        x, y, z, ym, U, V, W = load_state_mat(plan.state_path_name)
+        U, V, W = (np.repeat(np.asarray(a, dtype=np.float64)[None], B, 0) if B > 1 else a for a in (U, V, W))
+        env = ChannelFlowEnv(len(x) - 2, len(z) - 2, x[1] - x[0], z[1] - z[0], y, ym, U, V, W, x=x, z=z, **kw)
+    elif getattr(plan, "tanh_channel", False):
+        rhs = ChannelFlowRHS.tanh_channel(Nx=plan.x_range, Nz=plan.y_range, Re=plan.Re)
+        U, V, W = analytic_state(rhs, B, plan.seed)
+        if B == 1:
+            U, V, W = U[0], V[0], W[0]
+        env = ChannelFlowEnv(rhs.Nx, rhs.Nz, rhs.dx, rhs.dz, rhs.y, rhs.ym, U, V, W, **kw)
+    else:
+        raise FileNotFoundError(f"run_control: initial condition {plan.state_path_name!r} not found (or pass --tanh-channel)")
+    if plan.noise_scale > 0:
+        torch.manual_seed(plan.seed)
+        env.add_random_noise(plan.noise_scale)                           # control_env.py:86-88
+    return env
+
+
+def make_plan_policy(plan, device="cuda"):
+    if plan.policy_name in ("gt", "unmanipulated"):
+        return make_policy(plan.policy_name)
+    from .libs.pde_data_loader import PDEDataset
+    observer = torch.load(os.path.join(plan.output_dir, plan.load_model_name), map_location=device, weights_only=False)   # run_control.py:40
+    ds = PDEDataset(plan, plan.DATA_FOLDER, [0], 1, plan.x_range, plan.y_range)
+    return make_policy(plan.policy_name, observer=observer, p_norm=ds.p_norm, v_norm=ds.v_norm)
+
+
+def run(plan):
+    env = make_env(plan)
+    policy = make_plan_policy(plan, env.device)
+    collector = Collector(plan.collect_folder, plan.collect_start, re=plan.Re) if plan.collect_folder else None
+    result = ControlLoop(env, policy, plan.steps, collector=collector, graph=plan.graph, check_every=plan.check_every).run()
+    last = result.infos[-1]
+    for b, info in enumerate(last if isinstance(last, list) else [last]):
+        rel = info.get("drag_reduction_relative/3_3_dPdx_reverse_cal")
+        print(f"env {b}: dPdx {info['drag_reduction/3_3_dPdx_reverse_cal']:.7f}" + (f"; DR {1 - rel:.4f}" if rel is not None else ""))
+    return result
+
+
+def main():
+    run(plan_from_yaml(build_parser().parse_args()))
+
+
+if __name__ == "__main__":
+    main()

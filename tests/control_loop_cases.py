@@ -1,0 +1,159 @@
+"""Helpers of the control-loop tests (a helper module, not a conftest): the tolerance rule, the fixtures and the float64
+restatement of the closed loop.
+
+The rule, restated from the channel-flow step tests.  Nothing is tuned to what the kernels give.  For every compared quantity
+the test first measures the FLOOR on the CPU at the size at hand (what the floor is is said per case: a second evaluation of
+the reference in another precision or order, or the restatement re-run from a state perturbed by a relative 1e-16) and the GPU
+gets
+    bound = min(16 * max(floor, resolution), 1e-9),    resolution = eps = 2.2e-16 unless stated
+(two float64 evaluations of one quantity differ by eps unless they are bitwise equal; 1e-9 = cond * eps of the worst Poisson
+system).  Quantities that are differences or means of signed terms are measured against the scale of what is summed, because
+that is what one rounding is relative to (`info_scales`; dPdx carries the rounding of a bulk velocity divided by dt:
+`dpdx_resolution`).  Every measured distance, its floor and its bound go to profiles/r13_control_loop_errors.txt, one block per
+case, before anything is asserted."""
+import os
+
+import numpy as np
+import torch
+
+from oracle.detfill import fill_named
+from tests import chanflow_step_reference as R
+from tests.util import load_golden
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LOG = os.path.join(ROOT, "profiles", "r13_control_loop_errors.txt")
+EPS = float(np.finfo(np.float64).eps)
+CAP = 1e-9
+DT = 1e-3
+
+
+def bound(floor, resolution=EPS):
+    return min(16.0 * max(floor, resolution), CAP)
+
+
+def log_block(section, lines):
+    """replace `section` of the error log by `lines` (one file, one block per case)"""
+    try:
+        old = open(LOG).read().split("\n## ") if os.path.exists(LOG) else []
+        keep = [b for b in old if b.strip() and not b.lstrip("# ").startswith(section + "\n")]
+        body = "\n## ".join([b.lstrip("# ").rstrip("\n") for b in keep] + [section + "\n" + "\n".join(lines)])
+        os.makedirs(os.path.dirname(LOG), exist_ok=True)
+        with open(LOG, "w") as f:
+            f.write("## " + body + "\n")
+    except OSError as e:
+        import warnings
+        warnings.warn(f"the error log {LOG} could not be written ({e}); the figures of `{section}` are on stdout only")
+
+
+def judge(section, rows):
+    """rows: (name, gpu distance, floor, resolution[, raw gpu distance relative to the entry's own magnitude]).  Logs all, then
+    asserts all."""
+    lines, bad = [], []
+    for name, got, floor, res, *raw in rows:
+        b = bound(floor, res)
+        lines.append(f"{name:52s} gpu {got:.3e}   floor {floor:.3e}   resolution {res:.3e}   bound {b:.3e}   {'ok' if got <= b else 'MISS'}")
+        if raw:
+            lines[-1] += f"   [own magnitude: gpu {raw[0]:.3e}]"
+        print(section, lines[-1])
+        if not got <= b:
+            bad.append(lines[-1])
+    log_block(section, lines)
+    assert not bad, "\n".join([section] + bad)
+
+
+def fixture_state(tag, b=0):
+    """the deterministic float64 sample behind tests/golden/chanflow_<tag>.npz; b > 0: further samples of a batch"""
+    Nx, Ny, Nz = (int(v) for v in load_golden("chanflow_" + tag)["meta"][:3])
+    sfx = f"{tag}" if b == 0 else f"{tag}.b{b}"
+    f = lambda n, shp, s: fill_named(f"input:chanflow.{n}.{sfx}", shp, s, dtype=np.float64)
+    U = 1.0 + f("U", (Nx, Ny + 1, Nz), 0.5)
+    V = f("Vgt", (Nx, Ny, Nz), 0.3) + f("dV", (Nx, Ny, Nz), 0.1)
+    W = f("W", (Nx, Ny + 1, Nz), 0.3)
+    return R.Grid(Nx, Ny, Nz), U, V, W
+
+
+def engine(g):
+    from pde_policylearning_amd import functional as F
+    grid = F.ChannelGrid(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, g.yg, g.nu)
+    return grid, F.ChannelPoisson(grid)
+
+
+def to_dev(dev, *arrs):
+    return [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrs]
+
+
+def to_np(t):
+    return t.detach().cpu().numpy()
+
+
+def bits_equal(a, b):
+    a, b = a.contiguous(), b.contiguous()
+    it = {4: torch.int32, 8: torch.int64}[a.element_size()]
+    return a.shape == b.shape and torch.equal(a.view(it), b.view(it))
+
+
+def info_scales(g, U, V, W, p2):
+    """what one rounding of each cancelling `info` entry is relative to; entries not listed: their own magnitude"""
+    hy = np.diff(g.y)[None, :, None]
+    grads = np.abs((np.roll(U, -1, 0) - U)[:, 1:-1] / g.dx).sum() + np.abs((V[:, 1:] - V[:, :-1]) / hy).sum() + \
+        np.abs((np.roll(W, -1, 2) - W)[:, 1:-1] / g.dz).sum()
+    shear = np.mean(np.abs(U[:, -1] * V[:, -1]) + np.abs(g.nu * (U[:, -2] - U[:, -3]) / (g.y[-1] - g.y[-2])))
+    return {"drag_reduction/4_1_-|divergence|": grads, "drag_reduction/1_shear_stress": shear,
+            "drag_reduction/3_1_pressure_mean": np.abs(p2).mean()}
+
+
+def dpdx_resolution(m0, dpdx):
+    return EPS * abs(m0) / DT / abs(dpdx)
+
+
+def make_env(dev, g, states, plane):
+    """ChannelFlowEnv over `states` = [(U, V, W), ...]: one environment without a batch dimension, several as a batch"""
+    from pde_policylearning_amd.libs.envs.control_env import ChannelFlowEnv
+    U, V, W = (np.stack([s[k] for s in states]) if len(states) > 1 else states[0][k] for k in range(3))
+    return ChannelFlowEnv(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, U, V, W, dt=DT, detect_plane=plane, device=dev)
+
+
+def restated_rollout(g, state, steps, plane=None, actions=None, perturb=None):
+    """The closed loop in float64 on the CPU, one environment.  Action of iteration t: opposition control at `plane`
+    (R.gt_control) or `actions[t]` = (opV1, opV2).  perturb: a seed; the initial state is multiplied by 1 + 1e-16 N(0, 1), the
+    run the floors are taken from.  Returns per iteration the observation before the action, and after the step the state,
+    dPdx, the new observation and the info."""
+    U, V, W = (np.array(a, dtype=np.float64) for a in state)
+    m0 = R.bulk_velocity(g, U)                  # of the unperturbed state: the environment's meanU0
+    if perturb is not None:
+        rng = np.random.default_rng(perturb)
+        U, V, W = (a * (1 + 1e-16 * rng.standard_normal(a.shape)) for a in (U, V, W))
+    dp = R.DPDX0
+    p2 = R.pressure(g, U, V, W, dp)[1]
+    out = []
+    for t in range(steps):
+        v1, v2 = R.gt_control(V, plane) if actions is None else actions[t]
+        obs = p2
+        U, V, W, dp = R.rk3_step(g, U, V, W, v1, v2, dp, m0, DT)
+        p2 = R.pressure(g, U, V, W, dp)[1]
+        out.append({"obs": obs, "action": v2, "state": (U, V, W), "dPdx": dp, "p2": p2, "info": R.step_info(g, U, V, W, p2, dp),
+                    "m0": m0})
+    return out
+
+
+def cat(state):
+    return np.concatenate([np.asarray(a).ravel() for a in state])
+
+
+def loop_rows(g, tag, gpu, base, pert):
+    """rows for judge(): GPU iteration records against the restatement `base`, floors from the perturbed run `pert`"""
+    rows = []
+    for t, (G, A, Bp) in enumerate(zip(gpu, base, pert)):
+        rows.append((f"{tag} it {t} state", R.rel(cat(G["state"]), cat(A["state"])), R.rel(cat(Bp["state"]), cat(A["state"])), EPS))
+        rows.append((f"{tag} it {t} observation", R.rel(G["obs"], A["obs"]), R.rel(Bp["obs"], A["obs"]), EPS))
+        res = dpdx_resolution(A["m0"], A["dPdx"])
+        rows.append((f"{tag} it {t} dPdx", abs(G["dPdx"] - A["dPdx"]) / abs(A["dPdx"]), abs(Bp["dPdx"] - A["dPdx"]) / abs(A["dPdx"]), res))
+        if "info" in G:
+            scales = info_scales(g, *A["state"], A["p2"])
+            for k in R.INFO_KEYS:
+                want = A["info"][k]
+                s = scales.get(k, abs(want))
+                own = abs(want) if want != 0 else 1.0
+                rows.append((f"{tag} it {t} {k}", abs(G["info"][k] - want) / s, abs(Bp["info"][k] - want) / s,
+                             res if k.endswith("dPdx_reverse_cal") else EPS, abs(G["info"][k] - want) / own))
+    return rows
