@@ -32,8 +32,9 @@ def build(force=False, verbose=True):
     # operands - the form that misreads lanes 48-63 beside another wave's matrix instructions on gfx950 (fno_dev.h,
     # tools/pk_opsel_hazard.hip).  Without it NO kernel of the library carries the form (tools/check_opsel.py, linted in
     # tests/test_abi_and_host.py); cost measured in round 5: +0.5 % (config 2) to -1.4 % (PINO fine-tuning) fields/s.
+    # -Werror=undef: an identifier that `#if` tests but nothing defines is an error, not a silent 0.
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-slp-vectorize",
-           "-Wno-unused-value", "-Wno-unused-result"] + os.environ.get("FNO_EXTRA_FLAGS", "").split() + ["-o", OUT, SRC]
+           "-Wno-unused-value", "-Wno-unused-result", "-Werror=undef"] + os.environ.get("FNO_EXTRA_FLAGS", "").split() + ["-o", OUT, SRC]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -81,12 +81,6 @@ static thread_local int g_terms_next = 0;
 #define GT(n) (g_terms_next = (n))
 static std::vector<ProfAgg> g_agg;
 
-#ifdef PFW_TRACE
-extern "C" int fno_debug_pfw_dump(unsigned long long* host, size_t n) {
-  hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pfw_trace), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-#endif
 #ifdef FNO_CLOCK
 extern "C" int fno_debug_clock_dump(unsigned long long* host, size_t n) {
   hipDeviceSynchronize();
@@ -962,25 +956,13 @@ static const int kBndProj = 59, kBndDy = kBndProj + 1, kBndW1 = kBndProj + 2, kB
 static_assert(kBndX < bnd_u(0) && bnd_u(FNO_MAX_LAYERS) < bnd_g(0) && bnd_g(FNO_MAX_LAYERS) < kBndProj && kBndW2 < kNAmax,
               "bound slots: [8, 32) forward |u_l|, [32, 59) backward |g_l|, [59, 63) projection scalars");
 // persistent-grid size per CU of the forward kernels (= workgroups that fit: registers / LDS)
-#ifndef FNO_GRID_LIFT
-#define FNO_GRID_LIFT 3
-#endif
-#ifndef FNO_GRID_PW
-#define FNO_GRID_PW 2
-#endif
-#ifndef FNO_GRID_BWD
-#define FNO_GRID_BWD 1   // persistent workgroups per CU of the backward kernels: their LDS footprint allows one resident
-                         // workgroup, and every extra one adds a partial slab to reduce
-#endif
-#ifndef FNO_GRID_PWX
-#define FNO_GRID_PWX 4
-#endif
-#ifndef FNO_NTW_PWX
-#define FNO_NTW_PWX 2   // 4-wave workgroups, two per CU
-#endif
-#ifndef FNO_GRID_PF
-#define FNO_GRID_PF 1
-#endif
+static constexpr int FNO_GRID_LIFT = 3;
+static constexpr int FNO_GRID_PW = 2;
+static constexpr int FNO_GRID_BWD = 1;   // persistent workgroups per CU of the backward kernels: their LDS footprint allows one resident
+                                         // workgroup, and every extra one adds a partial slab to reduce
+static constexpr int FNO_GRID_PWX = 4;
+static constexpr int FNO_NTW_PWX = 2;    // 4-wave workgroups, two per CU
+static constexpr int FNO_GRID_PF = 1;
 
 extern "C" int fno_model_plan_create(const FnoModelDesc* d, FnoModelPlan** out) {
   if (!d || !out) return fail(FNO_EINVAL, "null argument");
@@ -1701,10 +1683,7 @@ static int model_backward_impl(const FnoModelPlan* p, int B, const FnoModelParam
   // the same `saved` must not keep the first one's.  (Not after a forward that has just cleared all slots: one 4.5 us fill
   // less per step; a second backward on the same `saved`, or an unknown buffer, clears.)
   bool db2_done = false;
-#ifndef FNO_DEBUG_NO_BWD_FILL      // (debug builds of the detector test: 1 = never clear - tests/test_boundary_gpu.py must then fail)
-#define FNO_DEBUG_NO_BWD_FILL 0
-#endif
-  if (!FNO_DEBUG_NO_BWD_FILL && h2_chain && !(cs_found && cs.bwd_clean) &&
+  if (h2_chain && !(cs_found && cs.bwd_clean) &&
       hipMemsetAsync(amax + bnd_g(0), 0, (kNAmax - bnd_g(0)) * sizeof(float), st) != hipSuccess)
     return fail(FNO_EHIP, "memset of the magnitude bounds");
   if (use_pbwd_t(C, d.Cout, p->NPX)) {      // (split mode, one output channel: k_proj_bwd_t reads W1 as packed fragments)

@@ -22,21 +22,6 @@ FNO_DEV f32x16 mfma32(float a, float b, f32x16 c) {
 FNO_DEV f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-// 8-wave workgroups place waves w and w + 4 on the same SIMD.  Both run the same phase sequence between the same
-// barriers, so without help they reach their MFMA bursts and their VALU bursts together and the two pipes take turns
-// instead of overlapping (phase trace: A1 + E + A3 of the projection backward = MFMA time + VALU time).  Raising the
-// issue priority of one partner lets it run ahead: its VALU phase then overlaps the other's matrix phase.
-// FNO_PRIO: 0 = off, 1 = waves [0, n/2) high, 2 = waves [n/2, n) high.
-#ifndef FNO_PRIO
-#define FNO_PRIO 0
-#endif
-#if FNO_PRIO == 1
-#define FNO_SIMD_PARTNER_PRIO(wave, nwaves) do { if ((nwaves) == 8 && (wave) < 4) __builtin_amdgcn_s_setprio(2); } while (0)
-#elif FNO_PRIO == 2
-#define FNO_SIMD_PARTNER_PRIO(wave, nwaves) do { if ((nwaves) == 8 && (wave) >= 4) __builtin_amdgcn_s_setprio(2); } while (0)
-#else
-#define FNO_SIMD_PARTNER_PRIO(wave, nwaves) do { } while (0)
-#endif
 // FNO_TRACE_WHICH selects the traced kernel: 1 = projection backward, 2 = block backward (a middle block)
 #ifndef FNO_TRACE_WHICH
 #define FNO_TRACE_WHICH 1
@@ -140,21 +125,13 @@ FNO_DEV float gelu_grad_f(float x) { float g, d; gelu_both(x, g, d); return d; }
 // (half the issue slots), the clamps v_med3_f32 (a target intrinsic: no canonicalisation) and the sign select of the
 // derivative form a v_bfi: 15 instead of 26 instructions per pair for the value, 22 instead of ~36 for value + derivative.
 // Same polynomials and the same final operations as the scalar forms.  `six` / `inf` = 6.0f / +infinity in SGPRs
-// (gelu_consts: VOP3 takes no literal on gfx9).  -DFNO_GELU_PK=0 restores the scalar forms (A/B arm).
-#ifndef FNO_GELU_PK
-#define FNO_GELU_PK 1
-#endif
+// (gelu_consts: VOP3 takes no literal on gfx9).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 FNO_DEV void gelu_consts(float& six, float& inf) {
   asm volatile("s_mov_b32 %0, 0x40c00000\n\ts_mov_b32 %1, 0x7f800000" : "=s"(six), "=s"(inf));
 }
 template <int NP>
 FNO_DEV void gelu_pairs(f32x2 (&x)[NP], float six, float inf) {
-#if !FNO_GELU_PK
-#pragma unroll
-  for (int p = 0; p < NP; ++p) { x[p][0] = gelu_f(x[p][0]); x[p][1] = gelu_f(x[p][1]); }
-  return;
-#endif
   f32x2 s[NP], r[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
@@ -208,46 +185,14 @@ FNO_DEV float4 gelu4(const float4& v, float six, float inf) {
   gelu_pairs<2>(x, six, inf);
   return make_float4(x[0][0], x[0][1], x[1][0], x[1][1]);
 }
-// value and derivative of a pair (gelu_both's formulas: erfc by Abramowitz-Stegun 7.1.26, one v_exp and one v_rcp per element
-// shared by both).  The branch `x >= 0 ? 1 - q : q` becomes 0.5 + copysign(0.5 - q, x).
-FNO_DEV void gelu_both2(f32x2 x, f32x2& g, f32x2& dg) {
-#if !FNO_GELU_PK
-  { float g0, d0, g1, d1; gelu_both(x[0], g0, d0); gelu_both(x[1], g1, d1); g = f32x2{g0, g1}; dg = f32x2{d0, d1}; }
-  return;
-#endif
-  const f32x2 ax = {__builtin_fabsf(x[0]), __builtin_fabsf(x[1])};
-  f32x2 t = __builtin_elementwise_fma(ax, f32x2{0.3275911f * 0.70710678118654752440f, 0.3275911f * 0.70710678118654752440f}, f32x2{1.0f, 1.0f});
-  t[0] = __builtin_amdgcn_rcpf(t[0]); t[1] = __builtin_amdgcn_rcpf(t[1]);
-  // 0.5 * (((((a5 t + a4) t + a3) t + a2) t + a1) t): the 0.5 of q = 0.5 poly e is folded into the coefficients
-  f32x2 poly = __builtin_elementwise_fma(t, f32x2{0.5f * 1.061405429f, 0.5f * 1.061405429f}, f32x2{0.5f * -1.453152027f, 0.5f * -1.453152027f});
-  poly = __builtin_elementwise_fma(t, poly, f32x2{0.5f * 1.421413741f, 0.5f * 1.421413741f});
-  poly = __builtin_elementwise_fma(t, poly, f32x2{0.5f * -0.284496736f, 0.5f * -0.284496736f});
-  poly = __builtin_elementwise_fma(t, poly, f32x2{0.5f * 0.254829592f, 0.5f * 0.254829592f});
-  poly = poly * t;
-  f32x2 e = (x * x) * f32x2{-0.5f * 1.4426950408889634f, -0.5f * 1.4426950408889634f};      // exp(-x^2 / 2) = exp2(-x^2 log2(e) / 2)
-  e[0] = __builtin_amdgcn_exp2f(e[0]); e[1] = __builtin_amdgcn_exp2f(e[1]);
-  const f32x2 q = poly * e;                                 // = 0.5 erfc(|x| / sqrt 2)
-  const f32x2 hq = f32x2{0.5f, 0.5f} - q;
-  f32x2 sg;
-  sg[0] = __builtin_copysignf(hq[0], x[0]); sg[1] = __builtin_copysignf(hq[1], x[1]);
-  const f32x2 cdf = f32x2{0.5f, 0.5f} + sg;
-  g = x * cdf;
-  dg = __builtin_elementwise_fma(x * f32x2{0.39894228040143267794f, 0.39894228040143267794f}, e, cdf);
-}
-// NP pairs in lock step (gelu_both2's operations per element, bit-identical): gfx950 needs one wait state between a vector
-// instruction and a packed one that reads its result through op_sel (the broadcast constants), and the compiler schedules ONE
+// value and derivative of NP pairs in lock step (gelu_both's formulas: erfc by Abramowitz-Stegun 7.1.26, one v_exp and one v_rcp
+// per element shared by both; the branch `x >= 0 ? 1 - q : q` becomes 0.5 + copysign(0.5 - q, x), and the 0.5 of q = 0.5 poly e
+// is folded into the coefficients).  gfx950 needs one wait state between a vector instruction and a packed one that reads its
+// result through op_sel (the broadcast constants), and the compiler schedules ONE
 // pair's chain depth first and fills the gaps with s_nop 0 (k_proj_bwd_t: 103 of them per chunk, a wave alone on its SIMD pays 4
 // cycles each).  Written step by step over the pairs, the next pair's instruction sits in every gap.
-#ifndef FNO_GELU_LOCKSTEP
-#define FNO_GELU_LOCKSTEP 1      // 0: one pair after the other (A/B arm)
-#endif
 template <int NP>
 FNO_DEV void gelu_both_pairs(const f32x2 (&x)[NP], f32x2 (&g)[NP], f32x2 (&dg)[NP]) {
-#if !FNO_GELU_PK || !FNO_GELU_LOCKSTEP
-#pragma unroll
-  for (int p = 0; p < NP; ++p) gelu_both2(x[p], g[p], dg[p]);
-  return;
-#endif
   constexpr float ca = 0.3275911f * 0.70710678118654752440f;
   constexpr float cp[5] = {0.5f * 1.061405429f, 0.5f * -1.453152027f, 0.5f * 1.421413741f, 0.5f * -0.284496736f, 0.5f * 0.254829592f};
   f32x2 t[NP], poly[NP], e[NP];
@@ -379,11 +324,9 @@ FNO_DEV void split3x8(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
 }
 // acc += A * B for one 16-deep k block; a[0..2] / b[0..2] = (h, m, l) fragments; small terms first
 FNO_DEV f32x16 mfma_x3(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 acc) {
-#ifndef FNO_EXP_HALF_MFMA      // (timing experiment: what three instead of six products per k block would buy; results are wrong)
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-#endif
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
@@ -411,26 +354,19 @@ FNO_DEV float buf_ld1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
 // STREAMING loads (round 6): activations a kernel reads exactly once are loaded non-temporally - no allocation in L2 / the
 // Infinity Cache - so that what stays resident is what the kernel WRITES, which the next kernel of the chain (walking its
 // tiles in the opposite direction: "zigzag", fno_abi.hip) reads first.  Measured on the strip kernel alone: 110 -> 101 us per
-// launch (issue -> landed is shorter for nt loads, MI355X_MICROARCH.md, nt-weights).  -DFNO_NT_LOADS=0: default policy (A/B arm).
+// launch (issue -> landed is shorter for nt loads, MI355X_MICROARCH.md, nt-weights).
 // Only for loads that take WHOLE 128-byte lines per instruction: a line the L2 does not keep is fetched again by every later
 // instruction that touches another part of it (k_block_bwd_t's u loads, 16 bytes of 32 rows per instruction: 0.36 -> 0.46 ms).
-#ifndef FNO_NT_LOADS
-#define FNO_NT_LOADS 1
-#endif
 FNO_DEV float buf_ld1s(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, FNO_NT_LOADS ? 2 : 0));
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 2));
 }
 FNO_DEV float4 buf_ld4s(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, FNO_NT_LOADS ? 2 : 0));
+  const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 2));
   return make_float4(v[0], v[1], v[2], v[3]);
 }
 FNO_DEV float4 ld4s(const float* p) {
-#if FNO_NT_LOADS
   const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
   return make_float4(v[0], v[1], v[2], v[3]);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
 }
 FNO_DEV bf16x8 buf_ld8h(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -443,11 +379,9 @@ FNO_DEV bf16x8 buf_ld8h(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
 // result feeds activations or the dx chain uses this form; `hi` may be a long-running accumulator (products of one size
 // class), `lo` is summed into the result once.
 FNO_DEV void mfma_x3s(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& hi, f32x16& lo) {
-#ifndef FNO_EXP_HALF_MFMA
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], lo, 0, 0, 0);
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], lo, 0, 0, 0);
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], lo, 0, 0, 0);
-#endif
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], lo, 0, 0, 0);
   lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], lo, 0, 0, 0);
   hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], hi, 0, 0, 0);
@@ -458,7 +392,8 @@ FNO_DEV void st8h(unsigned short* p, bf16x8 v) { *reinterpret_cast<bf16x8*>(p) =
 // ---------------------------------------------------------------------------
 // fp32-grade GEMMs from TWO fp16 terms and THREE products ("h2").  The training step runs at the board's power cap
 // (1400 W, tools/smi_sample.sh): time follows energy, and halving the matrix-pipe work of the split-precision GEMMs took
-// 10 % off the step in a timing experiment (-DFNO_EXP_HALF_MFMA).  x = h + l with h = fp16(s x), l = fp16(s x - h) keeps
+// 10 % off the step in a timing experiment (round 4: three of the six products knocked out).
+// x = h + l with h = fp16(s x), l = fp16(s x - h) keeps
 // 22 significant bits when s (a power of two) brings the operand's largest magnitude to 2^13: values above 2^-16 of the
 // maximum keep a relative error of 2^-23, smaller ones an absolute error of 2^-38 of the maximum.  The products hh,
 // hl, lh (ll <= 2^-22) in fp32 accumulators give a GEMM error equal to the fp32 MFMA's own (1.5e-7 at K = 64, measured
@@ -487,61 +422,26 @@ FNO_DEV f32x2 natural_pair(float lo, float hi) {
   asm volatile("" : "+v"(p));
   return p;
 }
-// FNO_SPLIT2_VARIANT (build flag): 0 = the product; 1 = element-wise (A/B arm); 6 = the HAZARDOUS form spelled out (a pair
-// held in swapped order, un-swapped by op_sel inside the packed operations - what hipcc generated before round 4), kept so
-// that the detectors can be shown to fail on it (tools/h2_rate.py, tests/test_fullsize_gpu.py)
-#ifndef FNO_SPLIT2_VARIANT
-#define FNO_SPLIT2_VARIANT 0
-#endif
 // low term of the two-term split, l = fp16(v - float(h)) for both halves of a packed h: ONE v_fma_mix{lo,hi}_f16 each
 // (fma(v, 1.0, -h) with h read as fp16 straight from its half of the packed register; the difference is exact in fp32, so the
 // single rounding to fp16 is the one that v_cvt_f32_f16 / v_sub_f32 / v_cvt_f16_f32 make - 2 instructions per pair instead of
 // 4, and the split is paid per element of every GEMM operand.  tools/mix_split_test.hip: bit-identical on 2^23 values incl.
-// the fp16 denormal and overflow ranges, alone and beside another wave's MFMAs).  -DFNO_SPLIT2_MIX=0: the compiler's form.
-#ifndef FNO_SPLIT2_MIX
-#define FNO_SPLIT2_MIX 1
-#endif
+// the fp16 denormal and overflow ranges, alone and beside another wave's MFMAs).
 FNO_DEV f16x2 split2_low(f32x2 v, f16x2 h) {
-#if FNO_SPLIT2_MIX
   unsigned l;
   const unsigned hu = __builtin_bit_cast(unsigned, h);
   asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
       "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=&v"(l) : "v"(v[0]), "v"(v[1]), "v"(hu));
   return __builtin_bit_cast(f16x2, l);
-#else
-  return __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2);
-#endif
 }
 FNO_DEV void split2x8(const float (&x)[8], float s, f16x8& h, f16x8& l) {
-#if FNO_SPLIT2_VARIANT == 1
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = x[j] * s;
-    asm volatile("" : "+v"(v));
-    const _Float16 hh = (_Float16)v;
-    float r = v - (float)hh;
-    asm volatile("" : "+v"(r));
-    h[j] = hh; l[j] = (_Float16)r;
-  }
-#else
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
-#if FNO_SPLIT2_VARIANT == 0
     const f32x2 v = natural_pair(x[j], x[j + 1]) * f32x2{s, s};
     const f16x2 hh = __builtin_convertvector(v, f16x2);
     const f16x2 ll = split2_low(v, hh);
-#else
-    const f32x2 ss = {s, s};
-    f32x2 xin = {x[j + 1], x[j]}, v;
-    asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0]" : "=&v"(v) : "v"(ss), "v"(xin));
-    const f16x2 hh = __builtin_convertvector(v, f16x2);
-    const f32x2 hf = __builtin_convertvector(hh, f32x2);
-    asm volatile("v_pk_fma_f32 %0, %1, %0, %2 op_sel:[0,1,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "+v"(xin) : "v"(ss), "v"(hf));
-    const f16x2 ll = __builtin_convertvector(xin, f16x2);
-#endif
     h[j] = hh[0]; h[j + 1] = hh[1]; l[j] = ll[0]; l[j + 1] = ll[1];
   }
-#endif
 }
 // acc += A * B for one 16-deep k block; a / b = (h, l) fragments; cross terms first
 FNO_DEV void mfma_h2s(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x16& hi, f32x16& lo) {
@@ -812,9 +712,7 @@ FNO_DEV void row_dft_epilogue(const float* tile, const float* __restrict__ tfwd,
         av[j] = in ? ld4(tf + 16 * (q0 + j)) : make_float4(0.f, 0.f, 0.f, 0.f);
         bv[j] = in ? ld4(xr + 16 * (q0 + j)) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
-#ifndef FNO_DFT_NOPIPE
       __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         d0 = mfma16(av[j].x, bv[j].x, d0);

@@ -18,9 +18,7 @@
 #pragma once
 #include "fno_dev.h"
 
-#ifndef FNO_OCC_BB
-#define FNO_OCC_BB 2   // measured: 2 (no spills, 1 workgroup/CU) beats 4 (spills) on MI355X
-#endif
+static constexpr int FNO_OCC_BB = 2;   // measured: 2 (no spills, 1 workgroup/CU) beats 4 (spills) on MI355X
 
 struct BlkBwdArgs {
   const float* g;      // (B, C, PW)

@@ -16,9 +16,6 @@
 #include "fno_dev.h"
 #include "k_block_bwd.h"
 
-#ifndef FNO_BBT_LINE_ST
-#define FNO_BBT_LINE_ST 1      // k_block_bwd_t: gout in whole lines from the LDS tile (A/B arm 0: 16 bytes per channel row from registers)
-#endif
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
@@ -357,7 +354,7 @@ __global__ void __launch_bounds__((C / 32) * (NPX / 32) * 64, 2) k_block_bwd_t(B
         if (a.act_in) { v.x *= dg[i].x; v.y *= dg[i].y; v.z *= dg[i].z; v.w *= dg[i].w; }
         // (with a gout tile in LDS the tile leaves in whole lines behind the barrier, below: from this layout - lane <-> channel
         // row, 16 bytes - one store instruction touches 32 lines for 32 bytes each)
-        if (a.gout && !(FNO_BBT_LINE_ST && (a.x1g || a.xin))) st4(a.gout + ro + 8 * i, v);
+        if (a.gout && !(a.x1g || a.xin)) st4(a.gout + ro + 8 * i, v);
         if (a.gmax_out) vmax = fmaxf(fmaxf(vmax, fabsf(v.x)), fmaxf(fmaxf(fabsf(v.y), fabsf(v.z)), fabsf(v.w)));
         if (a.x1g || a.xin) st4(r3p + 8 * i, v);
       }
@@ -365,7 +362,7 @@ __global__ void __launch_bounds__((C / 32) * (NPX / 32) * 64, 2) k_block_bwd_t(B
     FNO_STAMP(tslot + 5);
     __syncthreads();          // images are free for the next commit; the gout tile is complete
     FNO_STAMP(tslot + 6);
-    if (FNO_BBT_LINE_ST && a.gout && (a.x1g || a.xin)) {      // gout: row tid / 32 + (NT / 32) i of the tile, 16-byte piece tid % 32: whole 512-byte rows
+    if (a.gout && (a.x1g || a.xin)) {      // gout: row tid / 32 + (NT / 32) i of the tile, 16-byte piece tid % 32: whole 512-byte rows
       int t_ = tid;
       asm volatile("" : "+v"(t_));         // (opaque: the offsets are derived per tile, not hoisted into registers live through the GEMMs)
       const float* r3l = r3 + (t_ >> 5) * PITCH + 4 * (t_ & 31);
@@ -636,12 +633,9 @@ __global__ void __launch_bounds__(512, 2) k_block_bwd_g2(BlkBwdArgs a) {
   f32x4 dl = {0.f, 0.f, 0.f, 0.f};                   // lifting gradients: job wg (16 channels)
   f32x4 dft0[NJP], dft1[NJP];                         // W = 128: row-DFT accumulators of jobs wg (, wg + 4), carried over the halves
 
-#ifndef FNO_G2_STAGGER
-#define FNO_G2_STAGGER 55
-#endif
   // identical programs started together stay in lockstep (both groups in their VALU phase, then both on the matrix pipe);
   // starting group 1 about half a period late puts its commits beside group 0's GEMMs
-  if (FNO_G2_STAGGER > 0 && grp == 1) __builtin_amdgcn_s_sleep(FNO_G2_STAGGER);
+  if (grp == 1) __builtin_amdgcn_s_sleep(55);
 
   int par = 0;
   FNO_TRACE_IF(FNO_TRACE_WHICH == 2 && a.x1g != nullptr);
@@ -733,12 +727,9 @@ __global__ void __launch_bounds__(512, 2) k_block_bwd_g2(BlkBwdArgs a) {
       FNO_STAMP(tslot + 1);
       group_barrier(bar, epoch, lane);
       FNO_STAMP(tslot + 2);
-#ifndef FNO_G2_PRIO
-#define FNO_G2_PRIO 1
-#endif
       // the matrix-pipe phase gets issue priority over the other group's VALU phase on this SIMD: its MFMAs and LDS reads are
       // latency-bound, the VALU stream fills the gaps (tools/simd_share_test.hip: VALU beside bf16 MFMA runs at 87 %)
-      if (FNO_G2_PRIO) __builtin_amdgcn_s_setprio(2);
+      __builtin_amdgcn_s_setprio(2);
       // ---- dW[o][i] += sum_px g[o][px] a[i][px]: wave wg owns one 32 x 32 tile over the 64 pixels of the half -------------
       {
         const int ro = mt * 32 + l31, ri = nt * 32 + l31;
@@ -810,7 +801,7 @@ __global__ void __launch_bounds__(512, 2) k_block_bwd_g2(BlkBwdArgs a) {
             if (s0 + j < a.K2in) acc = mfma32(tq4[j], zq[j], acc);
         }
       }
-      if (FNO_G2_PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       FNO_STAMP(tslot + 4);
       // the next half's operands: issued behind the GEMMs (32 registers that must not be live beside the weight fragments and
       // the accumulators); their latency is covered by the epilogue, the row DFT and the other group's work on this SIMD
@@ -864,9 +855,7 @@ __global__ void __launch_bounds__(512, 2) k_block_bwd_g2(BlkBwdArgs a) {
               float4 av[4], bv[4];        // all four k steps' operands in flight before the first MFMA (fno_dev.h: row_dft_epilogue)
 #pragma unroll
               for (int q = 0; q < 4; ++q) { av[q] = ld4(tf + 16 * q); bv[q] = ld4(xr + 16 * q); }
-#ifndef FNO_DFT_NOPIPE
               __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
                 dft0[jj] = mfma16(av[q].x, bv[q].x, dft0[jj]);

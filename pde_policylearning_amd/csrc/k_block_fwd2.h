@@ -232,11 +232,6 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
   // nothing, and on gfx950 that lost 5 % of the outputs when the next float4 was formed in the same registers.
   const int st_voff = (l31 * a.PW + 4 * half + ng * NTW * 32) * 4;
 
-#ifdef FNO_ELIM      // phase elimination (tools/bf2_test.hip -DFNO_ELIM, timing only: results are wrong): bits of a.loose switch phases off
-  const int elim = a.loose;
-#else
-  constexpr int elim = 0;
-#endif
   int tslot = 0;
   float vmax = 0.f;          // max |u| stored by this thread (a.umax)
   FNO_TRACE_IF(true);
@@ -262,7 +257,7 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = pv[i][j];
-        if constexpr (ACT_IN) { if (!(elim & 2)) gelu8(v, six, inf); }
+        if constexpr (ACT_IN) gelu8(v, six, inf);
       }
       bf16x8 f[NT3];
       split_n_x8<NT3>(v, sx, f);
@@ -399,15 +394,8 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
         for (int r = 0; r < 16; ++r) acc[q][r] = hi[r] + lo[r];
       };
       static_assert(NTW == 2, "two 32-pixel column tiles per wave");
-      if (!(elim & 1)) {
-        qtile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-        qtile(std::integral_constant<int, 1>{}, std::integral_constant<int, (KB + KZ) % 2>{});      // q = 0 left its successor's first fragment there
-      } else {
-#pragma unroll
-        for (int q = 0; q < NTW; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[q][r] = (float)fa[0][0][r & 3];
-      }
+      qtile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+      qtile(std::integral_constant<int, 1>{}, std::integral_constant<int, (KB + KZ) % 2>{});      // q = 0 left its successor's first fragment there
     }
     // the next tile's loads go out behind the GEMM (their 32 registers must not be live beside the weight fragments, the
     // accumulators and the fragment double buffer); epilogue, row DFT and the other workgroup's phases cover their latency
@@ -454,10 +442,10 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
           if constexpr (RELU) {      // (NaN stays NaN, as torch's relu)
             v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w;
           }
-          if (a.u && !(elim & 16)) buf_st4(ru, st_voff + (q * 32 + 8 * g) * 4, 0, v);
+          if (a.u) buf_st4(ru, st_voff + (q * 32 + 8 * g) * 4, 0, v);
           if (a.umax) vmax = fmaxf(fmaxf(vmax, fabsf(v.x)), fmaxf(fmaxf(fabsf(v.y), fabsf(v.z)), fabsf(v.w)));
           if constexpr (EPI != 0) {
-            if constexpr (EPI == 2) { if (!(elim & 4)) v = gelu4(v, six, inf); }
+            if constexpr (EPI == 2) v = gelu4(v, six, inf);
             st4(xp + 8 * g, v);
           }
         }
@@ -468,7 +456,7 @@ __global__ void __launch_bounds__((C / 32) * 2 * 64, 2) k_blk_fwd_t(PwFwdArgs a)
     if constexpr (EPI != 0) {
       __syncthreads();
       FNO_STAMP(tslot + 6);
-      if (!(elim & 8)) row_dft_epilogue<C, NPX, NW>(xs, tfwd_s, a.W + 4, a.x1, b, px0, a.P, a.W, a.K2out, a.NJ, wave, lane);
+      row_dft_epilogue<C, NPX, NW>(xs, tfwd_s, a.W + 4, a.x1, b, px0, a.P, a.W, a.K2out, a.NJ, wave, lane);
       FNO_STAMP(tslot + 7);
       __syncthreads();      // the next commit rewrites the images under the tile
     }

@@ -27,19 +27,11 @@
 // 16 bytes per lane HBM -> LDS without a register destination: LDS address = lds_dst (wave-uniform, bytes) + 16 * lane,
 // source = sbase (wave-uniform) + voff (per lane, bytes).  M0 carries the LDS base and is compiler-reserved: saved and
 // restored inside the statement (cdna_hip_programming.md, inline-asm rules).  Not counted by the compiler's s_waitcnt
-// bookkeeping: the caller waits with a counted s_waitcnt vmcnt.
-#ifndef FNO_BFS_NT
-#define FNO_BFS_NT FNO_NT_LOADS // the strip loads are non-temporal (fno_dev.h: streaming loads)
-#endif
+// bookkeeping: the caller waits with a counted s_waitcnt vmcnt.  The strip loads are non-temporal (fno_dev.h: streaming loads).
 FNO_DEV void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
   unsigned keep;
-#if FNO_BFS_NT
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#else
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-#endif
 }
 FNO_DEV unsigned lds_addr(const void* p) {
   return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
@@ -57,16 +49,7 @@ static inline size_t blk_fwd_s_lds_bytes(int K2out, bool has_x1) {
 }
 
 // u stores per strip and wave (16-byte buffer stores, 4 per 32-channel half) - the count behind the counted vmcnt below
-#define FNO_BFS_NST 8
-#ifndef FNO_BFS_FORCE_TR
-#define FNO_BFS_FORCE_TR 0      // (A/B arm: transposed accumulators and 16-byte stores also without a row-DFT epilogue)
-#endif
-#ifndef FNO_BFS_STAGE
-#define FNO_BFS_STAGE 1         // (A/B arm 0: transposed accumulators stored as they stand)
-#endif
-#ifndef FNO_BFS_EXP
-#define FNO_BFS_EXP 0           // timing experiments of tools/bf3_test.hip (results are wrong): 1 = no u stores, 2 = no strip loads
-#endif
+static constexpr int FNO_BFS_NST = 8;
 
 // LIFT: block 0 of a model with a lifting layer: the strip is u_0 = W_l x + b_l of the <= 4-channel model input (tfno.py:11-20),
 // computed where the other variants read their slot (no DMA: four dword loads per lane and strip, one strip ahead)
@@ -109,7 +92,7 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
     } else {
       const float* src = strip_src(tile);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) if (!(FNO_BFS_EXP & 2)) glds16(src + (size_t)i * 8 * a.PW, dma_voff, slot_a + i * 1024);
+      for (int i = 0; i < 8; ++i) glds16(src + (size_t)i * 8 * a.PW, dma_voff, slot_a + i * 1024);
     }
   };
   // spectral coefficients of the strip's row for channel o = mt * 32 + l31: k = 8 half + j <-> mode 4 half + (j >> 1), re / im
@@ -208,7 +191,7 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
   // With a row-DFT epilogue the accumulators are TRANSPOSED (D^T[px][o]: lane <-> channel, registers <-> 4-pixel runs: they are
   // the DFT's matrix operand as they stand, one bias register per half, 16-byte stores).  Without one the plain orientation
   // (D[o][px]: lane <-> pixel, registers <-> channels) leaves as whole 128-byte lines per wave half and dword store.
-  constexpr bool TR = EPI != 0 || FNO_BFS_FORCE_TR;
+  constexpr bool TR = EPI != 0;
   float bias_o[2];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt) bias_o[mt] = a.bias ? a.bias[mt * 32 + l31] : 0.f;
@@ -221,7 +204,6 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
   }
   __syncthreads();
 
-  const int st_voff = (l31 * a.PW + 4 * half) * 4;           // output row l31 of the 32-channel half, pixels 4 half .. (+ 8 g)
   int st_line[4];                                            // whole-line stores: row 8 i + lane / 8, 16-byte chunk lane % 8
 #pragma unroll
   for (int i = 0; i < 4; ++i) st_line[i] = ((8 * i + (lane >> 3)) * a.PW + 4 * (lane & 7)) * 4;
@@ -234,7 +216,7 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
     // ---- the strip has landed: behind its DMA this wave issued only the previous strip's stores (and nothing the first time) ------
     if constexpr (!LIFT) {
       if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" :: "n"((FNO_BFS_EXP & 1) ? 0 : (TR ? FNO_BFS_NST : 32)) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(TR ? FNO_BFS_NST : 32) : "memory");
     }
     first = false;
     float raw[KB][8];
@@ -322,15 +304,7 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
     for (int mt = 0; mt < 2; ++mt) {
       const size_t obase = ((size_t)b * C + mt * 32) * a.PW + px0 + w0;
       const __amdgpu_buffer_rsrc_t ru = make_rsrc(a.u + obase, 31u * PWb + 32 * 4);
-      if constexpr (TR && !FNO_BFS_STAGE) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 v = make_float4(acc[mt][4 * g], acc[mt][4 * g + 1], acc[mt][4 * g + 2], acc[mt][4 * g + 3]);
-          if (!(FNO_BFS_EXP & 1))
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4{v.x, v.y, v.z, v.w}), ru, st_voff + 8 * g * 4, 0, 0);
-          if (a.umax) vmax = fmaxf(fmaxf(vmax, fabsf(v.x)), fmaxf(fmaxf(fabsf(v.y), fabsf(v.z)), fabsf(v.w)));
-        }
-      } else if constexpr (TR) {
+      if constexpr (TR) {
         // A transposed accumulator register holds 32 bytes of each of 32 channel rows: stored as it stands, one instruction
         // touches 32 lines (measured: 136 vs 111 us per launch against whole-line stores).  So the 32 x 32 tile takes a turn
         // through the wave's own 4 KB of LDS - rows of 128 bytes, 16-byte chunks XOR-swizzled by the row, no conflicts either
@@ -346,8 +320,7 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
         for (int i = 0; i < 4; ++i) {
           const int row = 8 * i + (lane >> 3);
           const float4 v = ld4(reinterpret_cast<const float*>(sg_ + row * 128 + (((lane & 7) ^ (row & 7)) * 16)));
-          if (!(FNO_BFS_EXP & 1))
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4{v.x, v.y, v.z, v.w}), ru, st_line[i], 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4{v.x, v.y, v.z, v.w}), ru, st_line[i], 0, 0);
         }
       } else {
         // acc[r] = channel mt * 32 + 4 half + (r & 3) + 8 (r >> 2), pixel l31: the row offset rides in the scalar offset
@@ -355,12 +328,10 @@ __global__ void __launch_bounds__(256, 2) k_blk_fwd_s(PwFwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float v = acc[mt][r];
-          if (!(FNO_BFS_EXP & 1))
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ru, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * PWb, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ru, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * PWb, 0);
           if (a.umax) vmax = fmaxf(vmax, fabsf(v));
         }
       }
-      if (FNO_BFS_EXP & 1) asm volatile("" :: "v"(acc[mt]));
     }
     if constexpr (EPI != 0) {
       // g = act_out(u) in place; the wave's own maximum scales the two-term split (exact power of two, undone on the result)

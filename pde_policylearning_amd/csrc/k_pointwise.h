@@ -24,12 +24,8 @@
 #pragma once
 #include "fno_dev.h"
 
-#ifndef FNO_OCC_PW
-#define FNO_OCC_PW 4   // lifting / no-GEMM variants (CIN <= 4) ask for 6 waves per SIMD: 3 workgroups per CU fit their 42 KB of LDS
-#endif
-#ifndef FNO_OCC_PWX
-#define FNO_OCC_PWX 2   // measured: 1 workgroup/CU without spills (0.175 ms) beats 2 with spills (0.27 ms)
-#endif
+static constexpr int FNO_OCC_PW = 4;    // lifting / no-GEMM variants (CIN <= 4) ask for 6 waves per SIMD: 3 workgroups per CU fit their 42 KB of LDS
+static constexpr int FNO_OCC_PWX = 2;   // measured: 1 workgroup/CU without spills (0.175 ms) beats 2 with spills (0.27 ms)
 
 struct PwFwdArgs {
   const float* x;     // (B, CIN, PW) pre-activation input, or null (no conv part)

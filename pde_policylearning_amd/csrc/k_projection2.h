@@ -145,9 +145,6 @@ static inline size_t proj_bwd_t_lds_bytes(int C, const ProjBwdArgs& a) {
   const size_t nt = a.amax ? 2 : 3;
   return nt * C * 256 + 2 * nt * 64 * 256 + 128 * 4 + (a.x1g ? (size_t)16 * a.NJ * (a.W + 4) * 4 : 0);
 }
-#ifndef FNO_PB_SDFOLD
-#define FNO_PB_SDFOLD 1      // 0: the split multiplies by the fp16 scale itself (A/B arm)
-#endif
 template <int C, int HID, bool RELU = false, int NT3 = 3>
 __global__ void __launch_bounds__(512, 2) k_proj_bwd_t(ProjBwdArgs a) {
   FNO_CLK_ENTRY();
@@ -229,25 +226,17 @@ __global__ void __launch_bounds__(512, 2) k_proj_bwd_t(ProjBwdArgs a) {
     const int b = tile / a.tiles_per_plane;
     const int px0 = (tile % a.tiles_per_plane) * NPX;
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.x + (size_t)b * C * a.PW, (unsigned)(C * a.PW * 4));
-#ifdef PBT_GLOBAL_X
-#pragma unroll
-    for (int i = 0; i < XI; ++i) xq[i] = ld4(a.x + ((size_t)b * C + (tid >> 5) + 16 * i) * a.PW + px0 + 4 * (tid & 31));
-#else
 #pragma unroll
     for (int i = 0; i < XI; ++i) xq[i] = buf_ld4s(rs, xvoff, (16 * i * a.PW + px0) * 4);
-#endif
   };
   if ((int)blockIdx.x < a.ntiles) issue_x(blockIdx.x);
   if (a.x1g)
     for (int i = tid; i < 16 * a.NJ * a.W; i += NT) tfwd_s[(i / a.W) * (a.W + 4) + i % a.W] = a.tfwd[i];
   load_wa1(0);
 
-#ifndef PBT_BASE_PRIO
-#define PBT_BASE_PRIO 1
-#endif
   // static priority for the later-dispatched half (MI355X_MICROARCH.md, two waves per SIMD, item 4): waves 4-7 lose every
   // VALU arbitration to their older partners otherwise (GELU phase 4 k vs 1.9 k cycles in the phase trace)
-  const int base_prio = (PBT_BASE_PRIO && wave >= 4) ? 1 : 0;
+  const int base_prio = wave >= 4 ? 1 : 0;
   if (base_prio) __builtin_amdgcn_s_setprio(1);
   int tslot = 0;
   FNO_TRACE_IF(FNO_TRACE_WHICH == 1);
@@ -312,7 +301,7 @@ __global__ void __launch_bounds__(512, 2) k_proj_bwd_t(ProjBwdArgs a) {
         const int hrow = hm * 32 + l31;
         // w2 carries the fp16 scale of dP1 (a power of two: every product below is the unscaled one times sd, bit for bit),
         // so the split needs no multiply of its own; the bias-gradient sum is unscaled once per chunk
-        const float w2s = FNO_PB_SDFOLD ? w2v * sd : w2v;
+        const float w2s = w2v * sd;
         const f32x2 b1p = {b1v, b1v}, w2p = {w2s, w2s};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -334,11 +323,11 @@ __global__ void __launch_bounds__(512, 2) k_proj_bwd_t(ProjBwdArgs a) {
             sdw = __builtin_elementwise_fma(gv[h2], dyp[h2], sdw);
             sdb = sdb + dpp[h2];
           }
-          put_split4_n<NT3>(dr, DTERM, swz_off(hrow, (n0 >> 3) + i) + 8 * half, make_float4(dpp[0][0], dpp[0][1], dpp[1][0], dpp[1][1]), FNO_PB_SDFOLD ? 1.f : sd);
+          put_split4_n<NT3>(dr, DTERM, swz_off(hrow, (n0 >> 3) + i) + 8 * half, make_float4(dpp[0][0], dpp[0][1], dpp[1][0], dpp[1][1]), 1.f);
         }
 #pragma unroll
         for (int k = 0; k < NCH; ++k)
-          if (k == ch) { sdb1[k] += (sdb[0] + sdb[1]) * (FNO_PB_SDFOLD ? inv_sd : 1.f); sdw2[k] += sdw[0] + sdw[1]; }
+          if (k == ch) { sdb1[k] += (sdb[0] + sdb[1]) * inv_sd; sdw2[k] += sdw[0] + sdw[1]; }
       }
       if (ch == 1) FNO_STAMP(tslot + 5);
       __syncthreads();         // dr[ch & 1] is complete; every reader of dr[(ch + 1) & 1] (chunk ch - 1) is done

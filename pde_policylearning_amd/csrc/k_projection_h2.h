@@ -77,9 +77,6 @@ FNO_DEV float wg_absmax(const float* __restrict__ w, int n, float* scratch, int 
 //     accumulator values of a lane; the waves of a SIMD drift apart on their own, so one wave's matrix burst runs under the
 //     others' vector work.
 // Same arithmetic as k_proj_fwd_h2 (bitwise: same products, same order); reference semantics neuralop/models/tfno.py:23-38.
-#ifdef PFW_TRACE
-__device__ unsigned long long g_pfw_trace[64 * 16 * 4];
-#endif
 // Two 12-wave workgroups per CU (six waves per SIMD, <= 80 VGPRs), static shares of the columns.  Measured on the way
 // (profiles/r04_proj_fwd_w_workgroup_times.txt, tools/kernel_clock.py): the workgroup that arrives second on a CU loses the
 // vector-issue arbitration to the older one (median 83 us vs 137 us for workgroups [0, 256) / [256, 512) of one launch, both
@@ -97,9 +94,6 @@ __device__ unsigned long long g_pfw_trace[64 * 16 * 4];
 // (three or two of a chunk's four groups of hidden values scalar, the rest packed) is slower than all-scalar: 0.1678 / 0.1690
 // against 0.1646 ms on one box - every packed instruction holds the matrix pipe off.  Issue priorities (none, or raised
 // around the products instead of alternating per column): 0.1654 / 0.1674 against 0.1650.
-#ifndef FNO_PFW_SCALAR_ACT
-#define FNO_PFW_SCALAR_ACT 2      // 0 = packed forms (A/B arm), 1 = scalar hidden activation, 2 = + scalar input activation and split
-#endif
 template <int C, int HID, int NWAVE>
 __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArgs a) {
   FNO_CLK_ENTRY();
@@ -117,9 +111,6 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
   const int l31 = lane & 31, half = lane >> 5;
   FNO_CLK_BEGIN();
 
-#ifdef PFW_TRACE
-  const unsigned long long tr_k0 = __builtin_readcyclecounter();
-#endif
   // ONE pass over W1: a thread fetches its fragment items (hidden 32-block, k block, lane: eight consecutive channels of one
   // row), the workgroup maximum of |W1| comes from the same registers (the items cover W1 exactly once), then they are split.
   // (Was a scan followed by a second, dependent read of the same 64 KB: 21 k cycles of prologue per workgroup.)
@@ -147,9 +138,6 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
 #pragma unroll
   for (int k = 0; k < NWAVE; ++k) mw = fmaxf(mw, scratch[k]);
   const float sx = h2_scale(bxv), sw = h2_scale(mw);
-#ifdef PFW_TRACE
-  const unsigned long long tr_k1 = __builtin_readcyclecounter();
-#endif
   const float inv = 1.0f / (sx * sw);
 #pragma unroll
   for (int q = 0; q < NIT; ++q) {
@@ -167,13 +155,6 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
 
   const int cols_per_plane = a.PW / 32, ncols = a.ntiles * 4;
   const unsigned PWb = (unsigned)a.PW * 4u;
-#ifdef PFW_TRACE      // diagnostic build: where a wave's cycles go (stamps cost an s_waitcnt lgkmcnt(0) each)
-  unsigned long long tr_load = 0, tr_mfma = 0, tr_valu = 0, tr_cols = 0, tr_t = __builtin_readcyclecounter(), tr_n;
-  const unsigned long long tr_k2 = tr_t;
-#define PFW_STAMP(acc) do { tr_n = __builtin_readcyclecounter(); acc += tr_n - tr_t; tr_t = tr_n; } while (0)
-#else
-#define PFW_STAMP(acc) do { } while (0)
-#endif
   const int voff = (8 * half * a.PW + l31) * 4;
   // A workgroup owns a static share of the columns (pair_share: the one dispatched first on its CU the larger one) and its
   // waves POP them from a counter in LDS: the waves of a SIMD are served oldest first, so with one static share per wave the
@@ -200,7 +181,7 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = buf_ld1(rx, voff, (unsigned)(16 * kb + j) * PWb);      // (default policy: the projection backward re-reads u_L, last part first)
-#if FNO_PFW_SCALAR_ACT >= 2      // the column's own activation and split with scalar instructions too
+      // the column's own activation and split with scalar instructions too
       if (a.act_in) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = gelu_s(v[j], gk_six, gk_inf);
@@ -211,15 +192,7 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
         const _Float16 hh = (_Float16)sv;
         bfrag[kb][0][j] = hh; bfrag[kb][1][j] = (_Float16)(sv - (float)hh);
       }
-#else
-      if (a.act_in) gelu8(v, gk_six, gk_inf);
-      split2x8(v, sx, bfrag[kb][0], bfrag[kb][1]);
-#endif
     }
-#ifdef PFW_TRACE
-    asm volatile("" :: "v"(bfrag[KB - 1][1]));
-#endif
-    PFW_STAMP(tr_load);
     float ysum = 0.f;
 #pragma unroll 1
     for (int ch = 0; ch < NCHK; ++ch) {
@@ -234,14 +207,9 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
         for (int t = 0; t < 2; ++t) af[t] = *reinterpret_cast<const f16x8*>(wa + (size_t)(kb * 2 + t) * 64 * 8);
         mfma_h2s(af, bfrag[kb], acc, lo);
       }
-#ifdef PFW_TRACE
-      asm volatile("s_nop 11" :: "v"(acc), "v"(lo));
-#endif
-      PFW_STAMP(tr_mfma);
       // D[row = hidden 32 ch + (r & 3) + 8 (r >> 2) + 4 half][col = pixel l31]
       const float* b1p = b1s + ch * 32 + 4 * half;
       const float* w2p = w2s + ch * 32 + 4 * half;
-#if FNO_PFW_SCALAR_ACT
 #pragma unroll
       for (int q = 0; q < 4; ++q) {            // four values at a time (the scalar form's temporaries: 80 registers per wave)
         float hv[4];
@@ -256,43 +224,11 @@ __global__ void __launch_bounds__(NWAVE * 64, NWAVE / 2) k_proj_fwd_w(ProjFwdArg
           ysum = fmaf(w2p[(r & 3) + 8 * (r >> 2)], hv[k], ysum);
         }
       }
-#else
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {            // eight values at a time: half the live temporaries of the packed GELU
-        f32x2 hp[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int r = 8 * q + 2 * k;
-          hp[k][0] = fmaf(acc[r] + lo[r], inv, b1p[(r & 3) + 8 * (r >> 2)]);
-          hp[k][1] = fmaf(acc[r + 1] + lo[r + 1], inv, b1p[((r + 1) & 3) + 8 * ((r + 1) >> 2)]);
-        }
-        gelu_pairs<4>(hp, gk_six, gk_inf);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int r = 8 * q + 2 * k;
-          ysum = fmaf(w2p[(r & 3) + 8 * (r >> 2)], hp[k][0], ysum);
-          ysum = fmaf(w2p[((r + 1) & 3) + 8 * ((r + 1) >> 2)], hp[k][1], ysum);
-        }
-      }
-#endif
-#ifdef PFW_TRACE
-      asm volatile("" :: "v"(ysum));
-#endif
-      PFW_STAMP(tr_valu);
     }
     ysum += __shfl_xor(ysum, 32, 64);
     if (half == 0) a.y[(size_t)b * a.PW + px0 + l31] = ysum + a.b2[0];      // (a scalar load per column: held in a register across the
                                                                               // column loop it was the kernel's one spill)
-#ifdef PFW_TRACE
-    ++tr_cols;
-#endif
   }
   FNO_CLK_END(2);
-#ifdef PFW_TRACE
-  if (lane == 0 && blockIdx.x < 64) {
-    unsigned long long* q = g_pfw_trace + (blockIdx.x * NWAVE + wave) * 4;
-    q[0] = tr_load; q[1] = tr_mfma; q[2] = tr_valu; q[3] = tr_cols | ((tr_k1 - tr_k0) << 16) | ((tr_k2 - tr_k1) << 40);
-  }
-#endif
 }
 static inline size_t proj_fwd_w_lds(int C, int HID) { return (size_t)(HID / 32) * (C / 16) * 2 * 64 * 16 + (size_t)(2 * HID + 16 + 4) * 4; }

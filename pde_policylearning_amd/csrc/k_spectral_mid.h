@@ -1182,13 +1182,6 @@ __global__ void __launch_bounds__(256) k_channel_sums(const float* __restrict__ 
 // wait for HBM (50 MB in ~9 us), the contraction for L2 (151 MB of weight rows in ~6 us = 25 TB/s); none of them for the
 // vector unit.  The scalar form stays.
 //   block (64, 8), grid (inner / 64, samples), LDS (8 + 2) * NK * 64 float2
-#ifndef FNO_MID_SMEM_TABLE
-#define FNO_MID_SMEM_TABLE 1      // 1 = DFT table rows through scalar loads (round 5; up to 12 kept modes: 16 need more scalar
-                                  // registers than a wave has); 0 = staged in LDS, broadcast reads (A/B arm)
-#endif
-#ifndef FNO_MID_SKIP
-#define FNO_MID_SKIP 0        // timing experiments: 1 = no contraction, 2 = no phase 1 loads, 4 = no phase 3
-#endif
 #ifdef FNO_TRACE
 #define MID_STAMP(slot) do { if (blockIdx.x == 2 && blockIdx.y == gridDim.y / 2 && threadIdx.x == 0) \
     g_trace[threadIdx.y * 256 + (slot)] = __builtin_readcyclecounter(); \
@@ -1220,7 +1213,9 @@ __global__ void __launch_bounds__(512, 4) k_spec_mid(const float2* __restrict__ 
                                                      const float2* __restrict__ twT, const float2* __restrict__ twi, int n,
                                                      int inner, int K2, int conj_w, int Bm, size_t w_ms) {
   static_assert(C == 32 || C == 64, "whole bins per workgroup");
-  constexpr bool SREG = FNO_MID_SMEM_TABLE && NK <= 12;      // table rows in scalar registers
+  // DFT table rows through scalar loads (round 5) up to 12 kept modes: 16 need more scalar registers than a wave has and take
+  // the rows staged in LDS with broadcast reads
+  constexpr bool SREG = NK <= 12;
   constexpr int SEGS = 8, JW = C / SEGS, NTH = 64 * SEGS;
   constexpr int RB = 2, NG = NK / RB;               // RB modes' weight rows per load group, double-buffered
   static_assert(NK % RB == 0, "mode groups");
@@ -1251,7 +1246,7 @@ __global__ void __launch_bounds__(512, 4) k_spec_mid(const float2* __restrict__ 
 #pragma unroll
       for (int j = 0; j < JW; ++j) wv[buf][rr][j] = wb[((size_t)(g * RB + rr) * K2 * C + j) * C];
   };
-  if (!(FNO_MID_SKIP & 1)) load_w(0, 0);
+  load_w(0, 0);
   // ---- phase 1 ----
   {
     f32x2 acc[NK];
@@ -1266,7 +1261,7 @@ __global__ void __launch_bounds__(512, 4) k_spec_mid(const float2* __restrict__ 
 #pragma unroll
       for (int j = 0; j < NBR; ++j) {
         const int nn = nb + SEGS * j;
-        v[j] = (nn < n && !(FNO_MID_SKIP & 2)) ? src[(size_t)nn * inner] : make_float2(0.f, 0.f);
+        v[j] = nn < n ? src[(size_t)nn * inner] : make_float2(0.f, 0.f);
       }
       if constexpr (SREG) {
       (void)first;
@@ -1325,7 +1320,6 @@ __global__ void __launch_bounds__(512, 4) k_spec_mid(const float2* __restrict__ 
   __syncthreads();
   MID_STAMP(3);
   // ---- phase 2 ----
-  if (!(FNO_MID_SKIP & 1))
   {
     const float sg = conj_w ? -1.f : 1.f;
 #pragma unroll
@@ -1362,7 +1356,6 @@ __global__ void __launch_bounds__(512, 4) k_spec_mid(const float2* __restrict__ 
   }
   MID_STAMP(6);
   // ---- phase 3 ----
-  if (!(FNO_MID_SKIP & 4))
   {
     f32x2 v[NK], vs[NK];
 #pragma unroll

@@ -90,20 +90,11 @@ __global__ void k_adam_prep(int* step, float* dyn, double lr, double beta1, doub
   dyn[0] = (float)(lr / bc1);
   dyn[1] = (float)sqrt(bc2);
 }
-#ifndef FNO_ADAM_NT
-#define FNO_ADAM_NT 1      // 1 = nontemporal stores of p / m / v (nothing re-reads them before the next step: 1.34 -> 1.21 ms for the
-                           // full-field observer's 906 MB bucket, and the step's later kernels keep their cache lines); 0 = plain stores;
-                           // 2 = + nontemporal gradient loads (measured slower: 1.30 ms)
-#endif
-#ifndef FNO_ADAM_UNROLL
-#define FNO_ADAM_UNROLL 1
-#endif
+// p / m / v leave through nontemporal stores (nothing re-reads them before the next step: 1.34 -> 1.21 ms for the full-field
+// observer's 906 MB bucket, and the step's later kernels keep their cache lines; nontemporal gradient loads on top measured
+// slower: 1.30 ms)
 FNO_DEV void adam4(const AdamArgs& a, size_t i) {
-  float4 p = ld4(a.p + 4 * i), m = ld4(a.m + 4 * i), v = ld4(a.v + 4 * i), g;
-  if (FNO_ADAM_NT >= 2) {
-    g.x = __builtin_nontemporal_load(a.g + 4 * i); g.y = __builtin_nontemporal_load(a.g + 4 * i + 1);
-    g.z = __builtin_nontemporal_load(a.g + 4 * i + 2); g.w = __builtin_nontemporal_load(a.g + 4 * i + 3);
-  } else g = ld4(a.g + 4 * i);
+  float4 p = ld4(a.p + 4 * i), m = ld4(a.m + 4 * i), v = ld4(a.v + 4 * i), g = ld4(a.g + 4 * i);
   float* pp = &p.x; float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -113,23 +104,16 @@ FNO_DEV void adam4(const AdamArgs& a, size_t i) {
     const float denom = sqrtf(vp[j]) / a.bc2_sqrt + a.eps;
     pp[j] = fmaf(-a.step_size, mp[j] / denom, pp[j]);
   }
-  if (FNO_ADAM_NT >= 1) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{p.x, p.y, p.z, p.w}, reinterpret_cast<f4*>(a.p + 4 * i));
-    __builtin_nontemporal_store(f4{m.x, m.y, m.z, m.w}, reinterpret_cast<f4*>(a.m + 4 * i));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(a.v + 4 * i));
-  } else {
-    st4(a.p + 4 * i, p); st4(a.m + 4 * i, m); st4(a.v + 4 * i, v);
-  }
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  __builtin_nontemporal_store(f4{p.x, p.y, p.z, p.w}, reinterpret_cast<f4*>(a.p + 4 * i));
+  __builtin_nontemporal_store(f4{m.x, m.y, m.z, m.w}, reinterpret_cast<f4*>(a.m + 4 * i));
+  __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(a.v + 4 * i));
 }
 __global__ void __launch_bounds__(256) k_adam(AdamArgs a) {
   if (a.dyn) { a.step_size = a.dyn[0]; a.bc2_sqrt = a.dyn[1]; }
   const size_t n4 = a.n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (FNO_ADAM_UNROLL == 2) {
-    for (; i + stride < n4; i += 2 * stride) { adam4(a, i); adam4(a, i + stride); }
-  }
   for (; i < n4; i += stride) adam4(a, i);
   if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {
     const size_t i = n4 * 4 + threadIdx.x;

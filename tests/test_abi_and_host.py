@@ -533,6 +533,31 @@ def test_no_packed_fp32_op_sel_hazard_in_any_kernel():
     assert not bad, f"packed-fp32 op_sel hazard forms: {bad}"
 
 
+def test_compile_time_switches_of_the_kernel_sources_are_the_declared_set():
+    """The kernel sources carry no A/B arms: the only identifiers their preprocessor conditionals test are the two
+    instrumentation facilities (no-ops in the product build).  A new compile-time switch has to be declared here and in
+    tools/README.md ("Compile-time switches"), where the next reader looks; the build's -Werror=undef keeps a conditional from
+    silently testing a name that nothing defines."""
+    kept = {"FNO_TRACE", "FNO_TRACE_WHICH", "FNO_TRACE_SEL", "FNO_CLOCK"}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "pde_policylearning_amd", "csrc")
+    seen = {}
+    for fn in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, fn)).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b(.*)$", text, re.M):
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            for name in re.findall(r"[A-Za-z_]\w*", cond):
+                if name != "defined":
+                    seen.setdefault(name, set()).add(fn)
+    assert len(seen) >= 1 and "FNO_TRACE" in seen, "the scan found no conditional at all"
+    assert set(seen) == kept, {k: sorted(v) for k, v in seen.items() if k not in kept} or sorted(kept - set(seen))
+    readme = open(os.path.join(root, "tools", "README.md")).read()
+    section = readme.split("## Compile-time switches", 1)[1].split("\n## ", 1)[0]
+    assert set(re.findall(r"`-D(\w+)`", section.split("Retired", 1)[0])) == kept
+    from pde_policylearning_amd import build as B
+    assert "-Werror=undef" in open(B.__file__).read()
+
+
 def test_reference_yamls_become_the_run_plan(tmp_path):
     """`train_observer --train_yaml configs/base_fno.yaml` (BASELINE.json north_star; reference: libs/arguments.py:10-39 merge,
     run_pde_observers.py:336-346): the YAML's keys win over the flags, a key given twice keeps its last value, --set_epoch /

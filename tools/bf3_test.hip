@@ -38,7 +38,6 @@ static void run(int B, int W, int K2, int reps) {
   CK(hipMemset(u0, 0, nact * 4)); CK(hipMemset(u1, 0, nact * 4)); CK(hipMemset(x10, 0, nx1 * 4)); CK(hipMemset(x11, 0, nx1 * 4));
   a.PW = PW; a.W = W; a.P = P; a.K2in = K2; a.K2out = K2; a.NJ = NJ; a.act_in = AIN; a.act_out = EPI == 2;
   a.tiles_per_plane = PW / 128; a.ntiles = B * a.tiles_per_plane;
-  a.loose = getenv("STAG") ? atoi(getenv("STAG")) : 0;
   { float mx = 0.f; for (auto v : x) mx = std::max(mx, std::fabs(v)); std::vector<float> m1(4, mx); a.xmax = dev(m1); std::vector<float> z4(4, 0.f); a.umax = dev(z4); a.ubound = a.umax + 2; }
   if (LIFT) { a.lw = dev(lw); a.lb = dev(lb); a.CL = CL; }
   hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
