@@ -135,6 +135,12 @@ def lib():
     L.fno_pointwise_backward.argtypes = [ci, ci, sz, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp]
     L.fno_debug_pino_twopass.argtypes = [ci]
     L.fno_debug_pino_twopass.restype = None
+    up = C.POINTER(C.c_uint)
+    L.fno_debug_launch_log.argtypes = [ci]
+    L.fno_debug_launch_log.restype = None
+    L.fno_debug_launch_count.restype = ci
+    L.fno_debug_launch_get.argtypes = [ci, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(ci), C.POINTER(ci), up, up,
+                                       C.POINTER(sz)]
     L.fno_projection_workspace_bytes.argtypes = [ci, ci]
     L.fno_projection_workspace_bytes.restype = sz
     L.fno_projection_forward.argtypes = [ci, ci, ci, ci, sz] + [vp] * 7
@@ -241,3 +247,29 @@ def profile_summary(with_terms=False):
         rec = (name.value.decode(), float(ms.value), int(n.value))
         out.append(rec + (int(L.fno_profile_get_terms(i)),) if with_terms else rec)
     return out
+
+
+class launch_log(object):
+    """`with launch_log() as log:` records every kernel launch of the library inside the block (fno_debug_launch_log: made by
+    the launching statement itself, off by default); afterwards `log.records` is a list of dicts
+    {"name": profile label, "variant": the dispatch site's tag (kernel and template arguments, "" where it states none),
+     "rb", "ntiles" (0 where the site has none), "grid", "block" (3-tuples), "lds" (bytes)} in launch order."""
+
+    def __enter__(self):
+        self.records = []
+        lib().fno_debug_launch_log(1)
+        return self
+
+    def __exit__(self, *exc):
+        L = lib()
+        try:
+            for i in range(L.fno_debug_launch_count()):
+                name, var, rb, nt, lds = C.c_char_p(), C.c_char_p(), C.c_int(), C.c_int(), C.c_size_t()
+                grid, block = (C.c_uint * 3)(), (C.c_uint * 3)()
+                check(L.fno_debug_launch_get(i, C.byref(name), C.byref(var), C.byref(rb), C.byref(nt), grid, block, C.byref(lds)),
+                      "debug_launch_get")
+                self.records.append({"name": name.value.decode(), "variant": var.value.decode(), "rb": int(rb.value),
+                                     "ntiles": int(nt.value), "grid": tuple(grid), "block": tuple(block), "lds": int(lds.value)})
+        finally:
+            L.fno_debug_launch_log(0)
+        return False

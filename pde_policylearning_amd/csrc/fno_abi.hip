@@ -81,6 +81,40 @@ static thread_local int g_terms_next = 0;
 #define GT(n) (g_terms_next = (n))
 static std::vector<ProfAgg> g_agg;
 
+// --------------------------------------------------------------------------
+// optional launch log (tests): which kernel INSTANTIATION a dispatch site launched and with what tiling.  The profile labels
+// above cannot tell ("k_rowidft_chan" names three kernels, "k_mode_gemm" five) and stay as they are: bench.py prices kernels
+// by them.  A dispatch site states its variant in the launching statement itself - LV(tag, rb, ntiles), launch(...) - and
+// launch() reads and clears it like g_terms_next.  Off by default: nothing is recorded and the vector holds no storage.
+// Not part of include/fnoengine.h.
+// --------------------------------------------------------------------------
+struct LaunchTag { const char* variant; int rb, ntiles; };      // rb: rows (contractions: batch rows / input channels) per workgroup; 0 = the site has none
+struct LaunchRec { const char* name; LaunchTag tag; unsigned grid[3], block[3]; size_t lds; };
+static thread_local LaunchTag g_tag_next = {nullptr, 0, 0};
+#define LV(variant, rb, ntiles) (g_tag_next = LaunchTag{(variant), (int)(rb), (int)(ntiles)})
+static bool g_llog = false;
+static std::mutex g_llog_mu;
+static std::vector<LaunchRec> g_llog_recs;
+extern "C" void fno_debug_launch_log(int on) {      // on: start an empty log; off: stop and release it
+  std::lock_guard<std::mutex> lk(g_llog_mu);
+  g_llog = on != 0;
+  std::vector<LaunchRec>().swap(g_llog_recs);
+}
+extern "C" int fno_debug_launch_count(void) {
+  std::lock_guard<std::mutex> lk(g_llog_mu);
+  return (int)g_llog_recs.size();
+}
+// name: the profile label; variant: the site's tag ("" where the site states none); grid / block: three extents each
+extern "C" int fno_debug_launch_get(int i, const char** name, const char** variant, int* rb, int* ntiles, unsigned* grid,
+                                    unsigned* block, size_t* lds_bytes) {
+  std::lock_guard<std::mutex> lk(g_llog_mu);
+  if (i < 0 || i >= (int)g_llog_recs.size() || !name || !variant || !rb || !ntiles || !grid || !block || !lds_bytes) return FNO_EINVAL;
+  const LaunchRec& r = g_llog_recs[i];
+  *name = r.name; *variant = r.tag.variant ? r.tag.variant : ""; *rb = r.tag.rb; *ntiles = r.tag.ntiles; *lds_bytes = r.lds;
+  for (int d = 0; d < 3; ++d) { grid[d] = r.grid[d]; block[d] = r.block[d]; }
+  return FNO_OK;
+}
+
 #ifdef FNO_CLOCK
 extern "C" int fno_debug_clock_dump(unsigned long long* host, size_t n) {
   hipDeviceSynchronize();
@@ -145,6 +179,8 @@ static int launch(const char* name, void (*kern)(KArgs...), dim3 grid, dim3 bloc
                   Args... args) {
   const int terms = g_terms_next;      // read and cleared before any early return: a failed launch must not leave it for the next one
   g_terms_next = 0;
+  const LaunchTag tag = g_tag_next;
+  g_tag_next = LaunchTag{nullptr, 0, 0};
   if (grid.x == 0 || grid.y == 0 || grid.z == 0) return FNO_OK;
   if (lds > 64 * 1024) {
     if (lds > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "%s needs %zu bytes of LDS (160 KB per CU)", name, lds);
@@ -175,6 +211,10 @@ static int launch(const char* name, void (*kern)(KArgs...), dim3 grid, dim3 bloc
     rec.a = prof_event();
     rec.b = prof_event();
     hipEventRecord(rec.a, st);
+  }
+  if (g_llog) {
+    std::lock_guard<std::mutex> lk(g_llog_mu);
+    g_llog_recs.push_back(LaunchRec{name, tag, {grid.x, grid.y, grid.z}, {block.x, block.y, block.z}, lds});
   }
   hipLaunchKernelGGL(kern, grid, block, lds, st, static_cast<KArgs>(args)...);
   hipError_t e = hipGetLastError();
@@ -349,6 +389,14 @@ static ModeMap make_modemap(const Geom& g, int Cin, int Cout) {
 // many -> few (twT transposed (n_in, n_out)) or few -> many (tw (n_out, n_in)); the small (kept) extent
 // is a template parameter of the fast kernels (2*m for the usual m = 2..20), anything else is generic.
 #define FNO_AXIS_GENERIC 1      // axis_pass_t: "take the generic kernel" (not an error code: those are negative)
+// launch-log tags of axis_pass_t<NS>: form 0 k_axis_fwd<NS,SEGS,true>, 1 k_axis_fwd<NS,SEGS>, 2 k_axis_inv<NS,ISEGS,true>, 3 k_axis_inv<NS,ISEGS>
+template <int NS>
+static const char* axis_tag(int form) {
+#define AXT(NS_) case NS_: { static const char* const t[4] = {"k_axis_fwd<" #NS_ ",tlds>", "k_axis_fwd<" #NS_ ">", "k_axis_inv<" #NS_ ",tlds>", "k_axis_inv<" #NS_ ">"}; return t[form]; }
+  switch (NS) { AXT(4) AXT(6) AXT(8) AXT(10) AXT(12) AXT(16) AXT(24) AXT(32) AXT(40) }
+#undef AXT
+  return "k_axis<?>";
+}
 template <int NS>
 static int axis_pass_t(hipStream_t st, bool truncating, const float2* in, float2* out, const float2* tw, int outer,
                        int n_in, int n_out, int inner) {
@@ -359,19 +407,19 @@ static int axis_pass_t(hipStream_t st, bool truncating, const float2* in, float2
     const size_t red = (size_t)SEGS * NS * 64 * 8, tab = (size_t)n_in * NS * 8;
     if constexpr (NS >= 24) {
       if (std::max(red, tab) > 96 * 1024) return FNO_AXIS_GENERIC;      // (sweeps of > 300 rows: the generic kernel)
-      return launch("k_axis_fwd_tlds", k_axis_fwd<NS, SEGS, true>, dim3((inner + 63) / 64, outer), dim3(64, SEGS), std::max(red, tab), st,
+      return LV(axis_tag<NS>(0), 0, 0), launch("k_axis_fwd_tlds", k_axis_fwd<NS, SEGS, true>, dim3((inner + 63) / 64, outer), dim3(64, SEGS), std::max(red, tab), st,
                     in, out, tw, n_in, inner);
     } else
-    return launch("k_axis_fwd", k_axis_fwd<NS, SEGS>, dim3((inner + 63) / 64, outer), dim3(64, SEGS), red, st, in, out, tw, n_in,
+    return LV(axis_tag<NS>(1), 0, 0), launch("k_axis_fwd", k_axis_fwd<NS, SEGS>, dim3((inner + 63) / 64, outer), dim3(64, SEGS), red, st, in, out, tw, n_in,
                   inner);
   }
   constexpr int ISEGS = NS > 24 ? 8 : 16;
   if constexpr (NS >= 24) {
     if ((size_t)n_out * NS * 8 > 96 * 1024) return FNO_AXIS_GENERIC;
-    return launch("k_axis_inv_tlds", k_axis_inv<NS, ISEGS, true>, dim3((inner + 63) / 64, outer), dim3(64, ISEGS), (size_t)n_out * NS * 8,
+    return LV(axis_tag<NS>(2), 0, 0), launch("k_axis_inv_tlds", k_axis_inv<NS, ISEGS, true>, dim3((inner + 63) / 64, outer), dim3(64, ISEGS), (size_t)n_out * NS * 8,
                   st, in, out, tw, n_out, inner);
   } else
-  return launch("k_axis_inv", k_axis_inv<NS, ISEGS>, dim3((inner + 63) / 64, outer), dim3(64, ISEGS), 0, st, in, out, tw,
+  return LV(axis_tag<NS>(3), 0, 0), launch("k_axis_inv", k_axis_inv<NS, ISEGS>, dim3((inner + 63) / 64, outer), dim3(64, ISEGS), 0, st, in, out, tw,
                 n_out, inner);
 }
 static int axis_pass(hipStream_t st, bool truncating, const float* in_, float* out_, const float2* tw, int outer,
@@ -395,7 +443,7 @@ static int axis_pass(hipStream_t st, bool truncating, const float* in_, float* o
   }
   if (rc != FNO_AXIS_GENERIC) return rc;
   if (n_out > 65535) return fail(FNO_EUNSUPPORTED, "axis pass grid too large (%d)", n_out);
-  return launch("k_axis_generic", k_axis_generic, dim3((inner + 255) / 256, n_out, outer), dim3(256), 0, st, in, out,
+  return LV(truncating ? "k_axis_generic(truncating)" : "k_axis_generic(extending)", 0, 0), launch("k_axis_generic", k_axis_generic, dim3((inner + 255) / 256, n_out, outer), dim3(256), 0, st, in, out,
                 tw, n_in, n_out, inner, truncating ? 1 : 0);
 }
 
@@ -472,20 +520,20 @@ static int mode_gemm(hipStream_t st, const float* x, const float* w, float* out,
     if (!trans_w) {
       const dim3 grid((Ktot + 3) / 4), blk(256);
       switch (B) {
-        case 1: return launch("k_mode_gemv", k_mode_gemv<1>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
-        case 2: return launch("k_mode_gemv", k_mode_gemv<2>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
-        case 3: return launch("k_mode_gemv", k_mode_gemv<3>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
-        default: return launch("k_mode_gemv", k_mode_gemv<4>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
+        case 1: return LV("k_mode_gemv<1>", 0, 0), launch("k_mode_gemv", k_mode_gemv<1>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
+        case 2: return LV("k_mode_gemv<2>", 0, 0), launch("k_mode_gemv", k_mode_gemv<2>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
+        case 3: return LV("k_mode_gemv<3>", 0, 0), launch("k_mode_gemv", k_mode_gemv<3>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
+        default: return LV("k_mode_gemv<4>", 0, 0), launch("k_mode_gemv", k_mode_gemv<4>, grid, blk, 0, st, xx, ww, oo, Ktot, Cin, Cout, conj_w);
       }
     } else if (conj_w) {
       // here `Cin` counts the channels of x (= the forward's Cout) and the stored block is (Cout, Cin) = forward (Cin_f, Cout_f)
       const dim3 grid(Ktot), blk(256);
       const size_t lds = (size_t)Cout * (Cin + 1) * 8;
       switch (B) {
-        case 1: return launch("k_mode_gemv_t", k_mode_gemv_t<1>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
-        case 2: return launch("k_mode_gemv_t", k_mode_gemv_t<2>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
-        case 3: return launch("k_mode_gemv_t", k_mode_gemv_t<3>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
-        default: return launch("k_mode_gemv_t", k_mode_gemv_t<4>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
+        case 1: return LV("k_mode_gemv_t<1>", 0, 0), launch("k_mode_gemv_t", k_mode_gemv_t<1>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
+        case 2: return LV("k_mode_gemv_t<2>", 0, 0), launch("k_mode_gemv_t", k_mode_gemv_t<2>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
+        case 3: return LV("k_mode_gemv_t<3>", 0, 0), launch("k_mode_gemv_t", k_mode_gemv_t<3>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
+        default: return LV("k_mode_gemv_t<4>", 0, 0), launch("k_mode_gemv_t", k_mode_gemv_t<4>, grid, blk, lds, st, xx, ww, oo, Ktot, Cout, Cin);
       }
     }
   }
@@ -499,20 +547,20 @@ static int mode_gemm(hipStream_t st, const float* x, const float* w, float* out,
     const float2 *xx = (const float2*)x, *ww = (const float2*)w;
     float2* oo = (float2*)out;
     if (Cin == 32)      // (br = 64 always at 32 channels, above)
-      return launch("k_mode_gemm", k_mode_gemm_mfma<32, 32, 64>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
-    if (br == 64) return launch("k_mode_gemm", k_mode_gemm_mfma<64, 64, 64>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
-    return launch("k_mode_gemm", k_mode_gemm_mfma<64, 64, 32>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
+      return LV("k_mode_gemm_mfma<32,32,64>", br, 0), launch("k_mode_gemm", k_mode_gemm_mfma<32, 32, 64>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
+    if (br == 64) return LV("k_mode_gemm_mfma<64,64,64>", br, 0), launch("k_mode_gemm", k_mode_gemm_mfma<64, 64, 64>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
+    return LV("k_mode_gemm_mfma<64,64,32>", br, 0), launch("k_mode_gemm", k_mode_gemm_mfma<64, 64, 32>, grid, blk, lds, st, xx, ww, oo, B, Ktot, conj_w, x_ms / 2, w_ms / 2, o_ms / 2, trans_w);
   }
   if (512 % Cout == 0 && Cout >= 32) {
     const int bt = 2 * (512 / Cout);                   // 2 batch rows per thread
     const size_t lds = ((size_t)Cin * Cout + (size_t)bt * Cin) * 8;
     if (lds <= 150 * 1024)
-      return launch("k_mode_gemm", k_mode_gemm_lds<2>, dim3(Ktot, (B + bt - 1) / bt), dim3(512), lds, st,
+      return LV("k_mode_gemm_lds<2>", bt, 0), launch("k_mode_gemm", k_mode_gemm_lds<2>, dim3(Ktot, (B + bt - 1) / bt), dim3(512), lds, st,
                     (const float2*)x, (const float2*)w, (float2*)out, B, Ktot, Cin, Cout, conj_w);
   }
   const int nb = 256 / Cout;
   dim3 grid(Ktot, (B + nb - 1) / nb);
-  return launch("k_mode_gemm", k_mode_gemm, grid, dim3(256), 0, st, (const float2*)x, (const float2*)w, (float2*)out, B,
+  return LV("k_mode_gemm", nb, 0), launch("k_mode_gemm", k_mode_gemm, grid, dim3(256), 0, st, (const float2*)x, (const float2*)w, (float2*)out, B,
                 Ktot, Cin, Cout, conj_w);
 }
 static int mode_gemm_dw(hipStream_t st, const float* x, const float* g, float* dw, int B, int Ktot, int Cin, int Cout,
@@ -524,10 +572,10 @@ static int mode_gemm_dw(hipStream_t st, const float* x, const float* g, float* d
     const float2 *xx = (const float2*)x, *gg = (const float2*)g;
     float2* dd = (float2*)dw;
     switch (B) {
-      case 1: return launch("k_mode_outer_dw", k_mode_outer_dw<1>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
-      case 2: return launch("k_mode_outer_dw", k_mode_outer_dw<2>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
-      case 3: return launch("k_mode_outer_dw", k_mode_outer_dw<3>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
-      default: return launch("k_mode_outer_dw", k_mode_outer_dw<4>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
+      case 1: return LV("k_mode_outer_dw<1>", 0, 0), launch("k_mode_outer_dw", k_mode_outer_dw<1>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
+      case 2: return LV("k_mode_outer_dw<2>", 0, 0), launch("k_mode_outer_dw", k_mode_outer_dw<2>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
+      case 3: return LV("k_mode_outer_dw<3>", 0, 0), launch("k_mode_outer_dw", k_mode_outer_dw<3>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
+      default: return LV("k_mode_outer_dw<4>", 0, 0), launch("k_mode_outer_dw", k_mode_outer_dw<4>, grid, blk, 0, st, xx, gg, dd, Ktot, Cin, Cout);
     }
   }
   if (mode_gemm_members_ok(Cin, Cout)) {
@@ -537,20 +585,20 @@ static int mode_gemm_dw(hipStream_t st, const float* x, const float* g, float* d
     const float2 *xx = (const float2*)x, *gg = (const float2*)g;
     float2* dd = (float2*)dw;
 #define DWK(CI_, CO_) do { \
-      if (bc == 32) return launch("k_mode_gemm_dw", k_mode_gemm_dw_mfma<CI_, CO_, 32>, grid, blk, lds, st, xx, gg, dd, B, Ktot, x_ms / 2, g_ms / 2, d_ms / 2); \
-      return launch("k_mode_gemm_dw", k_mode_gemm_dw_mfma<CI_, CO_, 16>, grid, blk, lds, st, xx, gg, dd, B, Ktot, x_ms / 2, g_ms / 2, d_ms / 2); } while (0)
+      if (bc == 32) return LV("k_mode_gemm_dw_mfma<" #CI_ "," #CO_ ",32>", bc, 0), launch("k_mode_gemm_dw", k_mode_gemm_dw_mfma<CI_, CO_, 32>, grid, blk, lds, st, xx, gg, dd, B, Ktot, x_ms / 2, g_ms / 2, d_ms / 2); \
+      return LV("k_mode_gemm_dw_mfma<" #CI_ "," #CO_ ",16>", bc, 0), launch("k_mode_gemm_dw", k_mode_gemm_dw_mfma<CI_, CO_, 16>, grid, blk, lds, st, xx, gg, dd, B, Ktot, x_ms / 2, g_ms / 2, d_ms / 2); } while (0)
     if (Cin == 32) DWK(32, 32);
     DWK(64, 64);
 #undef DWK
   }
   if (512 % Cout == 0 && Cout >= 32) {
     const int it = 2 * (512 / Cout);                   // 2 input channels per thread
-    return launch("k_mode_gemm_dw", k_mode_gemm_dw_lds<2>, dim3(Ktot, (Cin + it - 1) / it), dim3(512),
+    return LV("k_mode_gemm_dw_lds<2>", it, 0), launch("k_mode_gemm_dw", k_mode_gemm_dw_lds<2>, dim3(Ktot, (Cin + it - 1) / it), dim3(512),
                   (size_t)64 * (it + Cout) * 8, st, (const float2*)x, (const float2*)g, (float2*)dw, B, Ktot, Cin, Cout);
   }
   const int ni = 256 / Cout;
   dim3 grid(Ktot, (Cin + ni - 1) / ni);
-  return launch("k_mode_gemm_dw", k_mode_gemm_dw, grid, dim3(256), 0, st, (const float2*)x, (const float2*)g,
+  return LV("k_mode_gemm_dw", ni, 0), launch("k_mode_gemm_dw", k_mode_gemm_dw, grid, dim3(256), 0, st, (const float2*)x, (const float2*)g,
                 (float2*)dw, B, Ktot, Cin, Cout);
 }
 // all layers of a stack in one launch each way (blockIdx.y = layer); wp / wpt nullable; `stride` = floats between layers
@@ -734,8 +782,8 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
       if (C == 32) return launch("k_rowdft_tile_drop", k_rowdft_tile<32, 128, 1>, dim3(grid), dim3(256), lds, st, a);
       return launch("k_rowdft_tile_drop", k_rowdft_tile<64, 128, 1>, dim3(grid), dim3(256), lds, st, a);
     }
-    if (C == 32) return launch("k_rowdft_tile", k_rowdft_tile<32, 128>, dim3(grid), dim3(256), lds, st, a);
-    return launch("k_rowdft_tile", k_rowdft_tile<64, 128>, dim3(grid), dim3(256), lds, st, a);
+    if (C == 32) return LV("k_rowdft_tile<32,128>", 0, a.ntiles), launch("k_rowdft_tile", k_rowdft_tile<32, 128>, dim3(grid), dim3(256), lds, st, a);
+    return LV("k_rowdft_tile<64,128>", 0, a.ntiles), launch("k_rowdft_tile", k_rowdft_tile<64, 128>, dim3(grid), dim3(256), lds, st, a);
   }
   constexpr int chan_rb = 320;
   if (K2P) {
@@ -750,7 +798,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
         const int ntiles = B * (C / 8) * (g.P / rb);
         const int per_cu = std::max(1, (int)std::min<size_t>(4, FNO_LDS_MAX / lds));
         const dim3 grid(std::min(ntiles, per_cu * dev_ncu())), blk(256);
-#define ROWDFT_CHAN4(K) launch("k_rowdft_chan4", k_rowdft_chan4<K>, grid, blk, lds, st, x, (float2*)x1, tfwd, C, g.P, g.W, g.Klast, rb, ntiles, act_in, 16 * g.NJ)
+#define ROWDFT_CHAN4(K) LV(act_in ? "k_rowdft_chan4<" #K ">(act_in)" : "k_rowdft_chan4<" #K ">", rb, ntiles), launch("k_rowdft_chan4", k_rowdft_chan4<K>, grid, blk, lds, st, x, (float2*)x1, tfwd, C, g.P, g.W, g.Klast, rb, ntiles, act_in, 16 * g.NJ)
         if (K2P == 8) return ROWDFT_CHAN4(8);
         if (K2P == 16) return ROWDFT_CHAN4(16);
         return ROWDFT_CHAN4(32);
@@ -768,7 +816,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
       const int per_cu = std::max(1, (int)std::min<size_t>(4, FNO_LDS_MAX / lds));
       const dim3 grid(std::min(ntiles, per_cu * dev_ncu())), blk(256);
       (void)cg;
-#define ROWDFT_CHAN(K) launch("k_rowdft_chan", k_rowdft_chan<K, 16>, grid, blk, lds, st, x, (float2*)x1, tT, C, g.P, g.W, g.Klast, rb, ntiles, act_in)
+#define ROWDFT_CHAN(K) LV(act_in ? "k_rowdft_chan<" #K ",16>(act_in)" : "k_rowdft_chan<" #K ",16>", rb, ntiles), launch("k_rowdft_chan", k_rowdft_chan<K, 16>, grid, blk, lds, st, x, (float2*)x1, tT, C, g.P, g.W, g.Klast, rb, ntiles, act_in)
       if (K2P == 8) return ROWDFT_CHAN(8);
       if (K2P == 16) return ROWDFT_CHAN(16);
       return ROWDFT_CHAN(32);
@@ -781,7 +829,7 @@ static int row_forward(hipStream_t st, const Geom& g, const float* tfwd, const f
   while (rb > 1 && ((size_t)C * (rb * g.W + 1) + (size_t)g.W * 2 * k2e) * 4 > 64 * 1024) rb >>= 1;
   const size_t lds = ((size_t)C * (rb * g.W + 1) + (size_t)g.W * 2 * k2e) * 4;
   if (lds > FNO_LDS_MAX) return fail(FNO_EUNSUPPORTED, "row tile of %d channels x %d floats exceeds LDS", C, g.W);
-  return launch("k_rowdft_generic", k_rowdft_generic, dim3(B * ((g.P + rb - 1) / rb)), dim3(256), lds, st, x, (float2*)x1,
+  return LV("k_rowdft_generic", rb, B * ((g.P + rb - 1) / rb)), launch("k_rowdft_generic", k_rowdft_generic, dim3(B * ((g.P + rb - 1) / rb)), dim3(256), lds, st, x, (float2*)x1,
                 tfwd, C, g.P, g.W, g.Klast, rb);
 }
 static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const float* tT, int K2P, int B, int C,
@@ -795,8 +843,8 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
     a.PW = g.PW; a.W = g.W; a.P = g.P; a.K2in = g.Klast; a.K2out = 0; a.NJ = g.NJ;
     a.tiles_per_plane = g.PW / 128; a.ntiles = B * a.tiles_per_plane;
     const int grid = std::min(a.ntiles, 2 * dev_ncu());
-    if (C == 32) return launch("k_rowidft_tile", k_pw_fwd<2, 32, 128>, dim3(grid), dim3(256), lds, st, a);
-    return launch("k_rowidft_tile", k_pw_fwd<2, 64, 128>, dim3(grid), dim3(512), lds, st, a);
+    if (C == 32) return LV("k_pw_fwd<2,32,128>", 0, a.ntiles), launch("k_rowidft_tile", k_pw_fwd<2, 32, 128>, dim3(grid), dim3(256), lds, st, a);
+    return LV("k_pw_fwd<2,64,128>", 0, a.ntiles), launch("k_rowidft_tile", k_pw_fwd<2, 64, 128>, dim3(grid), dim3(512), lds, st, a);
   }
   constexpr int chan_rb = 4;
   if (K2P) {
@@ -810,26 +858,26 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
       if (g.PW % 4 == 0 && g.W < ROWFLAT_CH && ldsf <= FNO_LDS_MAX && B <= 65535) {     // whole-line tiles of the flattened planes
         const dim3 gridf((g.PW + ROWFLAT_CH - 1) / ROWFLAT_CH, B);
         constexpr int flat_threads = 512;
-        if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_flat_mfma<8>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
-        if (K2P == 16) return launch("k_rowidft_chan", k_rowidft_flat_mfma<16>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
-        return launch("k_rowidft_chan", k_rowidft_flat_mfma<32>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
+        if (K2P == 8) return LV("k_rowidft_flat_mfma<8>", 0, (int)(gridf.x * gridf.y)), launch("k_rowidft_chan", k_rowidft_flat_mfma<8>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
+        if (K2P == 16) return LV("k_rowidft_flat_mfma<16>", 0, (int)(gridf.x * gridf.y)), launch("k_rowidft_chan", k_rowidft_flat_mfma<16>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
+        return LV("k_rowidft_flat_mfma<32>", 0, (int)(gridf.x * gridf.y)), launch("k_rowidft_chan", k_rowidft_flat_mfma<32>, gridf, dim3(flat_threads), ldsf, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast);
       }
       int rbm = rb;
       while (rbm > 1 && (size_t)C * (rbm * g.W + 1) * 4 + tabb > 80 * 1024) rbm >>= 1;
       const size_t lds3 = (size_t)C * (rbm * g.W + 1) * 4 + tabb;
       const dim3 gridm(B * ((g.P + rbm - 1) / rbm));
       if (lds3 <= FNO_LDS_MAX) {
-        if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_chan_mfma<8>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
-        if (K2P == 16) return launch("k_rowidft_chan", k_rowidft_chan_mfma<16>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
-        return launch("k_rowidft_chan", k_rowidft_chan_mfma<32>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
+        if (K2P == 8) return LV("k_rowidft_chan_mfma<8>", rbm, (int)gridm.x), launch("k_rowidft_chan", k_rowidft_chan_mfma<8>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
+        if (K2P == 16) return LV("k_rowidft_chan_mfma<16>", rbm, (int)gridm.x), launch("k_rowidft_chan", k_rowidft_chan_mfma<16>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
+        return LV("k_rowidft_chan_mfma<32>", rbm, (int)gridm.x), launch("k_rowidft_chan", k_rowidft_chan_mfma<32>, gridm, dim3(256), lds3, st, (const float2*)z, y, tinv, bias, C, g.P, g.W, g.Klast, rbm);
       }
     }
     if (lds2 <= FNO_LDS_MAX) {
       const dim3 grid(B * ((g.P + rb - 1) / rb));
       const dim3 blk(std::min(256, ((rb * C + 63) / 64) * 64));
-      if (K2P == 8) return launch("k_rowidft_chan", k_rowidft_chan<8>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
-      if (K2P == 16) return launch("k_rowidft_chan", k_rowidft_chan<16>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
-      return launch("k_rowidft_chan", k_rowidft_chan<32>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
+      if (K2P == 8) return LV("k_rowidft_chan<8>", rb, (int)grid.x), launch("k_rowidft_chan", k_rowidft_chan<8>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
+      if (K2P == 16) return LV("k_rowidft_chan<16>", rb, (int)grid.x), launch("k_rowidft_chan", k_rowidft_chan<16>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
+      return LV("k_rowidft_chan<32>", rb, (int)grid.x), launch("k_rowidft_chan", k_rowidft_chan<32>, grid, blk, lds2, st, (const float2*)z, y, tT, bias, C, g.P, g.W, g.Klast, rb);
     }
   }
   int rb = 8;
@@ -839,7 +887,7 @@ static int row_inverse(hipStream_t st, const Geom& g, const float* tinv, const f
   const dim3 grid(B * ((g.P + rb - 1) / rb));
   // (<= 32 kept bins always fit one of the tile / lanes-as-channels kernels above: plan creation refuses rows whose channel tile
   // exceeds LDS; what is left for the generic kernel is more than 32 bins, its run-time-bound form)
-  return launch("k_rowidft_generic", k_rowidft_generic<0>, grid, dim3(256), need(rb), st, (const float2*)z, y, tinv, bias, C,
+  return LV("k_rowidft_generic<0>", rb, (int)grid.x), launch("k_rowidft_generic", k_rowidft_generic<0>, grid, dim3(256), need(rb), st, (const float2*)z, y, tinv, bias, C,
                 g.P, g.W, g.Klast, rb);
 }
 

@@ -31,6 +31,24 @@ def test_header_symbols_exported(lib):
     assert lib.fno_version() >= 100
 
 
+def test_launch_log_is_off_by_default_and_outside_the_public_header(lib):
+    """fno_debug_launch_*: exported for the tests, declared in _lib.py only, empty until switched on, and empty again after
+    it is switched off"""
+    from pde_policylearning_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "fnoengine.h")).read()
+    names = ("fno_debug_launch_log", "fno_debug_launch_count", "fno_debug_launch_get")
+    assert all(hasattr(lib, n) and n not in hdr and n not in _lib.EXPORTED_SYMBOLS for n in names)
+    assert lib.fno_debug_launch_count() == 0
+    name, var, rb, nt, lds = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    grid, block = (ctypes.c_uint * 3)(), (ctypes.c_uint * 3)()
+    get = lambda i: lib.fno_debug_launch_get(i, ctypes.byref(name), ctypes.byref(var), ctypes.byref(rb), ctypes.byref(nt), grid, block,  # noqa: E731
+                                             ctypes.byref(lds))
+    assert get(0) < 0 and get(-1) < 0
+    with _lib.launch_log() as log:
+        assert lib.fno_debug_launch_count() == 0 and get(0) < 0
+    assert log.records == [] and lib.fno_debug_launch_count() == 0
+
+
 def test_struct_layout_matches_header(lib):
     from pde_policylearning_amd import _lib
     # FnoSpecDesc: 3 + 3 + 3 + 4 ints ; FnoModelDesc: 6 + 3 + 3 + 3 ints

@@ -339,19 +339,25 @@ SPEC_ROWS = [
     # dialect A: without bias, 3-D, and kept corners that overlap (2 m > H: the second corner wins)
     ("A-nobias", (2, 64, 64, 128), (6, 6)), ("A", (2, 32, 16, 16, 16), (4, 4, 4)), ("A-nobias", (1, 32, 16, 16, 16), (4, 4, 4)),
     ("A", (2, 32, 8, 16), (6, 6)), ("A-nobias", (2, 32, 8, 16), (6, 6)),
+    # routes no row above reaches on 256 compute units (tests/test_spec_conv_gpu.py asserts them from the launch log): row blocks
+    # of 2 and 4 rows with a partial last block on the VALU and matrix-core row kernels, persistent loops with uneven shares,
+    # the long-run forward kernel looping on odd rows, and Cin != Cout (channels (48, 64)) on the stream contraction
+    ("C", (2, 34, 1025, 73), (5, 12)), ("C", (2, 34, 45, 47, 73), (3, 4, 12)), ("C", (2, 32, 45, 47, 33), (3, 4, 12)),
+    ("C", (3, 32, 16, 32, 73), (3, 4, 12)), ("C", (3, (48, 64), 64, 64), (17, 21)),
 ]
 
 
 @pytest.mark.parametrize("dialect,shape,modes", SPEC_ROWS)
 def test_spectral_conv(dev, dialect, shape, modes):
     F = _F()
-    C, nd = shape[1], len(shape) - 2
+    cin, cout = shape[1] if isinstance(shape[1], tuple) else (shape[1], shape[1])
+    nd = len(shape) - 2
     nc = 2 ** (nd - 1)
-    d = {"x": fill_named("hs.x", shape, 1.0), "dy": fill_named("hs.dy", shape, 1.0)}
+    d = {"x": fill_named("hs.x", (shape[0], cin) + shape[2:], 1.0), "dy": fill_named("hs.dy", (shape[0], cout) + shape[2:], 1.0)}
     for i in range(nc):
-        d[f"w{i}"] = fill_named(f"hs.w{i}", (C, C) + tuple(modes) + (2,), 0.02)
+        d[f"w{i}"] = fill_named(f"hs.w{i}", (cin, cout) + tuple(modes) + (2,), 0.02)
     if dialect == "A":
-        d["bias"] = fill_named("hs.bias", (C,) + (1,) * nd, 0.1)
+        d["bias"] = fill_named("hs.bias", (cout,) + (1,) * nd, 0.1)
     inputs = _dev_inputs({k: torch.from_numpy(v) for k, v in d.items()}, dev, grad=set(d) - {"dy"})
     norm = {"A": "forward", "B": "ortho", "C": "backward"}[dialect[0]]
     live = list(modes)
