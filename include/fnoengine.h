@@ -477,6 +477,44 @@ int fno_chanflow_diagnostics2(const FnoChanflowGrid* grid, int batch, int dtype,
                               void* out, size_t out_stride, void* ws, size_t ws_bytes, void* stream);
 int fno_ctrl_stats_update(const FnoCtrlStats* table, int nfields, long long count, void* stream);
 
+/* ----------------------------------------------------------------------
+ * NSControlEnv2D (libs/envs/ns_control_2d.py): the 2-D periodic channel with wall blowing and suction, float64.  Arrays are
+ * (batch, ny, nx), row = wall-normal index, column = streamwise index, periodic in x with all nx columns distinct; `batch`
+ * independent environments, one workgroup each, the whole state in LDS for the whole launch.  3 <= ny, nx and
+ * ny * nx <= FNO_NS2D_MAX_POINTS (seven float64 planes in 160 KB of LDS); anything beyond returns FNO_EUNSUPPORTED.
+ *   fno_ns2d_solve: NSControlEnv2D.solve (:359-491) from (p, u, v) with per-environment F[batch], nu[batch] and wall velocities
+ *     bc_lo, bc_hi (batch, nx) (NULL: zero): steps while udiff > u_diff_thre; more than step_cap steps end the launch with
+ *     status 2 (the reference's "Not converged solving!", step_cap = 5000 there) and max_step > 1 caps with status 1; status 0
+ *     = converged.  out (batch, 3) = bulk_v (mean|u|), steps, status.  update_state != 0 writes p, u, v in place (and un, vn
+ *     unless NULL) unless the cap was hit.
+ *   fno_ns2d_fixed_mass: solve_fixed_mass (:493-536): converged solves at min_f[b] and max_f[b], then bisection on F towards
+ *     target[b] while error > error_threshold, at most max_bisect times, all in one launch.  out (batch, 6) = result_f, flow,
+ *     error, bisections, total steps, status (0 ok, 1 target outside the bracket: (F[b], target, 0) as the reference returns,
+ *     2 a solve hit step_cap).  The state is read only.
+ *   fno_ns2d_diagnostics: out (batch, 7) = the drag_reduction scalars of step (:562-581) in the order of `info`: |wall shear
+ *     stress|, mean|u|, mean|v|, mean(p[-1,:]), dpdx[b] (NULL: -1), -|divergence| at the fixed indices 10 and 9 (so ny, nx >= 11),
+ *     ||v|| + ||u||; ptop (batch, nx) = p[-1, :].
+ * Every sum is a fixed-order reduction inside one workgroup: run-to-run, batch-size and batch-position invariant.  No
+ * allocation, no synchronisation.
+ * ---------------------------------------------------------------------- */
+#define FNO_NS2D_MAX_POINTS 2907
+#define FNO_NS2D_SOLVE_OUT 3
+#define FNO_NS2D_FIXED_OUT 6
+#define FNO_NS2D_DIAG_OUT 7
+typedef struct FnoNs2dGrid {
+  int nx, ny, nit;
+  double dx, dy, dt, rho;
+} FnoNs2dGrid;
+int fno_ns2d_solve(const FnoNs2dGrid* grid, int batch, void* p, void* u, void* v, void* un, void* vn, const void* F,
+                   const void* nu, const void* bc_lo, const void* bc_hi, int max_step, double u_diff_thre, int step_cap,
+                   int update_state, void* out, void* stream);
+int fno_ns2d_fixed_mass(const FnoNs2dGrid* grid, int batch, const void* p, const void* u, const void* v, const void* F,
+                        const void* nu, const void* target, const void* min_f, const void* max_f, const void* bc_lo,
+                        const void* bc_hi, double u_diff_thre, int step_cap, int max_bisect, double error_threshold, void* out,
+                        void* stream);
+int fno_ns2d_diagnostics(const FnoNs2dGrid* grid, int batch, const void* p, const void* u, const void* v, const void* nu,
+                         const void* dpdx, void* out, void* ptop, void* stream);
+
 /* Names and average device time (ms, HIP events on `stream`) of the kernels launched
  * by the last fno_model_* call made with profiling enabled; used by bench.py for the
  * roofline line.  fno_profile_enable(1) makes every launch event-bracketed (slow path). */

@@ -50,6 +50,11 @@ class FnoChanflowGrid(C.Structure):
     _fields_ = [("Nx", C.c_int), ("Ny", C.c_int), ("Nz", C.c_int), ("dx", C.c_double), ("dz", C.c_double), ("nu", C.c_double)]
 
 
+class FnoNs2dGrid(C.Structure):
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nit", C.c_int), ("dx", C.c_double), ("dy", C.c_double), ("dt", C.c_double),
+                ("rho", C.c_double)]
+
+
 FNO_CTRL_STATS_MAX = 8
 
 
@@ -178,6 +183,10 @@ def lib():
     L.fno_chanflow_diagnostics2_workspace_bytes.restype = sz
     L.fno_chanflow_diagnostics2.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
     L.fno_ctrl_stats_update.argtypes = [C.POINTER(FnoCtrlStats), ci, C.c_longlong, vp]
+    ng = C.POINTER(FnoNs2dGrid)
+    L.fno_ns2d_solve.argtypes = [ng, ci] + [vp] * 9 + [ci, C.c_double, ci, ci, vp, vp]
+    L.fno_ns2d_fixed_mass.argtypes = [ng, ci] + [vp] * 10 + [C.c_double, ci, ci, C.c_double, vp, vp]
+    L.fno_ns2d_diagnostics.argtypes = [ng, ci] + [vp] * 8
     L.fno_pino_loss_workspace_bytes.argtypes = [ci, ci, ci]
     L.fno_pino_loss_workspace_bytes.restype = sz
     L.fno_pino_loss_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, fl, vp, vp, vp, sz, vp]
@@ -231,7 +240,7 @@ EXPORTED_SYMBOLS = [
     "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",
     "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
     "fno_ctrl_encode", "fno_ctrl_decode", "fno_chanflow_diagnostics2_workspace_bytes", "fno_chanflow_diagnostics2",
-    "fno_ctrl_stats_update",
+    "fno_ctrl_stats_update", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
     "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
 ]
 

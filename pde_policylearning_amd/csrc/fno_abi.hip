@@ -19,6 +19,7 @@
 #include "k_chanflow.h"
 #include "k_chanflow_step.h"
 #include "k_control_loop.h"
+#include "k_ns2d.h"
 #include "k_pointwise.h"
 #include "k_block_fwd2.h"
 #include "k_block_fwd3.h"
@@ -2606,6 +2607,77 @@ extern "C" int fno_chanflow_diagnostics2(const FnoChanflowGrid* grid, int B, int
                    ChanflowCFields{(const double*)U, (const double*)V, (const double*)W}, (const double*)p2, (double*)ws));
   return launch("k_chanflow_diag_finish", k_chanflow_diag_finish, dim3(B), dim3(256), 0, c.st, c.geo, (const double*)ws, (const double*)dpdx,
                 (double*)out, out_stride);
+}
+// ===========================================================================
+// NSControlEnv2D: the 2-D periodic channel, fp64, one workgroup per environment with the state in LDS (k_ns2d.h)
+// ===========================================================================
+static size_t ns2d_lds_bytes(int n) { return ((size_t)7 * n + kNs2dRed) * sizeof(double); }
+static int ns2d_prepare(const char* who, const FnoNs2dGrid* g, int B, std::initializer_list<const void*> need,
+                        std::initializer_list<const void*> opt, Ns2dGeo* geo) {
+  if (!g) return fail(FNO_EINVAL, "%s: null grid", who);
+  if (B < 1) return fail(FNO_EINVAL, "%s: batch must be positive (got %d)", who, B);
+  if (g->nx < 3 || g->ny < 3) return fail(FNO_EUNSUPPORTED, "%s: nx and ny must be at least 3 (got ny=%d, nx=%d)", who, g->ny, g->nx);
+  if ((long long)g->nx * g->ny > kNs2dMaxPoints)
+    return fail(FNO_EUNSUPPORTED, "%s: ny*nx = %lld exceeds %d points, the seven float64 planes of one environment have to fit LDS (160 KB per CU)",
+                who, (long long)g->nx * g->ny, kNs2dMaxPoints);
+  if (g->nit < 0) return fail(FNO_EINVAL, "%s: nit must not be negative (got %d)", who, g->nit);
+  if (!(g->dx > 0) || !(g->dy > 0) || !(g->dt > 0) || !(g->rho > 0) || !std::isfinite(g->dx) || !std::isfinite(g->dy) ||
+      !std::isfinite(g->dt) || !std::isfinite(g->rho))
+    return fail(FNO_EINVAL, "%s: dx, dy, dt and rho must be positive and finite", who);
+  for (const void* p : need)
+    if (!p || ((uintptr_t)p & 7)) return fail(FNO_EINVAL, "%s: null or misaligned (8 B) tensor", who);
+  for (const void* p : opt)
+    if ((uintptr_t)p & 7) return fail(FNO_EINVAL, "%s: misaligned (8 B) tensor", who);
+  *geo = Ns2dGeo{g->nx, g->ny, g->nit, g->dx, g->dy, g->dt, g->rho};
+  return FNO_OK;
+}
+static int ns2d_loop_check(const char* who, double thre, int step_cap) {
+  if (step_cap < 1 || step_cap > (1 << 30)) return fail(FNO_EINVAL, "%s: step_cap must be in 1..2^30 (got %d)", who, step_cap);
+  if (std::isnan(thre)) return fail(FNO_EINVAL, "%s: u_diff_thre is NaN", who);
+  return FNO_OK;
+}
+extern "C" int fno_ns2d_solve(const FnoNs2dGrid* grid, int B, void* p, void* u, void* v, void* un, void* vn, const void* F,
+                              const void* nu, const void* bc_lo, const void* bc_hi, int max_step, double u_diff_thre, int step_cap,
+                              int update_state, void* out, void* stream) {
+  static_assert(FNO_NS2D_SOLVE_OUT == kNs2dSolveOut && FNO_NS2D_FIXED_OUT == kNs2dFixedOut && FNO_NS2D_DIAG_OUT == kNs2dDiagOut &&
+                FNO_NS2D_MAX_POINTS == kNs2dMaxPoints, "ns2d constants of the header");
+  Ns2dGeo geo;
+  LAUNCHCHK(ns2d_prepare("fno_ns2d_solve", grid, B, {p, u, v, F, nu, out}, {un, vn, bc_lo, bc_hi}, &geo));
+  LAUNCHCHK(ns2d_loop_check("fno_ns2d_solve", u_diff_thre, step_cap));
+  Ns2dSolveArgs a;
+  a.p = (double*)p; a.u = (double*)u; a.v = (double*)v; a.un = (double*)un; a.vn = (double*)vn;
+  a.F = (const double*)F; a.nu = (const double*)nu; a.bc_lo = (const double*)bc_lo; a.bc_hi = (const double*)bc_hi;
+  a.out = (double*)out; a.max_step = max_step; a.step_cap = step_cap; a.update = update_state ? 1 : 0; a.thre = u_diff_thre;
+  return LV("k_ns2d_solve", 1, B), launch("k_ns2d_solve", k_ns2d_solve, dim3(B), dim3(kNs2dThreads), ns2d_lds_bytes(geo.nx * geo.ny),
+                                          (hipStream_t)stream, geo, a);
+}
+extern "C" int fno_ns2d_fixed_mass(const FnoNs2dGrid* grid, int B, const void* p, const void* u, const void* v, const void* F,
+                                   const void* nu, const void* target, const void* min_f, const void* max_f, const void* bc_lo,
+                                   const void* bc_hi, double u_diff_thre, int step_cap, int max_bisect, double error_threshold,
+                                   void* out, void* stream) {
+  Ns2dGeo geo;
+  LAUNCHCHK(ns2d_prepare("fno_ns2d_fixed_mass", grid, B, {p, u, v, F, nu, target, min_f, max_f, out}, {bc_lo, bc_hi}, &geo));
+  LAUNCHCHK(ns2d_loop_check("fno_ns2d_fixed_mass", u_diff_thre, step_cap));
+  if (max_bisect < 1 || max_bisect > 4096) return fail(FNO_EINVAL, "fno_ns2d_fixed_mass: max_bisect must be in 1..4096 (got %d)", max_bisect);
+  if (std::isnan(error_threshold)) return fail(FNO_EINVAL, "fno_ns2d_fixed_mass: error_threshold is NaN");
+  Ns2dFixedArgs a;
+  a.p = (const double*)p; a.u = (const double*)u; a.v = (const double*)v; a.F = (const double*)F; a.nu = (const double*)nu;
+  a.target = (const double*)target; a.min_f = (const double*)min_f; a.max_f = (const double*)max_f;
+  a.bc_lo = (const double*)bc_lo; a.bc_hi = (const double*)bc_hi; a.out = (double*)out;
+  a.step_cap = step_cap; a.max_bisect = max_bisect; a.thre = u_diff_thre; a.err_thre = error_threshold;
+  return LV("k_ns2d_fixed_mass", 1, B), launch("k_ns2d_fixed_mass", k_ns2d_fixed_mass, dim3(B), dim3(kNs2dThreads),
+                                               ns2d_lds_bytes(geo.nx * geo.ny), (hipStream_t)stream, geo, a);
+}
+extern "C" int fno_ns2d_diagnostics(const FnoNs2dGrid* grid, int B, const void* p, const void* u, const void* v, const void* nu,
+                                    const void* dpdx, void* out, void* ptop, void* stream) {
+  Ns2dGeo geo;
+  LAUNCHCHK(ns2d_prepare("fno_ns2d_diagnostics", grid, B, {p, u, v, nu, out, ptop}, {dpdx}, &geo));
+  if (geo.nx < 11 || geo.ny < 11)
+    return fail(FNO_EUNSUPPORTED, "fno_ns2d_diagnostics: the divergence probe reads the fixed indices 10 and 9, so ny and nx must be at least 11 (got ny=%d, nx=%d)",
+                geo.ny, geo.nx);
+  return LV("k_ns2d_diag", 1, B), launch("k_ns2d_diag", k_ns2d_diag, dim3(B), dim3(256), 0, (hipStream_t)stream, geo, (const double*)p,
+                                         (const double*)u, (const double*)v, (const double*)nu, (const double*)dpdx, (double*)out,
+                                         (double*)ptop);
 }
 extern "C" int fno_ctrl_stats_update(const FnoCtrlStats* tab, int nfields, long long count, void* stream) {
   static_assert(FNO_CTRL_STATS_MAX == kCtrlStatsMax, "statistics table size");

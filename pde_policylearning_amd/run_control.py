@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from .control import Collector, ControlLoop, make_policy
+from .control import Collector, ControlLoop, ControlResult, make_policy
 from .train_observer import load_train_yaml
 
 _KEYS = ("policy_name", "model_name", "load_model_name", "modes", "width", "x_range", "y_range", "control_timestep", "detect_plane",
@@ -46,6 +46,9 @@ def build_parser():
     ap.add_argument("--tanh-channel", dest="tanh_channel", action="store_true", help="analytic start state on a tanh grid")
     ap.add_argument("--check_every", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--env_name", default="NSControlEnvMatlab", help="NSControlEnvMatlab (3-D channel) | NSControlEnv2D (2-D channel)")
+    ap.add_argument("--fix_flow", action="store_true", help="NSControlEnv2D: bisect the force that holds the bulk velocity")
+    ap.add_argument("--bc_type", default="original")
     return ap
 
 
@@ -57,6 +60,10 @@ def plan_from_yaml(args, yaml_dict=None):
         yaml_dict = load_train_yaml(plan["control_yaml"])
     plan.update(dict(yaml_dict or {}))
     ns = argparse.Namespace(**plan)
+    if ns.env_name == "NSControlEnv2D":
+        return _plan_ns2d(ns)
+    if ns.env_name != "NSControlEnvMatlab":
+        raise RuntimeError("Not supported environment!")                 # run_control.py:107
     if ns.policy_name in ("rand", "optimal-observer", "optimal-policy-observer"):
         make_policy(ns.policy_name)                                      # raises NotImplementedError with the reason
     if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno"):
@@ -70,6 +77,29 @@ def plan_from_yaml(args, yaml_dict=None):
         raise ValueError("run_control: a neural policy needs load_model_name (a model saved by train_observer)")
     if not ns.state_path_name and not getattr(ns, "tanh_channel", False):
         raise ValueError("run_control: no initial condition (state_path_name, or --tanh-channel)")
+    return ns
+
+
+NS2D_POLICIES = ("gt", "unmanipulated")
+
+
+def _plan_ns2d(ns):
+    """the plan of an `env_name: NSControlEnv2D` run: `policies` = the listed names in order"""
+    names = list(ns.policy_name) if isinstance(ns.policy_name, (list, tuple)) else [ns.policy_name]
+    for name in names:
+        if name in ("rand", "optimal-observer", "optimal-policy-observer"):
+            make_policy(name)                                            # raises NotImplementedError with the reason
+        if name not in NS2D_POLICIES:
+            raise RuntimeError(f"Not supported policy name. (NSControlEnv2D runs {' and '.join(NS2D_POLICIES)}, got {name!r})")
+    if not names:
+        raise RuntimeError("Not supported policy name. (NSControlEnv2D: the policy list is empty)")
+    if ns.collect_data:
+        raise ValueError("run_control: collect_data is not supported with env_name NSControlEnv2D: the collector writes the 3-D "
+                         "fields of the channel (U_field, V_field, W_field), which this environment does not have")
+    ns.policies = names
+    ns.steps = int(ns.control_timestep) + 1
+    ns.collect_folder = None
+    ns.ensemble = max(int(getattr(ns, "ensemble", 1)), 1)
     return ns
 
 
@@ -115,7 +145,52 @@ def make_plan_policy(plan, device="cuda"):
     return make_policy(plan.policy_name, observer=observer, p_norm=ds.p_norm, v_norm=ds.v_norm)
 
 
+EXPLODE_AT = 10.0                 # run_control.py:294-295: |reward_div| above this is "Control exploded!"
+
+
+def run_ns2d(plan, device="cuda"):
+    """every listed policy in turn from the same start state -> {policy name: ControlResult}; `log` is (T, B, 7), the
+    drag_reduction scalars in the order of NSControlEnv2D.INFO_KEYS.  The reference raises "Control exploded!" when
+    |reward_div| passes 10 and loses what the other policies gave; here the rollout of that policy ends with the exploding
+    iteration as its last entry, `result.exploded_at` is that iteration (None otherwise), the message is printed and the
+    next policy runs.  (With python_env_rno.yaml as shipped, `unmanipulated` does explode, near iteration 89, in the
+    reference's arithmetic too: reset_init takes the target flow before the first step, every bisection then finds the target
+    below its bracket and returns F = 4 unchanged, and the accelerating flow leaves the explicit scheme's stable range.)"""
+    from .libs.envs.ns_control_2d import NSControlEnv2D
+    np.random.seed(plan.seed)
+    env = NSControlEnv2D(plan, detect_plane=plan.detect_plane, bc_type=plan.bc_type, ensemble=plan.ensemble, device=device)
+    start = env.get_state()
+    results = {}
+    for name in plan.policies:
+        env.set_state(start)
+        env.init_bulk_v = env.info_init = None
+        log, infos, exploded_at = [], [], None
+        for i in range(plan.steps):
+            opV1, opV2 = env.gt_control()
+            if name == "unmanipulated":                                  # run_control.py:158-161, :227-232
+                opV2 = opV2 * 0
+                if i == 0:
+                    env.reset_init()
+            _, div, _, info = env.step(opV1, opV2)
+            step_infos = [info] if env.B == 1 else info
+            infos.append(step_infos)
+            log.append([[x[k] for k in env.INFO_KEYS] for x in step_infos])
+            if any(not abs(d) <= EXPLODE_AT for d in ([div] if env.B == 1 else div)):      # :294-295
+                exploded_at = i
+                print(f"Control exploded! policy {name}, iteration {i}: the rollout of this policy ends here")
+                break
+        results[name] = ControlResult(np.asarray(log), infos, env.B == 1)
+        results[name].exploded_at = exploded_at
+        for b, info in enumerate(infos[-1]):
+            print(f"{name} env {b} (iteration {len(infos) - 1}): " +
+                  "; ".join(f"{k.split('/', 1)[1]} {v:.7g}" for k, v in info.items() if k.startswith("drag_reduction/")))
+    return results
+
+
 def run(plan):
+    if getattr(plan, "env_name", None) == "NSControlEnv2D":
+        results = run_ns2d(plan)
+        return results if isinstance(plan.policy_name, (list, tuple)) else results[plan.policies[0]]
     env = make_env(plan)
     policy = make_plan_policy(plan, env.device)
     collector = Collector(plan.collect_folder, plan.collect_start, re=plan.Re) if plan.collect_folder else None
