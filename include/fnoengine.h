@@ -379,6 +379,9 @@ int fno_lifting_forward(int batch, int cin, int channels, size_t plane, const fl
                         float* y, void* stream);
 int fno_lifting_backward(int batch, int cin, int channels, size_t plane, const float* x, const float* dy, float* dw,
                          float* dbias, void* ws, size_t ws_bytes, void* stream);
+/* dx[b][k][p] = sum_c w[c][k] dy[b][c][p], channels ascending: the input gradient, for the shapes fno_lifting_forward takes */
+int fno_lifting_backward_dx(int batch, int cin, int channels, size_t plane, const float* dy, const float* w, float* dx,
+                            void* stream);
 
 /* ------------------------------------------------------------------------
  * Channel-flow Navier-Stokes right-hand side on the staggered grid and the physics-informed loss built on it:
@@ -476,6 +479,34 @@ int fno_chanflow_diagnostics2(const FnoChanflowGrid* grid, int batch, int dtype,
                               size_t table_bytes, const void* U, const void* V, const void* W, const void* p2, const void* dpdx,
                               void* out, size_t out_stride, void* ws, size_t ws_bytes, void* stream);
 int fno_ctrl_stats_update(const FnoCtrlStats* table, int nfields, long long count, void* stream);
+
+/* ----------------------------------------------------------------------
+ * optimal-observer policy (run_control.py:186-224): Adam on the upper-wall action through the full-field observer.  Per
+ * environment b, S = std + eps (float64 wall-plane statistics), a (batch, plane) the float32 action, P predicted planes:
+ *   fno_ctrl_action_begin: a = (float)opV2_0; x[b * x_batch_stride + i] = (float)(((double)a - mean[i]) / S[i]): the leaf and the
+ *     first observer input, one rounding each.
+ *   fno_ctrl_action_objective: field = (double)y * S + mean over y (batch, P, plane); nf = sqrt(sum field^2), na = sqrt(sum a^2);
+ *     parts[b] = {nf + reg * na, nf, na}; dy = (float)(field / nf * S) (0 where nf == 0).  Two launches, two passes over y: a
+ *     workgroup per 1024 points leaves two partial sums in `ws` (fno_ctrl_action_workspace_bytes, exactly; 0 for a bad shape),
+ *     then every workgroup adds its environment's partials in one fixed order.  Run-to-run and batch-position invariant.
+ *   fno_ctrl_action_update: g = (float)((double)dx / S + reg * (double)a / na) (second term 0 where na == 0; na = parts[b][2]),
+ *     one Adam step on (a, g) in fp32 with fno_adam_step's arithmetic (no weight decay; bias corrections of `step` formed on the
+ *     host in double, fno_adam_scalars), and x = (float)(((double)a - mean) / S) for the next epoch, in one pass.  step == 1
+ *     initialises exp_avg / exp_avg_sq without reading them.
+ *   fno_ctrl_action_finish: opV2[b][i] = (double)a[b][i] - mean over the plane of (double)a[b]; the mean is a fixed-order sum
+ *     inside one workgroup.
+ * No allocation, no synchronisation, no atomics: every call can be captured into a graph.
+ * ---------------------------------------------------------------------- */
+size_t fno_ctrl_action_workspace_bytes(int batch, int planes, size_t plane);
+int fno_ctrl_action_begin(int batch, size_t plane, const double* opV2_0, const double* mean, const double* std_, double eps,
+                          float* a, float* x, size_t x_batch_stride, void* stream);
+int fno_ctrl_action_objective(int batch, int planes, size_t plane, const float* y, const float* a, const double* mean,
+                              const double* std_, double eps, double reg, double* parts, float* dy, void* ws, size_t ws_bytes,
+                              void* stream);
+int fno_ctrl_action_update(int batch, size_t plane, const float* dx, const double* parts, const double* mean, const double* std_,
+                           double eps, double reg, double lr, double beta1, double beta2, double adam_eps, int step, float* a,
+                           float* exp_avg, float* exp_avg_sq, float* x, size_t x_batch_stride, void* stream);
+int fno_ctrl_action_finish(int batch, size_t plane, const float* a, double* opV2, void* stream);
 
 /* ----------------------------------------------------------------------
  * NSControlEnv2D (libs/envs/ns_control_2d.py): the 2-D periodic channel with wall blowing and suction, float64.  Arrays are

@@ -156,6 +156,7 @@ def lib():
     L.fno_lifting_workspace_bytes.restype = sz
     L.fno_lifting_forward.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp, vp]
     L.fno_lifting_backward.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp, vp, sz, vp]
+    L.fno_lifting_backward_dx.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp]
     L.fno_rno_gate_partials.restype = ci
     L.fno_rno_reset_gate_forward.argtypes = [sz] + [vp] * 7
     L.fno_rno_reset_gate_backward.argtypes = [sz] + [vp] * 7
@@ -183,6 +184,12 @@ def lib():
     L.fno_chanflow_diagnostics2_workspace_bytes.restype = sz
     L.fno_chanflow_diagnostics2.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
     L.fno_ctrl_stats_update.argtypes = [C.POINTER(FnoCtrlStats), ci, C.c_longlong, vp]
+    L.fno_ctrl_action_workspace_bytes.argtypes = [ci, ci, sz]
+    L.fno_ctrl_action_workspace_bytes.restype = sz
+    L.fno_ctrl_action_begin.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, vp, sz, vp]
+    L.fno_ctrl_action_objective.argtypes = [ci, ci, sz, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
+    L.fno_ctrl_action_update.argtypes = [ci, sz, vp, vp, vp, vp] + [C.c_double] * 6 + [ci, vp, vp, vp, vp, sz, vp]
+    L.fno_ctrl_action_finish.argtypes = [ci, sz, vp, vp, vp]
     ng = C.POINTER(FnoNs2dGrid)
     L.fno_ns2d_solve.argtypes = [ng, ci] + [vp] * 9 + [ci, C.c_double, ci, ci, vp, vp]
     L.fno_ns2d_fixed_mass.argtypes = [ng, ci] + [vp] * 10 + [C.c_double, ci, ci, C.c_double, vp, vp]
@@ -231,7 +238,7 @@ EXPORTED_SYMBOLS = [
     "fno_pointwise_workspace_bytes", "fno_pointwise_forward", "fno_pointwise_backward",
     "fno_projection_workspace_bytes", "fno_projection_forward", "fno_projection_backward",
     "fno_projection_forward_act", "fno_projection_backward_act",
-    "fno_lifting_workspace_bytes", "fno_lifting_forward", "fno_lifting_backward",
+    "fno_lifting_workspace_bytes", "fno_lifting_forward", "fno_lifting_backward", "fno_lifting_backward_dx",
     "fno_rno_gate_partials", "fno_rno_reset_gate_forward", "fno_rno_reset_gate_backward",
     "fno_rno_output_gate_forward", "fno_rno_output_gate_backward",
     "fno_pino_loss_workspace_bytes", "fno_pino_loss_forward", "fno_pino_loss_backward",
@@ -240,7 +247,8 @@ EXPORTED_SYMBOLS = [
     "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",
     "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
     "fno_ctrl_encode", "fno_ctrl_decode", "fno_chanflow_diagnostics2_workspace_bytes", "fno_chanflow_diagnostics2",
-    "fno_ctrl_stats_update", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
+    "fno_ctrl_stats_update", "fno_ctrl_action_workspace_bytes", "fno_ctrl_action_begin", "fno_ctrl_action_objective",
+    "fno_ctrl_action_update", "fno_ctrl_action_finish", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
     "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
 ]
 

@@ -9,7 +9,8 @@ step) on the same state with the same dPdx; here the observation of iteration i 
 
 Policies map the observation p2 (B, Nx, Nz) float64 on the device to opV1, opV2 (B, Nx, Nz) float64 on the device:
 GtPolicy (opposition control), UnmanipulatedPolicy, FnoPolicy / RnoPolicy (a trained observer between the two bridges
-functional.ctrl_encode / ctrl_decode).  Collector writes the reference's dataset format (run_control.py:234-293)."""
+functional.ctrl_encode / ctrl_decode), OptimalObserverPolicy (Adam on the action itself through the full-field observer,
+functional.ctrl_action_*).  Collector writes the reference's dataset format (run_control.py:234-293)."""
 import os
 import queue
 import threading
@@ -83,6 +84,9 @@ class _ObserverPolicy(Policy):
     def bind(self, env):
         super().bind(env)
         dev, plane = env.device, env.Nx * env.Nz
+        # side effect on the caller's module: moved to the environment's device and left in eval().  OptimalObserverPolicy.bind
+        # goes one step further and freezes the parameters (requires_grad_(False)); a caller that trains the observer
+        # afterwards has to switch both back, and one that shares the module with other code should pass a copy.
         self.observer = self.observer.to(dev).eval()
         self.p_stats = (_stat(self.p_norm.mean, dev), _stat(self.p_norm.std, dev), float(self.p_norm.eps))
         self.v_stats = (_stat(self.v_norm.mean, dev), _stat(self.v_norm.std, dev), float(self.v_norm.eps))
@@ -135,6 +139,88 @@ class RnoPolicy(_ObserverPolicy):
         return self.observer(x, None)
 
 
+class OptimalObserverPolicy(Policy):
+    """The reference's `optimal-observer` (run_control.py:186-224): every control iteration starts from opposition control and
+    takes `epochs` Adam steps on the upper-wall action itself, descending
+        |decoded v-planes the full-field observer predicts from the action|_2 + reg_weight * |action|_2
+    through the trained PINObserverFullField down to its input; opV1 is opposition control as it is, opV2 the optimised action
+    minus its own plane mean.  Per environment b, S = std + eps:
+        a = float32(opV2_0), fresh Adam state; per epoch  x = float32((float64(a) - mean) / S),  y = observer(x, Re) in float32,
+        field = float64(y) * S + mean,  loss = |field| + reg |a| in float64,  g = float32(dL/dx / S + reg a / |a|),  Adam step.
+    The objective (functional.ctrl_action_objective) hands the observer's backward its output gradient dy directly
+    (torch.autograd.grad(y, x, dy)): no scalar torch loss is built, and everything around the observer is four engine kernels
+    on persistent tensors, so the whole iteration is captured by ControlLoop(graph=True) on one stream.
+    v_norm: the wall-plane normaliser the action is encoded with (FullFieldNSDataset.bound_v_norm); field_norm: the one the
+    predicted planes are decoded with (the dataset's v_field_norm is the same object; default v_norm).  re: default env.Re.
+    `losses`: the last iteration's (epochs, B, 3) device tensor, columns functional.ACTION_PARTS.
+    Departures from the reference: (1) its forward before the loop (`initial_loss`, :195-206) computes a value nothing uses and
+    is not run; the epoch-0 loss is what `losses[0]` holds.  (2) it calls torch.norm over the whole batch and its batch is 1;
+    here every environment of an ensemble has its own norms, loss and Adam state, so environment b of B solves the problem
+    its own B = 1 run solves.  (3) it leaves the observer's parameters collecting .grad that nothing reads; bind() puts the
+    observer in eval() and freezes its parameters (requires_grad_(False)), so the backward skips the weight gradients it can.
+    (4) g is assembled in float64 and rounded once; the reference accumulates two float32 contributions.
+    The freeze of (3) is done in place on the module that was passed and is not undone: do not share one observer object
+    between this policy and anything that expects its parameters to require grad (another policy, a trainer) - hand this
+    policy its own copy (copy.deepcopy), or switch requires_grad back on afterwards.  model_timestep != 1 is refused by
+    make_policy and by the run plan."""
+    name, collects = "optimal-observer", False
+
+    def __init__(self, observer, v_norm, epochs=10, lr=1e-3, reg_weight=0.1, re=None, field_norm=None):
+        if int(epochs) < 1:
+            raise ValueError(f"OptimalObserverPolicy: epochs must be at least 1 (got {epochs})")
+        self.observer, self.v_norm, self.field_norm = observer, v_norm, v_norm if field_norm is None else field_norm
+        self.epochs, self.lr, self.reg, self.re = int(epochs), float(lr), float(reg_weight), re
+
+    def bind(self, env):
+        super().bind(env)
+        dev, B, plane = env.device, env.B, env.Nx * env.Nz
+        obs = self.observer
+        P = getattr(obs, "plane_num", None)
+        if getattr(obs, "in_dim", None) != 1 or not isinstance(P, int) or P < 1:
+            raise RuntimeError(f"OptimalObserverPolicy: the observer must take in_dim = 1 (the encoded wall plane) and return "
+                               f"plane_num planes, as PINObserverFullField does (got in_dim = {getattr(obs, 'in_dim', None)}, "
+                               f"plane_num = {P})")
+        self.observer = obs.to(dev).eval()       # (see _ObserverPolicy.bind) and frozen: the loop differentiates to the input only
+        for prm in self.observer.parameters():
+            prm.requires_grad_(False)
+        self.v_stats = (_stat(self.v_norm.mean, dev), _stat(self.v_norm.std, dev), float(self.v_norm.eps))
+        self.f_stats = (_stat(self.field_norm.mean, dev), _stat(self.field_norm.std, dev), float(self.field_norm.eps))
+        for n, s in (("wall-plane", self.v_stats), ("field", self.f_stats)):
+            if s[0].numel() != plane or s[1].numel() != plane:
+                raise RuntimeError(f"OptimalObserverPolicy: the {n} statistics have {s[0].numel()} / {s[1].numel()} points, the "
+                                   f"controlled plane {env.Nx} x {env.Nz} = {plane}")
+        f32 = lambda *shp: torch.zeros(shp, dtype=torch.float32, device=dev)      # noqa: E731
+        self.P = P
+        self.a, self.exp_avg, self.exp_avg_sq = f32(B, plane), f32(B, plane), f32(B, plane)
+        self.x = f32(B, env.Nx, env.Nz, 1, 1).requires_grad_(True)                 # the persistent observer input: a leaf
+        self.dy = f32(B, P, plane)
+        self.start = torch.zeros((B, env.Nx, env.Nz), dtype=torch.float64, device=dev)
+        self.losses = torch.zeros((self.epochs, B, len(F.ACTION_PARTS)), dtype=torch.float64, device=dev)
+        self.ws = F.ctrl_action_workspace(B, P, plane, dev)
+        self.re_t = torch.full((B,), float(env.Re if self.re is None else self.re), dtype=torch.float32, device=dev)
+        return self
+
+    def act(self, p2):
+        env = self.env
+        B, plane = env.B, env.Nx * env.Nz
+        d = env.detect_plane
+        torch.neg(env.V[:, :, d, :], out=self.opV1)
+        torch.neg(env.V[:, :, -d, :], out=self.start)
+        mean, std, eps = self.v_stats
+        F.ctrl_action_begin(self.start, mean, std, eps, self.a, self.x)
+        with torch.enable_grad():
+            for k in range(self.epochs):
+                y = self.observer(self.x, self.re_t)
+                if y.numel() != B * self.P * plane:
+                    raise RuntimeError(f"OptimalObserverPolicy: the observer returned {tuple(y.shape)} for {B} x {self.P} planes of {plane}")
+                F.ctrl_action_objective(y.detach(), self.a, *self.f_stats, reg=self.reg, parts=self.losses[k], dy=self.dy, ws=self.ws)
+                (dx,) = torch.autograd.grad(y, self.x, self.dy.view(y.shape))
+                F.ctrl_action_update(dx, self.losses[k], mean, std, eps, self.a, self.exp_avg, self.exp_avg_sq, self.x, k + 1,
+                                     reg=self.reg, lr=self.lr)
+        F.ctrl_action_finish(self.a, out=self.opV2)
+        return self.opV1, self.opV2
+
+
 def make_policy(policy_name, **kw):
     """the policy of a reference `policy_name` (run_control.py:135-226)"""
     if policy_name == "gt":
@@ -146,7 +232,18 @@ def make_policy(policy_name, **kw):
         return cls(kw["observer"], kw["p_norm"], kw["v_norm"], kw.get("zero_mean", False), kw.get("scale", 1.0), kw.get("clip", 0.0))
     if policy_name == "rand":
         raise NotImplementedError("policy `rand`: the reference's rand_control is a MATLAB call (compute_opposition)")
-    if policy_name in ("optimal-observer", "optimal-policy-observer"):
+    if policy_name == "optimal-observer":
+        if kw.get("observer") is None or kw.get("v_norm") is None:
+            raise NotImplementedError("policy `optimal-observer` optimises the action through a trained full-field observer: pass "
+                                      "observer=<a PINObserverFullField with in_dim = 1> and v_norm=<the wall-plane normaliser, "
+                                      "FullFieldNSDataset.bound_v_norm> (run_control: model_name: PINObserverFullField, "
+                                      "load_model_name and DATA_FOLDER of a full-field dataset); the bare name cannot build it")
+        if int(kw.get("model_timestep", 1)) != 1:
+            raise NotImplementedError(f"policy `optimal-observer` with model_timestep = {kw['model_timestep']}: it optimises one wall "
+                                      "plane through an observer of one time step (model_timestep = 1)")
+        opt = {k: kw[k] for k in ("epochs", "lr", "reg_weight", "re", "field_norm") if k in kw}
+        return OptimalObserverPolicy(kw["observer"], kw["v_norm"], **opt)
+    if policy_name == "optimal-policy-observer":
         raise NotImplementedError(f"policy `{policy_name}` optimises through the PINO full-field observer; it is outside this loop")
     raise RuntimeError("Not supported policy name.")
 

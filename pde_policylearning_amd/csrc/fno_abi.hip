@@ -19,6 +19,7 @@
 #include "k_chanflow.h"
 #include "k_chanflow_step.h"
 #include "k_control_loop.h"
+#include "k_action_opt.h"
 #include "k_ns2d.h"
 #include "k_pointwise.h"
 #include "k_block_fwd2.h"
@@ -2700,6 +2701,82 @@ extern "C" int fno_ctrl_stats_update(const FnoCtrlStats* tab, int nfields, long 
 }
 
 // ===========================================================================
+// optimal-observer policy (run_control.py:186-224): the objective and the Adam step on the wall action (k_action_opt.h)
+// ===========================================================================
+static int act_check(const char* who, int B, size_t plane, size_t stride, const double* mean, const double* std_, double eps) {
+  LAUNCHCHK(ctrl_plane_check(who, B, plane, stride));
+  if (!mean || !std_) return fail(FNO_EINVAL, "%s: null statistics", who);
+  if (((uintptr_t)mean | (uintptr_t)std_) & 7) return fail(FNO_EINVAL, "%s: misaligned statistics", who);
+  if (!std::isfinite(eps)) return fail(FNO_EINVAL, "%s: eps must be finite", who);
+  return FNO_OK;
+}
+static int act_obj_chunks(int B, int P, size_t plane, size_t* nchunk) {
+  LAUNCHCHK(ctrl_plane_check("fno_ctrl_action_objective", B, plane, plane));
+  if (P < 1 || P > 64) return fail(FNO_EINVAL, "fno_ctrl_action_objective: 1..64 predicted planes (got %d)", P);
+  if ((size_t)P * plane > 0x3fffffffull) return fail(FNO_EINVAL, "fno_ctrl_action_objective: %d planes of %zu points", P, plane);
+  *nchunk = ((size_t)P * plane + kActChunk - 1) / kActChunk;
+  return FNO_OK;
+}
+extern "C" size_t fno_ctrl_action_workspace_bytes(int B, int P, size_t plane) {
+  size_t nchunk;
+  if (act_obj_chunks(B, P, plane, &nchunk) != FNO_OK) return 0;
+  return (size_t)B * nchunk * 2 * sizeof(double);
+}
+extern "C" int fno_ctrl_action_begin(int B, size_t plane, const double* opV2_0, const double* mean, const double* std_, double eps,
+                                     float* a, float* x, size_t x_batch_stride, void* stream) {
+  LAUNCHCHK(act_check("fno_ctrl_action_begin", B, plane, x_batch_stride, mean, std_, eps));
+  if (!opV2_0 || !a || !x) return fail(FNO_EINVAL, "fno_ctrl_action_begin: null argument");
+  if (((uintptr_t)opV2_0 & 7) || (((uintptr_t)a | (uintptr_t)x) & 3)) return fail(FNO_EINVAL, "fno_ctrl_action_begin: misaligned tensor");
+  return launch("k_act_begin", k_act_begin, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, plane, opV2_0,
+                ActStats{mean, std_, eps}, a, x, x_batch_stride);
+}
+extern "C" int fno_ctrl_action_objective(int B, int P, size_t plane, const float* y, const float* a, const double* mean,
+                                         const double* std_, double eps, double reg, double* parts, float* dy, void* ws,
+                                         size_t ws_bytes, void* stream) {
+  size_t nchunk;
+  LAUNCHCHK(act_obj_chunks(B, P, plane, &nchunk));
+  LAUNCHCHK(act_check("fno_ctrl_action_objective", B, plane, plane, mean, std_, eps));
+  if (!y || !a || !parts || !dy || !ws) return fail(FNO_EINVAL, "fno_ctrl_action_objective: null argument");
+  if ((((uintptr_t)y | (uintptr_t)a | (uintptr_t)dy) & 3) || (((uintptr_t)parts | (uintptr_t)ws) & 7))
+    return fail(FNO_EINVAL, "fno_ctrl_action_objective: misaligned tensor");
+  if (!std::isfinite(reg)) return fail(FNO_EINVAL, "fno_ctrl_action_objective: reg must be finite");
+  if (ws_bytes != (size_t)B * nchunk * 2 * sizeof(double))
+    return fail(FNO_EINVAL, "fno_ctrl_action_objective: workspace of %zu bytes does not belong to batch %d, %d planes of %zu (needs %zu)",
+                ws_bytes, B, P, plane, (size_t)B * nchunk * 2 * sizeof(double));
+  ActObjArgs o;
+  o.y = y; o.a = a; o.s = ActStats{mean, std_, eps}; o.plane = plane; o.total = (size_t)P * plane; o.nchunk = (int)nchunk; o.reg = reg;
+  o.ws = (double*)ws; o.parts = parts; o.dy = dy;
+  LAUNCHCHK(launch("k_act_obj_part", k_act_obj_part, dim3((unsigned)nchunk, B), dim3(256), 0, (hipStream_t)stream, o));
+  return launch("k_act_obj_dy", k_act_obj_dy, dim3((unsigned)nchunk, B), dim3(256), 0, (hipStream_t)stream, o);
+}
+extern "C" int fno_ctrl_action_update(int B, size_t plane, const float* dx, const double* parts, const double* mean,
+                                      const double* std_, double eps, double reg, double lr, double beta1, double beta2,
+                                      double adam_eps, int step, float* a, float* exp_avg, float* exp_avg_sq, float* x,
+                                      size_t x_batch_stride, void* stream) {
+  LAUNCHCHK(act_check("fno_ctrl_action_update", B, plane, x_batch_stride, mean, std_, eps));
+  if (step < 1) return fail(FNO_EINVAL, "fno_ctrl_action_update: step must be >= 1 (got %d)", step);
+  if (!dx || !parts || !a || !exp_avg || !exp_avg_sq || !x) return fail(FNO_EINVAL, "fno_ctrl_action_update: null argument");
+  if ((((uintptr_t)dx | (uintptr_t)a | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)x) & 3) || ((uintptr_t)parts & 7))
+    return fail(FNO_EINVAL, "fno_ctrl_action_update: misaligned tensor");
+  if (!std::isfinite(reg) || !std::isfinite(lr) || !(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(adam_eps >= 0))
+    return fail(FNO_EINVAL, "fno_ctrl_action_update: need finite reg and lr, betas in [0, 1) and eps >= 0");
+  const AdamHyper h = adam_hyper(lr, beta1, beta2, adam_eps, 0.0);
+  float sc[2];
+  fno_adam_scalars(lr, beta1, beta2, step, sc);
+  ActUpdateArgs u;
+  u.dx = dx; u.parts = parts; u.s = ActStats{mean, std_, eps}; u.plane = plane; u.x_stride = x_batch_stride; u.reg = reg;
+  u.beta2 = h.beta2; u.eps = h.eps; u.step_size = sc[0]; u.bc2_sqrt = sc[1]; u.omb1 = h.omb1; u.omb2 = h.omb2;
+  u.first = step == 1; u.a = a; u.m = exp_avg; u.v = exp_avg_sq; u.x = x;
+  return launch("k_act_update", k_act_update, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, u);
+}
+extern "C" int fno_ctrl_action_finish(int B, size_t plane, const float* a, double* opV2, void* stream) {
+  LAUNCHCHK(ctrl_plane_check("fno_ctrl_action_finish", B, plane, plane));
+  if (!a || !opV2) return fail(FNO_EINVAL, "fno_ctrl_action_finish: null argument");
+  if (((uintptr_t)a & 3) || ((uintptr_t)opV2 & 7)) return fail(FNO_EINVAL, "fno_ctrl_action_finish: misaligned tensor");
+  return launch("k_act_finish", k_act_finish, dim3(B), dim3(256), 0, (hipStream_t)stream, plane, a, opV2);
+}
+
+// ===========================================================================
 // RNO cell gates (neuralop/models/rno.py:254-260)
 // ===========================================================================
 static const int kGateGrid = 2048;
@@ -2991,4 +3068,13 @@ extern "C" int fno_lifting_backward(int B, int Cin, int C, size_t PW, const floa
   jobs.add(a.dwl_part, dw, grid, C, Cin, 16, Cin);
   if (dbias) jobs.add(a.dwl_part + Cin, dbias, grid, C, 1, 16, 1);
   return jobs.run(st);
+}
+// dx[b][k][px] = sum_c w[c][k] dy[b][c][px], channels ascending: the lifting's adjoint on its own (k_lift_dx, k_block_bwd.h)
+extern "C" int fno_lifting_backward_dx(int B, int Cin, int C, size_t PW, const float* dy, const float* w, float* dx, void* stream) {
+  LAUNCHCHK(lift_check(B, Cin, C, PW));
+  if (!dy || !w || !dx) return fail(FNO_EINVAL, "fno_lifting_backward_dx: null argument");
+  if ((((uintptr_t)dy | (uintptr_t)dx) & 15) || ((uintptr_t)w & 3)) return fail(FNO_EINVAL, "fno_lifting_backward_dx: misaligned tensor");
+  const size_t n4 = (size_t)B * PW / 4;
+  return launch("k_lift_dx", k_lift_dx, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, w,
+                dx, C, Cin, PW, n4);
 }

@@ -1329,6 +1329,122 @@ def running_stats_update(fields, means, m2s, count):
 
 
 # ----------------------------------------------------------------------------
+# optimal-observer policy (run_control.py:186-224): the objective and the Adam step on the wall action (k_action_opt.h)
+# ----------------------------------------------------------------------------
+ACTION_PARTS = ("loss", "field_norm", "action_norm")      # columns of ctrl_action_objective's `parts`
+
+
+def _action_rows(e, name, t, anchor, B, plane):
+    """a float32 tensor of B planes that the engine updates in place (the action, its two Adam moments)"""
+    return _operand(e, name, t, anchor, dtype=torch.float32, numel=B * plane, layout="dense")
+
+
+def ctrl_action_begin(opV2_0, mean, std, eps, a, x, batch_stride=None):
+    """a[b] = float32(opV2_0[b]) and x[b * batch_stride + i] = float32((float64(a[b, i]) - mean[i]) / (std[i] + eps)): the leaf
+    of the optimal-observer policy and its first observer input, in one launch.  opV2_0 (B, Nx, Nz) float64; a float32 with
+    B * Nx * Nz elements and x the dense float32 observer input, both written in place."""
+    e = "ctrl_action_begin"
+    _gpu_anchor(e, "opV2_0", opV2_0)
+    if opV2_0.dim() < 2:
+        raise _refuse(e, "opV2_0", "be (B, Nx, Nz)", tuple(opV2_0.shape))
+    B, plane = opV2_0.shape[0], opV2_0[0].numel()
+    v0 = _operand(e, "opV2_0", opV2_0, opV2_0, dtype=torch.float64)
+    mean, std = _plane_stats(e, mean, std, v0, plane)
+    a = _action_rows(e, "a", a, v0, B, plane)
+    stride = plane if batch_stride is None else int(batch_stride)
+    x = _strided_rows(e, "x", x, v0, B, plane, stride)
+    _call(e, v0.device, "fno_ctrl_action_begin", B, plane, v0, mean, std, float(eps), a, x, stride, STREAM)
+    return a, x
+
+
+def ctrl_action_workspace(B, planes, plane, device):
+    """the partial-sum workspace of ctrl_action_objective for B environments, `planes` predicted planes of `plane` points"""
+    n = _lib.lib().fno_ctrl_action_workspace_bytes(int(B), int(planes), int(plane))
+    if n == 0:
+        raise RuntimeError("fnoengine ctrl_action_objective: " + _lib.lib().fno_last_error().decode("utf-8", "replace"))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def ctrl_action_objective(y, a, mean, std, eps=1e-5, reg=0.1, parts=None, dy=None, ws=None):
+    """The optimal-observer objective of every environment and its gradient with respect to the observer's output:
+    field = float64(y) * (std + eps) + mean, parts[b] = (nf + reg * na, nf, na) with nf = |field[b]|_2 over all predicted
+    planes and na = |float64(a[b])|_2 (columns ACTION_PARTS, float64), dy = float32(field / nf * (std + eps)), zero where
+    nf == 0.  y (B, P, Nx, Nz[, 1]) float32, a (B, Nx * Nz) float32.  Fixed-order float64 sums in two launches: the same bits
+    run to run and at every batch position.  `ws`: ctrl_action_workspace of this shape.  Returns (parts, dy)."""
+    e = "ctrl_action_objective"
+    _gpu_anchor(e, "y", y)
+    if not torch.is_tensor(a) or a.dim() < 2 or y.dim() < 3 or a.shape[0] != y.shape[0]:
+        raise _refuse(e, "a", "be (B, Nx * Nz) beside y (B, P, Nx, Nz)", getattr(a, "shape", type(a).__name__))
+    B, plane = a.shape[0], a[0].numel()
+    P = y.shape[1]
+    y = _operand(e, "y", y, y, dtype=torch.float32, numel=B * P * plane)
+    a = _operand(e, "a", a, y, dtype=torch.float32)
+    mean, std = _plane_stats(e, mean, std, y, plane)
+    if parts is None:
+        parts = torch.empty((B, len(ACTION_PARTS)), dtype=torch.float64, device=y.device)
+    parts = _operand(e, "parts", parts, y, dtype=torch.float64, shape=(B, len(ACTION_PARTS)), layout="dense")
+    if dy is None:
+        dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    dy = _operand(e, "dy", dy, y, dtype=torch.float32, numel=y.numel(), layout="dense")
+    need = _lib.lib().fno_ctrl_action_workspace_bytes(B, P, plane)
+    if ws is None:
+        ws = ctrl_action_workspace(B, P, plane, y.device)
+    ws = _operand(e, "workspace", ws, y, dtype=torch.uint8, layout="dense")
+    if ws.numel() != need:
+        raise _refuse(e, "workspace", f"be the {need} bytes of a batch of {B} with {P} planes of {plane}", f"{ws.numel()} bytes")
+    _call(e, y.device, "fno_ctrl_action_objective", B, P, plane, y, a, mean, std, float(eps), float(reg), parts, dy, ws, ws.numel(),
+          STREAM)
+    return parts, dy
+
+
+def ctrl_action_update(dx, parts, mean, std, eps, a, exp_avg, exp_avg_sq, x, step, reg=0.1, lr=1e-3, betas=(0.9, 0.999),
+                       adam_eps=1e-8, batch_stride=None):
+    """One epoch's update of the optimal-observer action, in one launch and in place: g = float32(float64(dx) / (std + eps) +
+    reg * float64(a) / na) with na = parts[:, 2] (the regulariser's term is zero where na == 0), torch.optim.Adam's float32 step
+    number `step` on (a, g) (no weight decay, no amsgrad; step 1 initialises exp_avg / exp_avg_sq without reading them), and
+    x = float32((float64(a) - mean) / (std + eps)), the observer input of the next epoch.  dx: the observer's input gradient
+    (B, Nx * Nz) float32."""
+    e = "ctrl_action_update"
+    _gpu_anchor(e, "dx", dx)
+    if not torch.is_tensor(parts) or parts.dim() != 2:
+        raise _refuse(e, "parts", "be the (B, 3) float64 tensor of ctrl_action_objective", getattr(parts, "shape", type(parts).__name__))
+    if int(step) < 1:
+        raise _refuse(e, "step", "be the number of this Adam step (>= 1)", step)
+    B = parts.shape[0]
+    plane = dx.numel() // max(B, 1)
+    dx = _operand(e, "dx", dx, dx, dtype=torch.float32, numel=B * plane)
+    parts = _operand(e, "parts", parts, dx, dtype=torch.float64, shape=(B, len(ACTION_PARTS)))
+    mean, std = _plane_stats(e, mean, std, dx, plane)
+    a, m, v = (_action_rows(e, n, t, dx, B, plane) for n, t in (("a", a), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)))
+    stride = plane if batch_stride is None else int(batch_stride)
+    x = _strided_rows(e, "x", x, dx, B, plane, stride)
+    _call(e, dx.device, "fno_ctrl_action_update", B, plane, dx, parts, mean, std, float(eps), float(reg), float(lr), float(betas[0]),
+          float(betas[1]), float(adam_eps), int(step), a, m, v, x, stride, STREAM)
+    return a
+
+
+def ctrl_action_finish(a, out=None, shape=None):
+    """opV2 (B, Nx, Nz) float64 = float64(a) minus each environment's own plane mean (run_control.py:223); the mean is a
+    fixed-order sum inside one workgroup.  `shape` = (B, Nx, Nz) unless `out` gives it."""
+    e = "ctrl_action_finish"
+    _gpu_anchor(e, "a", a)
+    if out is not None:
+        shape = tuple(out.shape)
+    if shape is None:
+        shape = tuple(a.shape)
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 2:
+        raise _refuse(e, "shape", "be (B, Nx, Nz)", shape)
+    B, plane = shape[0], math.prod(shape[1:])
+    a = _operand(e, "a", a, a, dtype=torch.float32, numel=B * plane)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=a.device)
+    out = _operand(e, "opV2", out, a, dtype=torch.float64, shape=shape, layout="dense")
+    _call(e, a.device, "fno_ctrl_action_finish", B, plane, a, out, STREAM)
+    return out
+
+
+# ----------------------------------------------------------------------------
 # NSControlEnv2D: the 2-D periodic channel (libs/envs/ns_control_2d.py), float64, one workgroup per environment
 # ----------------------------------------------------------------------------
 NS2D_SOLVE_OUT = ("bulk_v", "steps", "status")
@@ -1618,13 +1734,20 @@ def lifting_supported(x, c_out):
 def _lifting_operands(e, x, w, bias, per_sample):
     """-> x contiguous, (B, cin, cout, pw), w (cout, cin), bias (None allowed unless per_sample)"""
     _require_cuda(x, "x")
-    if x.requires_grad:
-        raise RuntimeError("fnoengine lifting: the input field is data (no gradient is produced for it)")
     x = x.contiguous()
     B, cin, cout = x.shape[0], x.shape[1], w.shape[0]
     wc = _operand(e, "w", w, x, numel=cout * cin).reshape(cout, cin)
     bc = _operand(e, "bias", bias, x, shape=(B, cout)) if per_sample else _operand(e, "bias", bias, x, numel=cout, optional=True)
     return x, (B, cin, cout, x.numel() // (B * cin)), wc, bc
+
+
+def _lifting_dx(ctx, x, wc, dy, B, cin, cout, pw):
+    """dL/dx of a lifting when the input asks for it (fno_lifting_backward_dx: channels summed in ascending order), else None"""
+    if not ctx.needs_input_grad[0]:
+        return None
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _call("lifting_backward_dx", x.device, "fno_lifting_backward_dx", B, cin, cout, pw, dy, wc, dx, STREAM)
+    return dx
 
 
 class _LiftingPerSampleFn(torch.autograd.Function):
@@ -1636,15 +1759,18 @@ class _LiftingPerSampleFn(torch.autograd.Function):
         y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         for b in range(B):
             _call("lifting_forward", x.device, "fno_lifting_forward", 1, cin, cout, pw, x[b], wc, bc[b], y[b], STREAM)
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, wc)
         ctx.meta = (B, cin, cout, pw, w.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, wc = ctx.saved_tensors
         B, cin, cout, pw, wshape = ctx.meta
         dy = _operand("lifting_per_sample_bias backward", "dy", dy, x, numel=B * cout * pw)
+        dx = _lifting_dx(ctx, x, wc, dy, B, cin, cout, pw)
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return dx, None, None
         dws = torch.empty((B, cout, cin), dtype=torch.float32, device=x.device)
         dbs = torch.empty((B, cout), dtype=torch.float32, device=x.device)
         nws = _lib.lib().fno_lifting_workspace_bytes(cout)
@@ -1652,11 +1778,11 @@ class _LiftingPerSampleFn(torch.autograd.Function):
         for b in range(B):
             _call("lifting_backward", x.device, "fno_lifting_backward", 1, cin, cout, pw, x[b], dy[b], dws[b], dbs[b], ws, nws,
                   STREAM)
-        return None, dws.sum(0).view(wshape), dbs
+        return dx, dws.sum(0).view(wshape), dbs
 
 
 def lifting_per_sample_bias(x, w, bias):
-    """y[b] = conv1x1(x[b]; w) + bias[b]: x (B, Cin <= 4, ...) data, w (C, Cin), bias (B, C)."""
+    """y[b] = conv1x1(x[b]; w) + bias[b]: x (B, Cin <= 4, ...), w (C, Cin), bias (B, C).  dL/dx is produced when x asks for it."""
     return _LiftingPerSampleFn.apply(x, w, bias)
 
 
@@ -1666,25 +1792,29 @@ class _LiftingFn(torch.autograd.Function):
         x, (B, cin, cout, pw), wc, bc = _lifting_operands("lifting", x, w, bias, False)
         y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         _call("lifting_forward", x.device, "fno_lifting_forward", B, cin, cout, pw, x, wc, bc, y, STREAM)
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, wc)
         ctx.meta = (B, cin, cout, pw, w.shape, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, wc = ctx.saved_tensors
         B, cin, cout, pw, wshape, has_b = ctx.meta
         dy = _operand("lifting backward", "dy", dy, x, numel=B * cout * pw)
+        dx = _lifting_dx(ctx, x, wc, dy, B, cin, cout, pw)
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):      # frozen parameters: only the input gradient is formed
+            return dx, None, None
         dw = torch.empty(cout, cin, dtype=torch.float32, device=x.device)
         db = torch.empty(cout, dtype=torch.float32, device=x.device) if has_b else None
         nws = _lib.lib().fno_lifting_workspace_bytes(cout)
         ws = _bytes(nws, x.device)
         _call("lifting_backward", x.device, "fno_lifting_backward", B, cin, cout, pw, x, dy, dw, db, ws, nws, STREAM)
-        return None, dw.view(wshape), db
+        return dx, dw.view(wshape), db
 
 
 def lifting(x, w, bias=None):
-    """conv1x1 from <= 4 input channels: x (B, Cin, ...) data, w (C, Cin[, 1..]), bias (C)."""
+    """conv1x1 from <= 4 input channels: x (B, Cin, ...), w (C, Cin[, 1..]), bias (C).  dL/dx = W^T dL/dy is produced when x
+    asks for it (the optimal-observer policy differentiates an observer down to its input field)."""
     return _LiftingFn.apply(x, w, bias)
 
 

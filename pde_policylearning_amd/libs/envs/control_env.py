@@ -27,6 +27,7 @@ class ChannelFlowRHS:
         y, ym = np.asarray(y, dtype=np.float64).reshape(-1), np.asarray(ym, dtype=np.float64).reshape(-1)
         if yg is None:
             yg = np.concatenate(([-ym[0]], ym, [2 + ym[0]]))                 # :165
+        self.Re = float(Re)                     # :25 (what the optimal-observer policy conditions its observer on)
         self.nu = self.default_nu * (self.default_re / Re) if Re > 0 else self.default_nu      # :26-29
         self.dPdx = self.default_dPdx if dPdx is None else float(dPdx)
         self.Nx, self.Ny, self.Nz = int(Nx), int(y.shape[0]), int(Nz)

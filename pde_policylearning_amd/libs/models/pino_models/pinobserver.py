@@ -55,9 +55,10 @@ class MultiplicativeNet(nn.Module):
 def _lift_front(fc0, mn, x, re, width):
     """multiplicative_net1(fc0(x), re) as a channels-first tensor (pinobserver.py:205-207, 356-358).  fc0 followed by the
     Re-conditioning affine is ONE linear map of the <= 4 input channels: when the shape allows it the two small matrices are
-    composed (autograd differentiates the composition) and applied by the engine's lifting kernels."""
+    composed (autograd differentiates the composition) and applied by the engine's lifting kernels; an input that asks for
+    its gradient gets it from them too (functional.lifting)."""
     xc = x.permute(0, 4, 1, 2, 3)
-    if not x.requires_grad and F.lifting_supported(xc, width):
+    if F.lifting_supported(xc, width):
         w = mn.B @ fc0.weight                                             # (C, in_dim)
         bias = mn.B @ fc0.bias + mn.bias
         code = (re if re.dim() >= 2 else re.unsqueeze(-1)) @ mn.A.t()     # (B, C)

@@ -4,10 +4,12 @@
 
 The reference's YAMLs drop in: the file is merged over the flags exactly as train_observer does (yaml.safe_load, the YAML's keys
 win).  Keys read: policy_name, model_name, load_model_name, modes, width, x_range, y_range, control_timestep, detect_plane,
-noise_scale, collect_data, DATA_FOLDER, state_path_name, output_dir, exp_name, Re; visualisation and W&B keys are carried in the
-plan and ignored.  The loop runs control_timestep + 1 iterations (run_control.py:133).  --ensemble B steps B environments under
-one policy (each with its own noise draw when noise_scale > 0), --graph replays the iteration as one graph, --tanh-channel starts
-from an analytic state on a tanh grid when there is no `.mat` initial condition."""
+noise_scale, collect_data, DATA_FOLDER, state_path_name, output_dir, exp_name, Re, model_timestep; visualisation and W&B keys
+are carried in the plan and ignored.  policy_name: optimal-observer needs model_name: PINObserverFullField, load_model_name and the
+DATA_FOLDER of a full-field dataset (its wall-plane statistics normalise the action: FullFieldNSDataset.bound_v_norm).  The
+loop runs control_timestep + 1 iterations (run_control.py:133).  --ensemble B steps B environments under one policy (each with
+its own noise draw when noise_scale > 0), --graph replays the iteration as one graph, --tanh-channel starts from an analytic
+state on a tanh grid when there is no `.mat` initial condition."""
 import argparse
 import os
 
@@ -24,7 +26,7 @@ _KEYS = ("policy_name", "model_name", "load_model_name", "modes", "width", "x_ra
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--control_yaml", "--control-yaml", dest="control_yaml", default=None, help="a reference YAML: its keys win over the flags")
-    ap.add_argument("--policy_name", default="gt", help="gt | unmanipulated | fno | rno")
+    ap.add_argument("--policy_name", default="gt", help="gt | unmanipulated | fno | rno | optimal-observer")
     ap.add_argument("--model_name", default="FNO2dObserver")
     ap.add_argument("--load_model_name", default=None, help="whole pickled module under output_dir (train_observer's save_if_best)")
     ap.add_argument("--modes", type=int, default=12)
@@ -64,16 +66,24 @@ def plan_from_yaml(args, yaml_dict=None):
         return _plan_ns2d(ns)
     if ns.env_name != "NSControlEnvMatlab":
         raise RuntimeError("Not supported environment!")                 # run_control.py:107
-    if ns.policy_name in ("rand", "optimal-observer", "optimal-policy-observer"):
+    if ns.policy_name in ("rand", "optimal-policy-observer") or (ns.policy_name == "optimal-observer"
+                                                                 and ns.model_name != "PINObserverFullField"):
         make_policy(ns.policy_name)                                      # raises NotImplementedError with the reason
-    if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno"):
+    if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno", "optimal-observer"):
         raise RuntimeError("Not supported policy name.")
+    if ns.policy_name == "optimal-observer":
+        if int(getattr(ns, "model_timestep", 1) or 1) != 1:
+            raise NotImplementedError(f"run_control: optimal-observer with model_timestep = {ns.model_timestep}; the policy "
+                                      "optimises one wall plane through an observer of one time step")
+        if not ns.DATA_FOLDER:
+            raise ValueError("run_control: optimal-observer needs DATA_FOLDER, the full-field dataset whose wall-plane statistics "
+                             "normalise the action")
     if ns.policy_name not in ("gt", "unmanipulated"):
         ns.collect_data = False                                          # run_control.py:45-46
     ns.steps = int(ns.control_timestep) + 1                              # :133
     ns.collect_folder = os.path.join(ns.output_dir, ns.exp_name) if ns.collect_data else None      # :112-114
     ns.ensemble = max(int(getattr(ns, "ensemble", 1)), 1)
-    if ns.policy_name in ("fno", "rno") and not ns.load_model_name:
+    if ns.policy_name in ("fno", "rno", "optimal-observer") and not ns.load_model_name:
         raise ValueError("run_control: a neural policy needs load_model_name (a model saved by train_observer)")
     if not ns.state_path_name and not getattr(ns, "tanh_channel", False):
         raise ValueError("run_control: no initial condition (state_path_name, or --tanh-channel)")
@@ -139,8 +149,11 @@ def make_env(plan, device="cuda"):
 def make_plan_policy(plan, device="cuda"):
     if plan.policy_name in ("gt", "unmanipulated"):
         return make_policy(plan.policy_name)
-    from .libs.pde_data_loader import PDEDataset
+    from .libs.pde_data_loader import FullFieldNSDataset, PDEDataset
     observer = torch.load(os.path.join(plan.output_dir, plan.load_model_name), map_location=device, weights_only=False)   # run_control.py:40
+    if plan.policy_name == "optimal-observer":
+        ds = FullFieldNSDataset(argparse.Namespace(model_timestep=1), plan.DATA_FOLDER, [0], [], 1, plan.x_range, plan.y_range)
+        return make_policy(plan.policy_name, observer=observer, v_norm=ds.bound_v_norm, field_norm=ds.v_field_norm)
     ds = PDEDataset(plan, plan.DATA_FOLDER, [0], 1, plan.x_range, plan.y_range)
     return make_policy(plan.policy_name, observer=observer, p_norm=ds.p_norm, v_norm=ds.v_norm)
 
