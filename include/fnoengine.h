@@ -509,6 +509,24 @@ int fno_ctrl_action_update(int batch, size_t plane, const float* dx, const doubl
 int fno_ctrl_action_finish(int batch, size_t plane, const float* a, double* opV2, void* stream);
 
 /* ----------------------------------------------------------------------
+ * optimal-policy-observer policy (run_control.py:162-185): a policy network maps the raw wall pressure to a correction `res`
+ * of the opposition-control action and is trained on line through the frozen full-field observer.  The glue between the two
+ * networks; every tensor is dense (batch, plane):
+ *   fno_ctrl_policy_begin: a0 = (float)opV2_0 and pin = (float)p2, one launch: the start action and the policy's input (the
+ *     RAW wall pressure, no normaliser).
+ *   fno_ctrl_policy_compose: x = a0 + res (one fp32 add) and opV2 = (double)x in the same pass: the observer's input and the
+ *     action the loop applies; what the last epoch leaves is the applied action, there is no finish kernel.
+ *   fno_ctrl_policy_grad: g = (float)((double)dx + reg * (double)x / na), na = parts[b][2] of fno_ctrl_action_objective
+ *     (g = dx where na == 0): dL/dres, assembled in fp64 and rounded once.
+ * The objective between compose and grad is fno_ctrl_action_objective with a := x and unit statistics (mean 0, std 1, eps 0).
+ * No allocation, no synchronisation, no atomics: every call can be captured into a graph.
+ * ---------------------------------------------------------------------- */
+int fno_ctrl_policy_begin(int batch, size_t plane, const double* opV2_0, const double* p2, float* a0, float* pin, void* stream);
+int fno_ctrl_policy_compose(int batch, size_t plane, const float* a0, const float* res, float* x, double* opV2, void* stream);
+int fno_ctrl_policy_grad(int batch, size_t plane, const float* dx, const float* x, const double* parts, double reg, float* g,
+                         void* stream);
+
+/* ----------------------------------------------------------------------
  * NSControlEnv2D (libs/envs/ns_control_2d.py): the 2-D periodic channel with wall blowing and suction, float64.  Arrays are
  * (batch, ny, nx), row = wall-normal index, column = streamwise index, periodic in x with all nx columns distinct; `batch`
  * independent environments, one workgroup each, the whole state in LDS for the whole launch.  3 <= ny, nx and

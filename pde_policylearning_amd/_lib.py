@@ -190,6 +190,9 @@ def lib():
     L.fno_ctrl_action_objective.argtypes = [ci, ci, sz, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
     L.fno_ctrl_action_update.argtypes = [ci, sz, vp, vp, vp, vp] + [C.c_double] * 6 + [ci, vp, vp, vp, vp, sz, vp]
     L.fno_ctrl_action_finish.argtypes = [ci, sz, vp, vp, vp]
+    L.fno_ctrl_policy_begin.argtypes = [ci, sz, vp, vp, vp, vp, vp]
+    L.fno_ctrl_policy_compose.argtypes = [ci, sz, vp, vp, vp, vp, vp]
+    L.fno_ctrl_policy_grad.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, vp]
     ng = C.POINTER(FnoNs2dGrid)
     L.fno_ns2d_solve.argtypes = [ng, ci] + [vp] * 9 + [ci, C.c_double, ci, ci, vp, vp]
     L.fno_ns2d_fixed_mass.argtypes = [ng, ci] + [vp] * 10 + [C.c_double, ci, ci, C.c_double, vp, vp]
@@ -248,7 +251,8 @@ EXPORTED_SYMBOLS = [
     "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
     "fno_ctrl_encode", "fno_ctrl_decode", "fno_chanflow_diagnostics2_workspace_bytes", "fno_chanflow_diagnostics2",
     "fno_ctrl_stats_update", "fno_ctrl_action_workspace_bytes", "fno_ctrl_action_begin", "fno_ctrl_action_objective",
-    "fno_ctrl_action_update", "fno_ctrl_action_finish", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
+    "fno_ctrl_action_update", "fno_ctrl_action_finish", "fno_ctrl_policy_begin", "fno_ctrl_policy_compose",
+    "fno_ctrl_policy_grad", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
     "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
 ]
 

@@ -10,7 +10,8 @@ step) on the same state with the same dPdx; here the observation of iteration i 
 Policies map the observation p2 (B, Nx, Nz) float64 on the device to opV1, opV2 (B, Nx, Nz) float64 on the device:
 GtPolicy (opposition control), UnmanipulatedPolicy, FnoPolicy / RnoPolicy (a trained observer between the two bridges
 functional.ctrl_encode / ctrl_decode), OptimalObserverPolicy (Adam on the action itself through the full-field observer,
-functional.ctrl_action_*).  Collector writes the reference's dataset format (run_control.py:234-293)."""
+functional.ctrl_action_*), PolicyObserverPolicy (a policy network trained on line through the same observer,
+functional.ctrl_policy_*).  Collector writes the reference's dataset format (run_control.py:234-293)."""
 import os
 import queue
 import threading
@@ -221,6 +222,118 @@ class OptimalObserverPolicy(Policy):
         return self.opV1, self.opV2
 
 
+class PolicyObserverPolicy(Policy):
+    """The reference's `optimal-policy-observer` (run_control.py:162-185): a neural policy (PolicyModel2D) maps the observed
+    RAW wall pressure to a correction of the opposition-control action and is trained on line, inside every control
+    iteration, by descending  |observer(action)|_2 + reg_weight * |action|_2  through the trained, frozen
+    PINObserverFullField.  opV1 is opposition control as it is.  Per control iteration:
+        begin():   opV1 = -V[detect], a0 = float32(-V[-detect]), pin = float32(p2) (functional.ctrl_policy_begin); the optimizer
+                   restarts (FusedAdam.reset_state: the reference builds a NEW Adam per iteration, so fresh moments and step
+                   count; the policy's parameters persist across iterations)
+        epoch(k):  res = policy(pin, Re);  x = a0 + res, opV2 = float64(x) (ctrl_policy_compose; x a persistent leaf)
+                   y = observer(x, Re): raw action in, raw planes out;  parts[k], dy = ctrl_policy_objective(y, x)
+                   dx = autograd.grad(y, x, dy);  g = float32(dx + reg x / |x|) = dL/dres (ctrl_policy_grad)
+                   zero the live gradients;  autograd.backward(res, g);  Adam step k + 1 (a host constant)
+    act(p2) = begin() then epoch(0 .. epochs - 1).  The applied opV2 is the x of the LAST FORWARD, i.e. under the parameters
+    after epochs - 1 steps (the reference's `opV2 = a0 + res` after its loop); the last step only shows in the next control
+    iteration; no plane mean is removed.  `losses`: the last iteration's (epochs, B, 3) device tensor, columns
+    functional.ACTION_PARTS.  re: default env.Re.
+    Ensemble: ONE policy network serves all B environments; the objective is the sum over the environments of each
+    environment's own nf_b + reg * na_b (the reference has B = 1 and one torch.norm), the parameter gradient the sum over b.
+    Unlike OptimalObserverPolicy, a member of an ensemble is therefore NOT its own B = 1 run: the members train one network.
+    Departures from the reference: (1) its forward pair before the loop computes a loss that is only printed and is not run
+    (as OptimalObserverPolicy's (1)); (2) bind() puts the observer in eval() and freezes its parameters in place - the
+    reference leaves them collecting .grad nothing reads; pass a copy if the module is shared (see OptimalObserverPolicy);
+    (3) g is assembled in float64 and rounded once; (4) the policy's parameters are re-pointed at one flat buffer
+    (FusedAdam), and the dead 11/12 of its spectral weights at T = 1 are neither stepped nor read in a control iteration.
+    Graph: Adam restarts at step 1 every iteration, so the step numbers are capture-time constants and ControlLoop(graph=True)
+    captures the whole iteration; state_tensors() names what the capture's eager warm-up must not leave changed."""
+    name, collects = "optimal-policy-observer", False
+
+    def __init__(self, policy_model, observer, epochs=3, lr=1e-4, reg_weight=0.1, re=None):
+        if int(epochs) < 1:
+            raise ValueError(f"PolicyObserverPolicy: epochs must be at least 1 (got {epochs})")
+        self.policy_model, self.observer = policy_model, observer
+        self.epochs, self.lr, self.reg, self.re = int(epochs), float(lr), float(reg_weight), re
+
+    def bind(self, env):
+        from .trainer import FlatGradBucket, FusedAdam
+        super().bind(env)
+        dev, B, plane = env.device, env.B, env.Nx * env.Nz
+        obs, pm = self.observer, self.policy_model
+        P = getattr(obs, "plane_num", None)
+        if getattr(obs, "in_dim", None) != 1 or not isinstance(P, int) or P < 1:
+            raise RuntimeError(f"PolicyObserverPolicy: the observer must take in_dim = 1 (the wall action) and return plane_num "
+                               f"planes, as PINObserverFullField does (got in_dim = {getattr(obs, 'in_dim', None)}, plane_num = {P})")
+        head = getattr(getattr(pm, "pred_net", None), "fc2", None)
+        if getattr(pm, "in_dim", None) != 1 or getattr(head, "out_features", None) != 1:
+            raise RuntimeError(f"PolicyObserverPolicy: the policy model must take in_dim = 1 (the wall pressure) and return one "
+                               f"channel, as PolicyModel2D(in_dim=1, out_dim=1) does (got in_dim = {getattr(pm, 'in_dim', None)}, "
+                               f"outputs = {getattr(head, 'out_features', None)})")
+        self.observer = obs.to(dev).eval()       # (see _ObserverPolicy.bind) and frozen: the loop differentiates to the input only
+        for prm in self.observer.parameters():
+            prm.requires_grad_(False)
+        self.policy_model = pm = pm.to(dev)
+        f32 = lambda *shp: torch.zeros(shp, dtype=torch.float32, device=dev)      # noqa: E731
+        self.P = P
+        self.a0, self.g = f32(B, plane), f32(B, plane)
+        self.pin = f32(B, env.Nx, env.Nz, 1, 1)
+        self.x = f32(B, env.Nx, env.Nz, 1, 1).requires_grad_(True)                 # the persistent observer input: a leaf
+        self.dy = f32(B, P, plane)
+        self.start = torch.zeros((B, env.Nx, env.Nz), dtype=torch.float64, device=dev)
+        self.losses = torch.zeros((self.epochs, B, len(F.ACTION_PARTS)), dtype=torch.float64, device=dev)
+        self.ws = F.ctrl_action_workspace(B, P, plane, dev)
+        self.unit = F.ctrl_policy_unit_stats(plane, dev)
+        self.re_t = torch.full((B,), float(env.Re if self.re is None else self.re), dtype=torch.float32, device=dev)
+        # the policy's optimizer as train_observer's full-field loop builds it: spectral-weight gradients written in place into
+        # one flat bucket, the dead last-dim slices of the spectral weights skipped.  The dead-slice plan is made HERE (one
+        # forward pass records the live extents) and not at the first step, so that state_tensors() names the final buffers
+        self.bucket = FlatGradBucket(pm.parameters(), direct_module=pm)
+        self.optimizer = FusedAdam(self.bucket, lr=self.lr, skip_dead_slices=True)
+        self.optimizer.plan_dead_slices(self.pin, self.re_t)
+        return self
+
+    def state_tensors(self):
+        """what a control iteration changes and the next one reads: the policy's parameters (one flat buffer) and Adam's
+        moments.  (The step count is a host number that begin() resets.)  ControlLoop hands them to GraphedControlLoop, which
+        restores them after its eager warm-up run, so the warm-up does not train the policy once too often."""
+        opt = self.optimizer
+        return [opt.flat_param, opt.exp_avg, opt.exp_avg_sq]
+
+    def begin(self, p2):
+        env = self.env
+        d = env.detect_plane
+        torch.neg(env.V[:, :, d, :], out=self.opV1)
+        torch.neg(env.V[:, :, -d, :], out=self.start)
+        F.ctrl_policy_begin(self.start, p2, self.a0, self.pin)
+        self.optimizer.reset_state()
+
+    def epoch(self, k):
+        B, plane = self.env.B, self.env.Nx * self.env.Nz
+        with torch.enable_grad():
+            res = self.policy_model(self.pin, self.re_t)
+            if res.numel() != B * plane:
+                raise RuntimeError(f"PolicyObserverPolicy: the policy model returned {tuple(res.shape)} for {B} planes of {plane}")
+            F.ctrl_policy_compose(self.a0, res.detach(), self.x, self.opV2)
+            y = self.observer(self.x, self.re_t)
+            if y.numel() != B * self.P * plane:
+                raise RuntimeError(f"PolicyObserverPolicy: the observer returned {tuple(y.shape)} for {B} x {self.P} planes of {plane}")
+            F.ctrl_policy_objective(y.detach(), self.x.detach(), reg=self.reg, parts=self.losses[k], dy=self.dy, ws=self.ws,
+                                    unit=self.unit)
+            (dx,) = torch.autograd.grad(y, self.x, self.dy.view(y.shape))
+            F.ctrl_policy_grad(dx, self.x.detach(), self.losses[k], reg=self.reg, out=self.g)
+            self.bucket.zero()
+            torch.autograd.backward(res, self.g.view(res.shape))
+        self.optimizer.step()
+        self.res, self.dx = res.detach(), dx      # (for inspection: the last forward's correction and the observer's input gradient)
+
+    def act(self, p2):
+        self.begin(p2)
+        for k in range(self.epochs):
+            self.epoch(k)
+        return self.opV1, self.opV2
+
+
 def make_policy(policy_name, **kw):
     """the policy of a reference `policy_name` (run_control.py:135-226)"""
     if policy_name == "gt":
@@ -244,7 +357,16 @@ def make_policy(policy_name, **kw):
         opt = {k: kw[k] for k in ("epochs", "lr", "reg_weight", "re", "field_norm") if k in kw}
         return OptimalObserverPolicy(kw["observer"], kw["v_norm"], **opt)
     if policy_name == "optimal-policy-observer":
-        raise NotImplementedError(f"policy `{policy_name}` optimises through the PINO full-field observer; it is outside this loop")
+        if kw.get("policy_model") is None or kw.get("observer") is None:
+            raise NotImplementedError("policy `optimal-policy-observer` trains a policy network through a trained full-field observer: "
+                                      "pass policy_model=<a PolicyModel2D with in_dim = 1> and observer=<a PINObserverFullField with "
+                                      "in_dim = 1> (run_control: model_name: PINObserverFullField, load_model_name and "
+                                      "policy_model_name: PolicyModel2D); the bare name cannot build it")
+        if int(kw.get("model_timestep", 1)) != 1:
+            raise NotImplementedError(f"policy `optimal-policy-observer` with model_timestep = {kw['model_timestep']}: it trains on one "
+                                      "wall plane through an observer of one time step (model_timestep = 1)")
+        opt = {k: kw[k] for k in ("epochs", "lr", "reg_weight", "re") if k in kw}
+        return PolicyObserverPolicy(kw["policy_model"], kw["observer"], **opt)
     raise RuntimeError("Not supported policy name.")
 
 
@@ -454,8 +576,10 @@ class ControlLoop:
         env = self.env
         if self._graph is None or self._graph_of is not env.U:
             staged = self.collector is not None
+            # (a policy that carries state from one iteration to the next names it: PolicyObserverPolicy.state_tensors)
             self._graph = F.GraphedControlLoop(lambda: self._iteration(self.row, staged),
-                                               [env.U, env.V, env.W, env.dPdx_dev, self.p1, self.p2], env.device)
+                                               [env.U, env.V, env.W, env.dPdx_dev, self.p1, self.p2]
+                                               + list(getattr(self.policy, "state_tensors", list)()), env.device)
             self._graph_of = env.U
         self._graph.replay()
 

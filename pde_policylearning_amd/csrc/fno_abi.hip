@@ -20,6 +20,7 @@
 #include "k_chanflow_step.h"
 #include "k_control_loop.h"
 #include "k_action_opt.h"
+#include "k_policy_opt.h"
 #include "k_ns2d.h"
 #include "k_pointwise.h"
 #include "k_block_fwd2.h"
@@ -2774,6 +2775,39 @@ extern "C" int fno_ctrl_action_finish(int B, size_t plane, const float* a, doubl
   if (!a || !opV2) return fail(FNO_EINVAL, "fno_ctrl_action_finish: null argument");
   if (((uintptr_t)a & 3) || ((uintptr_t)opV2 & 7)) return fail(FNO_EINVAL, "fno_ctrl_action_finish: misaligned tensor");
   return launch("k_act_finish", k_act_finish, dim3(B), dim3(256), 0, (hipStream_t)stream, plane, a, opV2);
+}
+
+// ===========================================================================
+// optimal-policy-observer policy (run_control.py:162-185): the glue between the policy network and the observer (k_policy_opt.h)
+// ===========================================================================
+static int pol_check(const char* who, int B, size_t plane, std::initializer_list<const void*> f32, std::initializer_list<const void*> f64) {
+  LAUNCHCHK(ctrl_plane_check(who, B, plane, plane));
+  for (const void* p : f32) {
+    if (!p) return fail(FNO_EINVAL, "%s: null argument", who);
+    if ((uintptr_t)p & 3) return fail(FNO_EINVAL, "%s: misaligned tensor", who);
+  }
+  for (const void* p : f64) {
+    if (!p) return fail(FNO_EINVAL, "%s: null argument", who);
+    if ((uintptr_t)p & 7) return fail(FNO_EINVAL, "%s: misaligned tensor", who);
+  }
+  return FNO_OK;
+}
+extern "C" int fno_ctrl_policy_begin(int B, size_t plane, const double* opV2_0, const double* p2, float* a0, float* pin, void* stream) {
+  LAUNCHCHK(pol_check("fno_ctrl_policy_begin", B, plane, {a0, pin}, {opV2_0, p2}));
+  return launch("k_pol_begin", k_pol_begin, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, plane, opV2_0,
+                p2, a0, pin);
+}
+extern "C" int fno_ctrl_policy_compose(int B, size_t plane, const float* a0, const float* res, float* x, double* opV2, void* stream) {
+  LAUNCHCHK(pol_check("fno_ctrl_policy_compose", B, plane, {a0, res, x}, {opV2}));
+  return launch("k_pol_compose", k_pol_compose, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, plane, a0,
+                res, x, opV2);
+}
+extern "C" int fno_ctrl_policy_grad(int B, size_t plane, const float* dx, const float* x, const double* parts, double reg, float* g,
+                                    void* stream) {
+  LAUNCHCHK(pol_check("fno_ctrl_policy_grad", B, plane, {dx, x, g}, {parts}));
+  if (!std::isfinite(reg)) return fail(FNO_EINVAL, "fno_ctrl_policy_grad: reg must be finite");
+  return launch("k_pol_grad", k_pol_grad, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, plane, dx, x,
+                parts, reg, g);
 }
 
 // ===========================================================================

@@ -1445,6 +1445,93 @@ def ctrl_action_finish(a, out=None, shape=None):
 
 
 # ----------------------------------------------------------------------------
+# optimal-policy-observer policy (run_control.py:162-185): the glue between the policy network and the observer (k_policy_opt.h)
+# ----------------------------------------------------------------------------
+def _policy_rows(e, name, t, anchor, B, plane, dtype=torch.float32, layout="dense"):
+    """a dense tensor of B planes of `plane` points, any shape"""
+    return _operand(e, name, t, anchor, dtype=dtype, numel=B * plane, layout=layout)
+
+
+def ctrl_policy_begin(opV2_0, p2, a0, pin):
+    """a0 = float32(opV2_0) and pin = float32(p2) in one launch: the start action of the optimal-policy-observer policy and
+    the policy network's input, the RAW wall pressure (run_control.py:163-166: no normaliser).  opV2_0, p2 (B, Nx, Nz)
+    float64; a0, pin float32 with B * Nx * Nz elements, written in place."""
+    e = "ctrl_policy_begin"
+    _gpu_anchor(e, "opV2_0", opV2_0)
+    if opV2_0.dim() < 2:
+        raise _refuse(e, "opV2_0", "be (B, Nx, Nz)", tuple(opV2_0.shape))
+    B, plane = opV2_0.shape[0], opV2_0[0].numel()
+    v0 = _operand(e, "opV2_0", opV2_0, opV2_0, dtype=torch.float64)
+    p2 = _policy_rows(e, "p2", p2, v0, B, plane, dtype=torch.float64, layout="copy")
+    a0, pin = _policy_rows(e, "a0", a0, v0, B, plane), _policy_rows(e, "pin", pin, v0, B, plane)
+    _call(e, v0.device, "fno_ctrl_policy_begin", B, plane, v0, p2, a0, pin, STREAM)
+    return a0, pin
+
+
+def ctrl_policy_compose(a0, res, x, opV2):
+    """x = a0 + res (one float32 add) and opV2 = float64(x) in the same pass: the observer's input and the action the loop
+    applies (run_control.py:170, 185).  a0 (B, Nx * Nz) float32; res, x float32 and opV2 float64 with the same number of
+    elements; x and opV2 are written in place."""
+    e = "ctrl_policy_compose"
+    _gpu_anchor(e, "a0", a0)
+    if a0.dim() < 2:
+        raise _refuse(e, "a0", "be (B, Nx * Nz)", tuple(a0.shape))
+    B, plane = a0.shape[0], a0[0].numel()
+    a0 = _operand(e, "a0", a0, a0, dtype=torch.float32)
+    res = _policy_rows(e, "res", res, a0, B, plane, layout="copy")
+    x = _policy_rows(e, "x", x, a0, B, plane)
+    opV2 = _policy_rows(e, "opV2", opV2, a0, B, plane, dtype=torch.float64)
+    _call(e, a0.device, "fno_ctrl_policy_compose", B, plane, a0, res, x, opV2, STREAM)
+    return x, opV2
+
+
+def ctrl_policy_unit_stats(plane, device):
+    """(mean, std) = (zeros, ones), float64 with `plane` points: the statistics ctrl_policy_objective hands the objective"""
+    return (torch.zeros(int(plane), dtype=torch.float64, device=device), torch.ones(int(plane), dtype=torch.float64, device=device))
+
+
+def ctrl_policy_objective(y, x, reg=0.1, parts=None, dy=None, ws=None, unit=None):
+    """The optimal-policy-observer objective |y[b]|_2 + reg * |x[b]|_2 of every environment and dy = float32(float64(y) / nf):
+    ctrl_action_objective as it stands (its kernels, reduction order, workspace and ACTION_PARTS columns), called with
+    a := x and unit statistics mean = 0, std = 1, eps = 0.  The reference feeds the observer the raw action and reads raw
+    planes (run_control.py:171-173: no encode, no decode), and unit statistics are exactly that: S = 1.0 + 0.0 = 1.0, the
+    product float64(y) * 1.0 and the sum + 0.0 return float64(y) itself (a negative zero becomes a positive one, whose
+    square and whose quotient by nf > 0 round to the same float32 magnitude 0), and dy = field / nf * 1.0 is the quotient
+    rounded once; no operation of the kernel rounds anything it would not round without the statistics.  y (B, P, Nx, Nz[, 1])
+    float32, x float32 with B * Nx * Nz elements; `unit`: ctrl_policy_unit_stats of this plane (made here when absent - pass
+    it inside a graph capture).  Returns (parts, dy)."""
+    e = "ctrl_policy_objective"
+    _gpu_anchor(e, "y", y)
+    if not torch.is_tensor(x) or y.dim() < 3 or x.dim() < 1 or x.shape[0] != y.shape[0]:
+        raise _refuse(e, "x", "hold B planes beside y (B, P, Nx, Nz)", getattr(x, "shape", type(x).__name__))
+    B = y.shape[0]
+    plane = x.numel() // max(B, 1)
+    if unit is None:
+        unit = ctrl_policy_unit_stats(plane, y.device)
+    return ctrl_action_objective(y, x.reshape(B, plane), unit[0], unit[1], 0.0, reg=reg, parts=parts, dy=dy, ws=ws)
+
+
+def ctrl_policy_grad(dx, x, parts, reg=0.1, out=None):
+    """g = float32(float64(dx) + reg * float64(x) / na) with na = parts[:, 2] (g = dx where na == 0): the gradient of
+    |y|_2 + reg * |x|_2 with respect to the policy's output res (x = a0 + res), assembled in float64 and rounded once.  dx:
+    the observer's input gradient given ctrl_policy_objective's dy; dx, x float32 with B * Nx * Nz elements; parts (B, 3)."""
+    e = "ctrl_policy_grad"
+    _gpu_anchor(e, "dx", dx)
+    if not torch.is_tensor(parts) or parts.dim() != 2:
+        raise _refuse(e, "parts", "be the (B, 3) float64 tensor of ctrl_policy_objective", getattr(parts, "shape", type(parts).__name__))
+    B = parts.shape[0]
+    plane = dx.numel() // max(B, 1)
+    dx = _policy_rows(e, "dx", dx, dx, B, plane, layout="copy")
+    x = _policy_rows(e, "x", x, dx, B, plane, layout="copy")
+    parts = _operand(e, "parts", parts, dx, dtype=torch.float64, shape=(B, len(ACTION_PARTS)))
+    if out is None:
+        out = torch.empty(dx.shape, dtype=torch.float32, device=dx.device)
+    out = _policy_rows(e, "g", out, dx, B, plane)
+    _call(e, dx.device, "fno_ctrl_policy_grad", B, plane, dx, x, parts, float(reg), out, STREAM)
+    return out
+
+
+# ----------------------------------------------------------------------------
 # NSControlEnv2D: the 2-D periodic channel (libs/envs/ns_control_2d.py), float64, one workgroup per environment
 # ----------------------------------------------------------------------------
 NS2D_SOLVE_OUT = ("bulk_v", "steps", "status")

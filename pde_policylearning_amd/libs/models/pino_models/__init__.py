@@ -1,2 +1,2 @@
 from .basics import SpectralConv2d, SpectralConv3d  # noqa: F401
-from .pinobserver import MultiplicativeNet, PINObserver2d, PINObserverFullField, PlanePredHead  # noqa: F401
+from .pinobserver import MultiplicativeNet, PINObserver2d, PINObserverFullField, PlanePredHead, PolicyModel2D  # noqa: F401

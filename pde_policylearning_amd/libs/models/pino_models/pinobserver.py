@@ -1,6 +1,6 @@
 """PINO observers with the reference surface (libs/models/pino_models/pinobserver.py:
 MultiplicativeNet :14-63, PINObserver2d :129-233, PlanePredHead :236-273,
-PINObserverFullField :276-375).  SpectralConv3d runs in the HIP engine; the channels-last
+PINObserverFullField :276-375, PolicyModel2D :378-463).  SpectralConv3d runs in the HIP engine; the channels-last
 Linear / Conv1d(k=1) glue is torch."""
 import math
 
@@ -256,3 +256,41 @@ class PINObserverFullField(nn.Module):
         x = _lift_front(self.fc0, self.multiplicative_net1, x, re, self.layers[0])
         pred = self.observer_head(_pad_last(x, num_pad).contiguous(), num_pad, re, self.multiplicative_net2)
         return pred.permute(0, 4, 1, 2, 3)     # (B, planes, X, Y, T)
+
+
+class PolicyModel2D(nn.Module):
+    """The policy network of `optimal-policy-observer` (pinobserver.py:378-463): PINObserverFullField with the head named
+    `pred_net`, out_dim outputs and the output left channels-last (B, X, Y, T, out_dim).  The reference ends its constructor
+    by zeroing EVERY parameter, which makes its run degenerate: fc2.weight's gradient is dy (x) gelu(0) = 0 and everything
+    upstream receives fc2.weight^T dy = 0, so only pred_net.fc2.bias ever changes and the policy is one scalar offset of the
+    whole plane.  zero_init (beyond the reference's signature): True - the reference; "head" - the ordinary initialisation
+    with only pred_net.fc2 zeroed, so the correction still starts at zero but gradients reach every layer from the second
+    step on; False - the ordinary initialisation."""
+
+    def __init__(self, modes1, modes2, modes3, width=16, fc_dim=128, layers=None, in_dim=4, out_dim=1,
+                 act='gelu', pad_ratio=[0., 0.], use_fourier_layer=False, zero_init=True):
+        super().__init__()
+        if use_fourier_layer:
+            raise NotImplementedError("use_fourier_layer=True is outside the accelerated hot path")
+        if zero_init not in (True, False, "head"):
+            raise ValueError(f"PolicyModel2D: zero_init must be True, False or 'head' (got {zero_init!r})")
+        self.pad_ratio = _pad_ratio(pad_ratio)
+        self.modes1, self.modes2, self.modes3 = modes1, modes2, modes3
+        self.max_re, self.in_dim, self.out_dim = 1000, in_dim, out_dim
+        self.layers = [width] * 4 if layers is None else layers
+        self.use_fourier_layer, self.fourier_layer1 = False, None
+        self.fc0 = nn.Linear(in_dim, self.layers[0])
+        self.multiplicative_net1 = MultiplicativeNet(self.layers[0], 1, self.layers[0])
+        self.multiplicative_net2 = MultiplicativeNet(self.layers[-1], 1, self.layers[-1])
+        self.pred_net = PlanePredHead(self.layers, modes1, modes2, modes3, fc_dim, out_dim, act)
+        with torch.no_grad():
+            zero = list(self.parameters()) if zero_init is True else list(self.pred_net.fc2.parameters()) if zero_init == "head" else []
+            for prm in zero:
+                prm.zero_()
+
+    def forward(self, x, re):
+        re = re.float() / self.max_re
+        size_z = x.shape[-2]
+        num_pad = [round(size_z * r) for r in self.pad_ratio] if max(self.pad_ratio) > 0 else [0., 0.]
+        x = _lift_front(self.fc0, self.multiplicative_net1, x, re, self.layers[0])
+        return self.pred_net(_pad_last(x, num_pad).contiguous(), num_pad, re, self.multiplicative_net2)      # (B, X, Y, T, out_dim)

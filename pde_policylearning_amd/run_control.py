@@ -6,7 +6,13 @@ The reference's YAMLs drop in: the file is merged over the flags exactly as trai
 win).  Keys read: policy_name, model_name, load_model_name, modes, width, x_range, y_range, control_timestep, detect_plane,
 noise_scale, collect_data, DATA_FOLDER, state_path_name, output_dir, exp_name, Re, model_timestep; visualisation and W&B keys
 are carried in the plan and ignored.  policy_name: optimal-observer needs model_name: PINObserverFullField, load_model_name and the
-DATA_FOLDER of a full-field dataset (its wall-plane statistics normalise the action: FullFieldNSDataset.bound_v_norm).  The
+DATA_FOLDER of a full-field dataset (its wall-plane statistics normalise the action: FullFieldNSDataset.bound_v_norm).
+policy_name: optimal-policy-observer needs model_name: PINObserverFullField, load_model_name, model_timestep 1 and
+policy_model_name: PolicyModel2D (the reference's own entry point passes policy_model=None and cannot run this policy from the
+YAML alone); the policy network is built as run_pde_observers.py:124-126 builds it (modes from the plan, [64] * 5, fc_dim 128,
+pad_ratio 0.0625, in_dim 1) and zero-initialised as the reference's is unless policy_zero_init says otherwise (true | head |
+false); load_policy_name / save_policy_name: a whole pickled policy module under output_dir, read before and written after the
+run.  No DATA_FOLDER: this policy uses no normaliser.  The
 loop runs control_timestep + 1 iterations (run_control.py:133).  --ensemble B steps B environments under one policy (each with
 its own noise draw when noise_scale > 0), --graph replays the iteration as one graph, --tanh-channel starts from an analytic
 state on a tanh grid when there is no `.mat` initial condition."""
@@ -26,7 +32,11 @@ _KEYS = ("policy_name", "model_name", "load_model_name", "modes", "width", "x_ra
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--control_yaml", "--control-yaml", dest="control_yaml", default=None, help="a reference YAML: its keys win over the flags")
-    ap.add_argument("--policy_name", default="gt", help="gt | unmanipulated | fno | rno | optimal-observer")
+    ap.add_argument("--policy_name", default="gt", help="gt | unmanipulated | fno | rno | optimal-observer | optimal-policy-observer")
+    ap.add_argument("--policy_model_name", default=None, help="optimal-policy-observer: PolicyModel2D")
+    ap.add_argument("--policy_zero_init", default=True, help="optimal-policy-observer: true (the reference) | head | false")
+    ap.add_argument("--load_policy_name", default=None, help="a whole pickled policy module under output_dir")
+    ap.add_argument("--save_policy_name", default=None, help="write the trained policy module under output_dir after the run")
     ap.add_argument("--model_name", default="FNO2dObserver")
     ap.add_argument("--load_model_name", default=None, help="whole pickled module under output_dir (train_observer's save_if_best)")
     ap.add_argument("--modes", type=int, default=12)
@@ -66,11 +76,22 @@ def plan_from_yaml(args, yaml_dict=None):
         return _plan_ns2d(ns)
     if ns.env_name != "NSControlEnvMatlab":
         raise RuntimeError("Not supported environment!")                 # run_control.py:107
-    if ns.policy_name in ("rand", "optimal-policy-observer") or (ns.policy_name == "optimal-observer"
-                                                                 and ns.model_name != "PINObserverFullField"):
+    policy_model_name = getattr(ns, "policy_model_name", None)
+    if ns.policy_name == "rand" or (ns.policy_name in ("optimal-observer", "optimal-policy-observer")
+                                    and ns.model_name != "PINObserverFullField"):
         make_policy(ns.policy_name)                                      # raises NotImplementedError with the reason
-    if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno", "optimal-observer"):
+    if ns.policy_name == "optimal-policy-observer" and policy_model_name != "PolicyModel2D":
+        if policy_model_name is None:
+            make_policy(ns.policy_name)                                  # the YAML alone cannot build it (nor can the reference's)
+        raise NotImplementedError(f"run_control: policy_model_name {policy_model_name!r}; optimal-policy-observer trains a PolicyModel2D "
+                                  "(policy_model_name: PolicyModel2D)")
+    if ns.policy_name not in ("gt", "unmanipulated", "fno", "rno", "optimal-observer", "optimal-policy-observer"):
         raise RuntimeError("Not supported policy name.")
+    if ns.policy_name == "optimal-policy-observer":
+        if int(getattr(ns, "model_timestep", 1) or 1) != 1:
+            raise NotImplementedError(f"run_control: optimal-policy-observer with model_timestep = {ns.model_timestep}; the policy "
+                                      "trains on one wall plane through an observer of one time step")
+        ns.policy_zero_init = _zero_init(getattr(ns, "policy_zero_init", True))
     if ns.policy_name == "optimal-observer":
         if int(getattr(ns, "model_timestep", 1) or 1) != 1:
             raise NotImplementedError(f"run_control: optimal-observer with model_timestep = {ns.model_timestep}; the policy "
@@ -83,11 +104,21 @@ def plan_from_yaml(args, yaml_dict=None):
     ns.steps = int(ns.control_timestep) + 1                              # :133
     ns.collect_folder = os.path.join(ns.output_dir, ns.exp_name) if ns.collect_data else None      # :112-114
     ns.ensemble = max(int(getattr(ns, "ensemble", 1)), 1)
-    if ns.policy_name in ("fno", "rno", "optimal-observer") and not ns.load_model_name:
+    if ns.policy_name in ("fno", "rno", "optimal-observer", "optimal-policy-observer") and not ns.load_model_name:
         raise ValueError("run_control: a neural policy needs load_model_name (a model saved by train_observer)")
     if not ns.state_path_name and not getattr(ns, "tanh_channel", False):
         raise ValueError("run_control: no initial condition (state_path_name, or --tanh-channel)")
     return ns
+
+
+def _zero_init(v):
+    """policy_zero_init of a plan: true | head | false (a YAML boolean or a flag's string) -> PolicyModel2D's zero_init"""
+    if isinstance(v, str):
+        table = {"true": True, "false": False, "head": "head"}
+        if v.strip().lower() not in table:
+            raise ValueError(f"run_control: policy_zero_init must be true, head or false (got {v!r})")
+        return table[v.strip().lower()]
+    return bool(v)
 
 
 NS2D_POLICIES = ("gt", "unmanipulated")
@@ -151,11 +182,31 @@ def make_plan_policy(plan, device="cuda"):
         return make_policy(plan.policy_name)
     from .libs.pde_data_loader import FullFieldNSDataset, PDEDataset
     observer = torch.load(os.path.join(plan.output_dir, plan.load_model_name), map_location=device, weights_only=False)   # run_control.py:40
+    if plan.policy_name == "optimal-policy-observer":
+        return make_policy(plan.policy_name, policy_model=make_policy_model(plan, device), observer=observer)
     if plan.policy_name == "optimal-observer":
         ds = FullFieldNSDataset(argparse.Namespace(model_timestep=1), plan.DATA_FOLDER, [0], [], 1, plan.x_range, plan.y_range)
         return make_policy(plan.policy_name, observer=observer, v_norm=ds.bound_v_norm, field_norm=ds.v_field_norm)
     ds = PDEDataset(plan, plan.DATA_FOLDER, [0], 1, plan.x_range, plan.y_range)
     return make_policy(plan.policy_name, observer=observer, p_norm=ds.p_norm, v_norm=ds.v_norm)
+
+
+def make_policy_model(plan, device="cuda"):
+    """the PolicyModel2D of an optimal-policy-observer plan: load_policy_name (a whole pickled module under output_dir), or
+    a new one built as run_pde_observers.py:124-126 does"""
+    from .libs.models.pino_models import PolicyModel2D
+    if getattr(plan, "load_policy_name", None):
+        return torch.load(os.path.join(plan.output_dir, plan.load_policy_name), map_location=device, weights_only=False)
+    modes = [int(plan.modes)] * 4
+    return PolicyModel2D(modes1=modes, modes2=modes, modes3=modes, fc_dim=128, layers=[64] * 5, in_dim=1, out_dim=1, act="gelu",
+                         pad_ratio=[0.0, 0.0625], zero_init=getattr(plan, "policy_zero_init", True)).to(device)
+
+
+def save_policy_model(plan, policy):
+    """save_policy_name: the trained policy module, whole, under output_dir (its dead weight slices brought up to date first)"""
+    policy.optimizer.sync_dead_slices()
+    os.makedirs(plan.output_dir, exist_ok=True)
+    torch.save(policy.policy_model, os.path.join(plan.output_dir, plan.save_policy_name))
 
 
 EXPLODE_AT = 10.0                 # run_control.py:294-295: |reward_div| above this is "Control exploded!"
@@ -208,6 +259,8 @@ def run(plan):
     policy = make_plan_policy(plan, env.device)
     collector = Collector(plan.collect_folder, plan.collect_start, re=plan.Re) if plan.collect_folder else None
     result = ControlLoop(env, policy, plan.steps, collector=collector, graph=plan.graph, check_every=plan.check_every).run()
+    if plan.policy_name == "optimal-policy-observer" and getattr(plan, "save_policy_name", None):
+        save_policy_model(plan, policy)
     last = result.infos[-1]
     for b, info in enumerate(last if isinstance(last, list) else [last]):
         rel = info.get("drag_reduction_relative/3_3_dPdx_reverse_cal")

@@ -780,6 +780,44 @@ class FusedAdam(object):
     def zero_grad(self, set_to_none=False):
         self.bucket.zero()
 
+    def plan_dead_slices(self, *sample_inputs):
+        """Make the dead-slice plan NOW instead of at the first step(): with `sample_inputs`, one forward pass of the bucket's
+        direct_module under no_grad records the live last-dim extents first.  For callers that need the final parameter and
+        moment buffers before the first step (a graph capture's state list: control.PolicyObserverPolicy).  A no-op without
+        skip_dead_slices=True or once a plan exists.  Returns whether anything is skipped."""
+        if not self._skip_dead or self._runs is not None or self.bucket.direct_module is None:
+            return self._runs is not None
+        if sample_inputs:
+            with torch.no_grad():
+                self.bucket.direct_module(*sample_inputs)
+        self._skip_dead = False      # (as step(): one attempt)
+        return self.skip_dead_slices()
+
+    def full_moments(self):
+        """(exp_avg, exp_avg_sq) in the bucket's full layout, whatever the internal representation (new tensors when the
+        moments are kept compact around dead slices)"""
+        return self._full_moments() if self._runs is not None else (self.exp_avg, self.exp_avg_sq)
+
+    def reset_state(self):
+        """What replacing the optimizer by a NEW torch.optim.Adam on the same parameters does (run_control.py:167, once per
+        control iteration): the step count back to 0 and the moments to zero; the parameters stay.  The live moments are
+        zeroed where they are (one fill each, capturable; the buffers a graph captured stay valid); a deferred replay of the
+        dead slices is DROPPED, not run: a dead element has g = m = v = 0, so every skipped step was lr_t * 0 / (0 + eps)
+        = 0 and the parameter keeps its bits, which holds only without weight decay - with one this raises.  Nothing here
+        touches the dead slices' memory."""
+        if float(self.weight_decay) != 0.0:
+            raise RuntimeError(f"FusedAdam.reset_state: exact only without weight decay (got {self.weight_decay}): with one the "
+                               "dead slices' skipped steps move the parameters and would have to be replayed first")
+        if any(d is not None for d in self._dead.values()):
+            raise RuntimeError("FusedAdam.reset_state: the dead slices carry non-zero moments (a loaded state); call "
+                               "sync_dead_slices() and rebuild the optimizer instead")
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.step_count = 0
+        if self.capturable:
+            self.step_dev.zero_()
+        self._dead_step, self._hp_log = 0, []
+
     def step(self):
         from . import functional as F
         self.bucket.check_views()

@@ -1,0 +1,221 @@
+"""What the optimal-policy-observer policy (control.PolicyObserverPolicy, csrc/k_policy_opt.h, PolicyModel2D,
+FusedAdam.reset_state) is held to: the fixture, the restatements of run_control.py:162-185 in float64 and in the reference's
+own dtypes, the closed forms the kernels evaluate, the comparison and the error log.  A helper module, not a conftest; shared
+by tests/test_policy_opt_host.py (CPU) and tests/test_policy_opt_gpu.py.
+
+Comparison (tests/step_tail_cases.accept):  err == 0 or err < max(floor, BUDGET_SLACK * err_ref32), err = relative L2 against
+the float64 restatement, err_ref32 = the error of the reference's own dtypes on the same inputs (float32 oracle networks,
+torch autograd, torch.optim.Adam's float32 arithmetic).  Floor 1e-5 for losses and gradients, none for the elementwise kernels.
+Every figure goes to profiles/r17_policy_opt_errors.txt, one block per case, before anything is asserted.
+
+Teacher forcing.  Adam's first step is lr * sign(g); among millions of parameters some gradients sit inside the float32 error
+and each flipped sign costs 2 lr against a displacement norm of lr * sqrt(N), so parameter trajectories are never compared
+across steps.  Every epoch is judged on its own from the parameters the run under test itself held at the start of that epoch
+(`epoch_oracle`), and the Adam step against a restatement fed that run's own parameters, gradients and moments (`adam_step`).
+The Adam step is judged on the whole flat parameter vector, as the DISPLACEMENT p_new - p_old (an error of the whole update
+would hide behind |p| >> lr): both float32 evaluations end in one rounding at the parameter's own ulp, which is what the
+displacement's error is made of, and only over many elements do two draws of that rounding have comparable norms (a single
+element, pred_net.fc2.bias, does not), hence the flat vector and not one tensor at a time."""
+import math
+import os
+
+import torch
+
+from oracle import observers_oracle as OO
+from tests import action_opt_cases as A
+from tests.step_tail_cases import accept, rel_err        # noqa: F401
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LOG = os.path.join(ROOT, "profiles", "r17_policy_opt_errors.txt")
+FLOOR = 1e-5
+RE, LR, BETAS, ADAM_EPS, EPOCHS = 180.0, 1e-4, (0.9, 0.999), 1e-8, 3
+NX = NZ = 32
+MODES, PAD, FC_DIM = [(4, 4, 4)] * 4, [0.0, 0.0625], 128
+WIDTHS = (64, 32)
+KEYS = (["fc0.weight", "fc0.bias"] + [f"multiplicative_net{i}.{n}" for i in (1, 2) for n in ("A", "B", "bias")]
+        + [f"pred_net.sp_convs.{i}.weights{j}" for i in range(4) for j in (1, 2, 3, 4)]
+        + [f"pred_net.ws.{i}.{n}" for i in range(4) for n in ("weight", "bias")]
+        + [f"pred_net.{fc}.{n}" for fc in ("fc1", "fc2") for n in ("weight", "bias")])
+
+
+def log_block(section, lines):
+    """replace `section` of the error log by `lines` (one file, one block per case), as action_opt_cases.log_block"""
+    keep, A.LOG = A.LOG, LOG
+    try:
+        A.log_block(section, lines)
+    finally:
+        A.LOG = keep
+
+
+def judge(section, rows, who="engine"):
+    """rows: (name, err, err_ref32, floor).  Logs all, then asserts all."""
+    lines, bad = [], []
+    for name, err, ref, floor in rows:
+        ok = accept(err, ref, floor)
+        lines.append(f"{name:52s} {who} {err:10.3e}   ref32 {ref:10.3e}   floor {floor:7.1e}   {'ok' if ok else 'MISS'}")
+        print(section, lines[-1])
+        if not ok:
+            bad.append(lines[-1])
+    log_block(section, lines)
+    assert not bad, "\n".join([section] + bad)
+
+
+def rejected(rows):
+    return [name for name, err, ref, floor in rows if not accept(err, ref, floor)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# fixture
+# ---------------------------------------------------------------------------------------------------------------------------
+def policy_model(width=64, zero_init=False, seed=1):
+    """PolicyModel2D (modes [4] * 4, fc_dim 128, [width] * 5) on the CPU.  zero_init False: the state of a seeded
+    PINObserverFullField(plane_num=1) copied in under the key rename observer_head. -> pred_net."""
+    from pde_policylearning_amd.libs.models.pino_models import PINObserverFullField, PolicyModel2D
+    kw = dict(modes1=[4] * 4, modes2=[4] * 4, modes3=[4] * 4, fc_dim=FC_DIM, layers=[width] * 5, in_dim=1, out_dim=1, act="gelu",
+              pad_ratio=list(PAD))
+    torch.manual_seed(seed + width)
+    pm = PolicyModel2D(zero_init=zero_init, **kw)
+    if zero_init is False:
+        src = PINObserverFullField(plane_num=1, **kw).state_dict()
+        pm.load_state_dict({k.replace("observer_head.", "pred_net."): v for k, v in src.items()})
+    return pm
+
+
+def oracle_params(sd, dtype):
+    """a PolicyModel2D / PINObserverFullField state dict for the oracle: on the CPU, pred_net. renamed to observer_head., cast"""
+    out = {}
+    for k, v in sd.items():
+        v = v.detach().cpu().clone()
+        if dtype == torch.float64:
+            v = v.to(torch.complex128 if v.is_complex() else torch.float64)
+        out[k.replace("pred_net.", "observer_head.")] = v
+    return out
+
+
+def policy_forward(p, pin, re, width):
+    """the oracle's PolicyModel2D: the full-field forward with one plane, permuted back to channels-last (B, Nx, Nz, 1, 1)"""
+    re = torch.as_tensor(re, dtype=pin.dtype).reshape(-1).expand(pin.shape[0])
+    return OO.pinobserver_fullfield_forward(p, pin, re, [width] * 5, MODES, PAD).permute(0, 2, 3, 4, 1)
+
+
+def planes(B, seed, scale):
+    g = torch.Generator().manual_seed(seed)
+    return (scale * torch.randn(B, NX, NZ, generator=g, dtype=torch.float64)).float()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# one epoch from given parameters
+# ---------------------------------------------------------------------------------------------------------------------------
+def epoch_oracle(pp, po, a0, pin, re, reg, dtype, width):
+    """run_control.py:169-174 under torch autograd in `dtype`, from the policy parameters `pp` and the observer's `po` (state
+    dicts of float32 tensors), a0 and pin (B, Nx, Nz) float32.  The loss is the sum over the environments of
+    torch.norm(y[b]) + reg * torch.norm(x[b]).  -> res, x (B, Nx, Nz), parts (B, 3), dx, g = dL/dres, grads {policy key: tensor}"""
+    p = {k: v.requires_grad_(True) for k, v in oracle_params(pp, dtype).items()}
+    o = oracle_params(po, dtype)
+    res = policy_forward(p, pin.to(dtype)[..., None, None], re, width)
+    x = a0.to(dtype)[..., None, None] + res
+    x.retain_grad()
+    res.retain_grad()
+    y = A.forward(o, x, re)
+    B = x.shape[0]
+    nf = torch.stack([torch.norm(y[b]) for b in range(B)])
+    na = torch.stack([torch.norm(x[b]) for b in range(B)])
+    (nf + reg * na).sum().backward()
+    d = lambda t: t.detach().double()        # noqa: E731
+    return {"res": d(res)[..., 0, 0], "x": d(x)[..., 0, 0], "parts": torch.stack([d(nf + reg * na), d(nf), d(na)], dim=1),
+            "g": d(res.grad)[..., 0, 0], "grads": {k.replace("observer_head.", "pred_net."): v.grad.detach() for k, v in p.items()},
+            "y": d(y)}
+
+
+def dx_oracle(po, x, re, dtype):
+    """the observer's input gradient of sum_b |y[b]| at the given x (B, Nx, Nz), in `dtype`"""
+    xl = x.to(dtype)[..., None, None].clone().requires_grad_(True)
+    y = A.forward(oracle_params(po, dtype), xl, re)
+    sum(torch.norm(y[b]) for b in range(y.shape[0])).backward()
+    return xl.grad.double()[..., 0, 0]
+
+
+def dy_closed(y):
+    """y (P, Nx, Nz) -> nf, dy = y / nf in float64 (0 where nf == 0)"""
+    y = y.double()
+    nf = torch.sqrt((y * y).sum())
+    return nf, (torch.zeros_like(y) if float(nf) == 0.0 else y / nf)
+
+
+def g_closed(dx, x, reg, na_squared=False):
+    """g = dx + reg * x / na in float64 per environment (second term 0 where na == 0).  na_squared: the planted fault x / na^2"""
+    dx, x = dx.double(), x.double()
+    out = torch.empty_like(dx)
+    for b in range(x.shape[0]):
+        na = torch.sqrt((x[b] * x[b]).sum())
+        out[b] = dx[b] if float(na) == 0.0 else dx[b] + reg * x[b] / (na * na if na_squared else na)
+    return out
+
+
+def epoch_kernels(pp, po, a0, pin, re, reg, width, na_squared=False):
+    """the engine's arithmetic restated in torch on the CPU: float32 oracle networks, x = a0 + res one float32 add, the
+    objective's norms in float64, dy = float32(y / nf), the observer's backward given dy, g assembled in float64 and rounded
+    once, the policy's backward given g.  -> as epoch_oracle"""
+    p = {k: v.requires_grad_(True) for k, v in oracle_params(pp, torch.float32).items()}
+    o = oracle_params(po, torch.float32)
+    res = policy_forward(p, pin[..., None, None], re, width)
+    x = (a0[..., None, None] + res.detach()).requires_grad_(True)
+    y = A.forward(o, x, re)
+    B = x.shape[0]
+    parts, dy = [], []
+    for b in range(B):
+        nf, d = dy_closed(y.detach()[b, ..., 0])
+        na = torch.sqrt((x.detach()[b].double() ** 2).sum())
+        parts.append(torch.stack([nf + reg * na, nf, na]))
+        dy.append(d.float())
+    (dx,) = torch.autograd.grad(y, x, torch.stack(dy)[..., None])
+    g = g_closed(dx[..., 0, 0], x.detach()[..., 0, 0], reg, na_squared).float()
+    torch.autograd.backward(res, g[..., None, None])
+    d = lambda t: t.detach().double()        # noqa: E731
+    return {"res": d(res)[..., 0, 0], "x": d(x)[..., 0, 0], "parts": torch.stack(parts), "g": g.double(),
+            "dx": d(dx)[..., 0, 0], "grads": {k.replace("observer_head.", "pred_net."): v.grad.detach() for k, v in p.items()}}
+
+
+def epoch_rows(tag, got, r32, r64, keys=("res", "x", "g"), grads=True):
+    """rows for judge(): the named entries, the three loss parts and every parameter gradient, each on its own"""
+    rows = [(f"{tag} {k}", rel_err(got[k], r64[k]), rel_err(r32[k], r64[k]), FLOOR) for k in keys]
+    for c, name in enumerate(("loss", "field_norm", "action_norm")):
+        rows.append((f"{tag} {name}", rel_err(got["parts"][:, c], r64["parts"][:, c]), rel_err(r32["parts"][:, c], r64["parts"][:, c]), FLOOR))
+    if grads:
+        for k in KEYS:
+            view = lambda t: torch.view_as_real(t.detach().cpu().resolve_conj()) if t.is_complex() else t.detach().cpu()      # noqa: E731
+            want = view(r64["grads"][k])
+            rows.append((f"{tag} d {k}", rel_err(view(got["grads"][k]), want), rel_err(view(r32["grads"][k]), want), FLOOR))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Adam
+# ---------------------------------------------------------------------------------------------------------------------------
+def adam_step(p, g, m, v, step, dtype, lr=LR):
+    """one torch.optim.Adam step (no weight decay, no amsgrad) on flat tensors, in `dtype`, with torch's own operation order
+    (_single_tensor_adam: lerp, mul + addcmul, sqrt / bias_correction2_sqrt + eps, addcdiv).  -> p, m, v (new tensors)"""
+    p, g, m, v = (t.detach().to(dtype).clone() for t in (p, g, m, v))
+    m.lerp_(g, 1.0 - BETAS[0])
+    v.mul_(BETAS[1]).addcmul_(g, g, value=1.0 - BETAS[1])
+    step_size = lr / (1.0 - BETAS[0] ** step)
+    denom = (v.sqrt() / math.sqrt(1.0 - BETAS[1] ** step)).add_(ADAM_EPS)
+    p.addcdiv_(m, denom, value=-step_size)
+    return p, m, v
+
+
+def adam_rows(tag, p0, got, g, m0, v0, step):
+    """rows for judge(): `got` = (p, m, v) after the step under test from (p0, g, m0, v0), all flat float32, against the float64
+    restatement fed the same float32 inputs; the parameters as the displacement from p0 (module docstring)"""
+    r64, r32 = adam_step(p0, g, m0, v0, step, torch.float64), adam_step(p0, g, m0, v0, step, torch.float32)
+    p0 = p0.double()
+    disp = lambda t: t.double() - p0      # noqa: E731
+    return [(f"{tag} Adam displacement", rel_err(disp(got[0]), disp(r64[0])), rel_err(disp(r32[0]), disp(r64[0])), FLOOR),
+            (f"{tag} Adam exp_avg", rel_err(got[1], r64[1]), rel_err(r32[1], r64[1]), FLOOR),
+            (f"{tag} Adam exp_avg_sq", rel_err(got[2], r64[2]), rel_err(r32[2], r64[2]), FLOOR)]
+
+
+def flat_of(tensors, keys=KEYS):
+    """{key: tensor} -> one flat real vector in KEYS order (complex entries as interleaved pairs)"""
+    return torch.cat([(torch.view_as_real(tensors[k].detach().cpu().resolve_conj()) if tensors[k].is_complex()
+                       else tensors[k].detach().cpu()).reshape(-1) for k in keys])
