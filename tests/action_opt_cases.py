@@ -2,7 +2,7 @@
 and the reference-dtype restatements of run_control.py:186-224, the closed forms the kernels evaluate, the comparison and the
 error log.  A helper module, not a conftest; shared by tests/test_action_opt_host.py (CPU) and tests/test_action_opt_gpu.py.
 
-Comparison (tests/step_tail_cases.accept, imported):  err_engine == 0 or err_engine < max(floor, BUDGET_SLACK * err_ref32),
+Comparison (tests/judging.py::accept, judge_budget):  err_engine == 0 or err_engine < max(floor, BUDGET_SLACK * err_ref32),
 err = relative L2 against the float64 restatement, err_ref32 = the error of the reference-dtype restatement (float32 observer
 through oracle.observers_oracle, torch autograd, torch.optim.Adam) on the same inputs.  Floor 1e-5 (the project's TOL_G) for
 the loss, the input gradient and the displacement; none for the elementwise kernels.  Every figure goes to
@@ -13,6 +13,7 @@ the whole update would hide behind the start action.  Why reg = 0 as well as 0.1
 regulariser carries |g| = 0.1 against 8.5e-4 from the observer; at 0.1 an error of the observer's input gradient would hide.
 Adam's first step is lr * sign(g), so the fixture is valid only while no |g_i| is within reach of the float32 error
 (`sign_margin`), a condition on the inputs that the host test checks before the GPU is asked anything."""
+import functools
 import math
 import os
 
@@ -20,46 +21,16 @@ import numpy as np
 import torch
 
 from oracle import observers_oracle as OO
-from tests.step_tail_cases import accept, rel_err
+from tests.judging import TOL_G, SectionLog, judge_budget, rejected, rel_err  # noqa: F401  (re-exported to the tests)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG = os.path.join(ROOT, "profiles", "r16_action_opt_errors.txt")
-FLOOR = 1e-5                                 # tests/test_parity_gpu.TOL_G
+LOG = SectionLog(os.path.join(ROOT, "profiles", "r16_action_opt_errors.txt"))
+log_block = LOG.replace
+judge = functools.partial(judge_budget, LOG)        # rows: (name, err_engine, err_ref32, floor)
+FLOOR = TOL_G
 EPS, RE, LR, BETAS, ADAM_EPS, EPOCHS = 1e-5, 180.0, 1e-3, (0.9, 0.999), 1e-8, 10
 NX = NZ = 32
 PLANES, LAYERS, MODES, PAD, FC_DIM = 3, [64] * 5, [(4, 4, 4)] * 4, [0.0, 0.0625], 128
-
-
-def log_block(section, lines):
-    """replace `section` of the error log by `lines` (one file, one block per case), as control_loop_cases.log_block"""
-    try:
-        old = open(LOG).read().split("\n## ") if os.path.exists(LOG) else []
-        keep = [b for b in old if b.strip() and not b.lstrip("# ").startswith(section + "\n")]
-        body = "\n## ".join([b.lstrip("# ").rstrip("\n") for b in keep] + [section + "\n" + "\n".join(lines)])
-        os.makedirs(os.path.dirname(LOG), exist_ok=True)
-        with open(LOG, "w") as f:
-            f.write("## " + body + "\n")
-    except OSError as e:
-        import warnings
-        warnings.warn(f"the error log {LOG} could not be written ({e}); the figures of `{section}` are on stdout only")
-
-
-def judge(section, rows, who="engine"):
-    """rows: (name, err_engine, err_ref32, floor).  Logs all, then asserts all."""
-    lines, bad = [], []
-    for name, err, ref, floor in rows:
-        ok = accept(err, ref, floor)
-        lines.append(f"{name:46s} {who} {err:10.3e}   ref32 {ref:10.3e}   floor {floor:7.1e}   {'ok' if ok else 'MISS'}")
-        print(section, lines[-1])
-        if not ok:
-            bad.append(lines[-1])
-    log_block(section, lines)
-    assert not bad, "\n".join([section] + bad)
-
-
-def rejected(rows):
-    """names of the rows the rule refuses (the planted faults must leave at least one)"""
-    return [name for name, err, ref, floor in rows if not accept(err, ref, floor)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -1,16 +1,13 @@
-"""Helpers of the control-loop tests (a helper module, not a conftest): the tolerance rule, the fixtures and the float64
+"""Helpers of the control-loop tests (a helper module, not a conftest): the error table, the fixtures and the float64
 restatement of the closed loop.
 
-The rule, restated from the channel-flow step tests.  Nothing is tuned to what the kernels give.  For every compared quantity
-the test first measures the FLOOR on the CPU at the size at hand (what the floor is is said per case: a second evaluation of
-the reference in another precision or order, or the restatement re-run from a state perturbed by a relative 1e-16) and the GPU
-gets
-    bound = min(16 * max(floor, resolution), 1e-9),    resolution = eps = 2.2e-16 unless stated
-(two float64 evaluations of one quantity differ by eps unless they are bitwise equal; 1e-9 = cond * eps of the worst Poisson
-system).  Quantities that are differences or means of signed terms are measured against the scale of what is summed, because
-that is what one rounding is relative to (`info_scales`; dPdx carries the rounding of a bulk velocity divided by dt:
-`dpdx_resolution`).  Every measured distance, its floor and its bound go to profiles/r13_control_loop_errors.txt, one block per
-case, before anything is asserted."""
+The rule is the float64 floor rule of tests/judging.py (`bound`, `judge_floor`); nothing is tuned to what the kernels give.  What
+the floor of a compared quantity is is said per case: a second evaluation of the reference in another precision or order, or
+the restatement re-run from a state perturbed by a relative 1e-16.  Quantities that are differences or means of signed terms
+are measured against the scale of what is summed, because that is what one rounding is relative to (`info_scales`; dPdx carries
+the rounding of a bulk velocity divided by dt: `dpdx_resolution`).  Every measured distance, its floor and its bound go to
+profiles/r13_control_loop_errors.txt, one block per case, before anything is asserted."""
+import functools
 import os
 
 import numpy as np
@@ -18,47 +15,14 @@ import torch
 
 from oracle.detfill import fill_named
 from tests import chanflow_step_reference as R
+from tests.judging import EPS64 as EPS, SectionLog, bound, judge_floor  # noqa: F401  (bound: re-exported to the tests)
 from tests.util import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG = os.path.join(ROOT, "profiles", "r13_control_loop_errors.txt")
-EPS = float(np.finfo(np.float64).eps)
-CAP = 1e-9
+LOG = SectionLog(os.path.join(ROOT, "profiles", "r13_control_loop_errors.txt"))
 DT = 1e-3
-
-
-def bound(floor, resolution=EPS):
-    return min(16.0 * max(floor, resolution), CAP)
-
-
-def log_block(section, lines):
-    """replace `section` of the error log by `lines` (one file, one block per case)"""
-    try:
-        old = open(LOG).read().split("\n## ") if os.path.exists(LOG) else []
-        keep = [b for b in old if b.strip() and not b.lstrip("# ").startswith(section + "\n")]
-        body = "\n## ".join([b.lstrip("# ").rstrip("\n") for b in keep] + [section + "\n" + "\n".join(lines)])
-        os.makedirs(os.path.dirname(LOG), exist_ok=True)
-        with open(LOG, "w") as f:
-            f.write("## " + body + "\n")
-    except OSError as e:
-        import warnings
-        warnings.warn(f"the error log {LOG} could not be written ({e}); the figures of `{section}` are on stdout only")
-
-
-def judge(section, rows):
-    """rows: (name, gpu distance, floor, resolution[, raw gpu distance relative to the entry's own magnitude]).  Logs all, then
-    asserts all."""
-    lines, bad = [], []
-    for name, got, floor, res, *raw in rows:
-        b = bound(floor, res)
-        lines.append(f"{name:52s} gpu {got:.3e}   floor {floor:.3e}   resolution {res:.3e}   bound {b:.3e}   {'ok' if got <= b else 'MISS'}")
-        if raw:
-            lines[-1] += f"   [own magnitude: gpu {raw[0]:.3e}]"
-        print(section, lines[-1])
-        if not got <= b:
-            bad.append(lines[-1])
-    log_block(section, lines)
-    assert not bad, "\n".join([section] + bad)
+log_block = LOG.replace
+judge = functools.partial(judge_floor, LOG)         # rows: (name, gpu distance, floor, resolution[, raw gpu distance])
 
 
 def fixture_state(tag, b=0):

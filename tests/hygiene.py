@@ -18,6 +18,7 @@ tile past the end passes every value test.  This module takes the allocator out 
   run_case(...)       the whole check for one case: one plain run, one run under each pattern with guarded inputs; outputs
                       bitwise equal across the four runs and finite, guard bands intact, inputs bitwise unchanged after the
                       forward and after the backward.
+  assert_clean(...)   run_case for a test: fails with the case's name and its findings, returns the outputs of the plain run.
 
 Patterns: 0x00; 0xFF (NaN in fp16, fp32 and fp64); 0x7F (fp32 3.396e38: finite, so it survives fmaxf and an integer max of
 bit patterns - the magnitude-bound slots are accumulated that way).
@@ -253,3 +254,10 @@ def run_case(fn, inputs, mutable=(), patterns=tuple(PATTERNS), modules=None):
             elif not torch.equal(o, b):
                 findings.append(f"[{pat}] {k} differs from the plain run: {describe_diff(o, b)}")
     return plain, findings
+
+
+def assert_clean(case, fn, inputs, mutable=()):
+    """run_case, no findings allowed (the first 40 are in the message).  Returns the outputs of the plain run."""
+    out, findings = run_case(fn, inputs, mutable)
+    assert not findings, "\n".join([case] + findings[:40])
+    return out

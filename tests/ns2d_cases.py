@@ -6,39 +6,23 @@ every update (interior, x = 2, x = 0) written once through np.roll: the same ope
 float64 it gives the reference's bits wherever numpy's vector arithmetic does.  It is generic in the dtype: run in
 np.longdouble it is the second evaluation the floors are taken from.
 
-The rule is the project's (tests/control_loop_cases.py): bound = min(16 * max(floor, eps), 1e-9), the floor of a compared field
+The rule is the float64 floor rule of tests/judging.py: bound = min(16 * max(floor, eps), 1e-9), the floor of a compared field
 being the max-norm distance between the float64 and the long-double restatement divided by max|field|.  Nothing is tuned to
 what the kernels give.  Every distance, floor and bound goes to profiles/r15_ns2d_errors.txt before anything is asserted."""
+import functools
 import os
 
 import numpy as np
 
-from tests import control_loop_cases as CL
+from tests.judging import EPS64 as EPS, SectionLog, bound, judge_floor  # noqa: F401  (re-exported to the tests)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG = os.path.join(ROOT, "profiles", "r15_ns2d_errors.txt")
-EPS = CL.EPS
-bound = CL.bound
+LOG = SectionLog(os.path.join(ROOT, "profiles", "r15_ns2d_errors.txt"))
+log_block = LOG.replace
+judge = functools.partial(judge_floor, LOG)
 INFO_KEYS = ("drag_reduction/1_shear_stress", "drag_reduction/2_1_mass_flow", "drag_reduction/2_2_v_velocity",
              "drag_reduction/3_1_pressure_mean", "drag_reduction/3_2_dPdx_required", "drag_reduction/4_1_-|divergence|",
              "drag_reduction/4_2_speed_norm")
-
-
-def _with_log(fn, *a):
-    old = CL.LOG
-    CL.LOG = LOG
-    try:
-        return fn(*a)
-    finally:
-        CL.LOG = old
-
-
-def log_block(section, lines):
-    return _with_log(CL.log_block, section, lines)
-
-
-def judge(section, rows):
-    return _with_log(CL.judge, section, rows)
 
 
 class Grid:

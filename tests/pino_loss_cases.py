@@ -3,7 +3,7 @@ float64 / float32 references, a float32 restatement of the kernels' arithmetic, 
 tests/test_pino_loss_gpu.py (the HIP kernels) and tests/test_pino_loss_reference.py (the same cases and the same comparison on
 the CPU, the restatement standing in for the engine, and five planted faults that must be refused).
 
-Criterion (tests/step_tail_cases.py::accept): with err against oracle/pino_loss_oracle.py in float64 on float64 copies of the
+Criterion (tests/judging.py::accept): with err against oracle/pino_loss_oracle.py in float64 on float64 copies of the
 same float32 inputs,   err_engine == 0 or err_engine < max(FLOOR, BUDGET_SLACK * err_ref32),   err_ref32 being the error of
 the same oracle in float32 on the CPU.  FLOOR = 2e-6 (the gate-field floor) for every quantity; a row is judged only where
 err_ref32 < CAP = 0.1, and only the rows of the floor family steady(0) may be above it (there they are logged).
@@ -18,19 +18,18 @@ error of the reference's reduction and not a budget for the field arithmetic; th
 beside it.  Every row goes to the file $PINO_LOSS_ERROR_LOG names, in the format of the step-tail table."""
 import functools
 import math
-import os
 
 import numpy as np
 import torch
 
 from oracle import pino_loss_oracle as P
 from oracle.detfill import fill_named, name_seed, unit_fill
-from tests.step_tail_cases import FLOOR_GATE, accept, rel_err, same_bits  # noqa: F401  (same_bits: re-exported to the tests)
-from tests.test_parity_gpu import BUDGET_SLACK  # noqa: F401  (the slack inside accept; the floor test applies it to loss_f itself)
+from tests.judging import BUDGET_SLACK, RowLog, accept, rel_err  # noqa: F401  (the floor test applies the slack to loss_f itself)
+from tests.step_tail_cases import FLOOR_GATE, same_bits  # noqa: F401  (same_bits: re-exported to the tests)
 
 FLOOR = FLOOR_GATE
 CAP = 0.1                                   # a float32 reference further than this from float64 measures nothing
-ERROR_LOG_ENV = "PINO_LOSS_ERROR_LOG"
+ROWS = RowLog("PINO_LOSS_ERROR_LOG")
 VISCS = (1.0 / 180.0, 1.0 / 395.0, 1.0 / 40.0)
 IC_WEIGHT, T_INTERVAL = 5.0, 0.5
 PINO_CHUNK = 64                             # fno_abi.hip kPinoChunk: planes per pass of the slab kernels
@@ -327,19 +326,11 @@ def judge(case, tensor, err_engine, err_ref32, floor=FLOOR, who="engine", log_on
     else:
         verdict = "FAIL"
         bad = f"{case} {tensor}: {who} {err_engine:.3e}, float32 reference {err_ref32:.3e}, floor {floor:.1e}"
-    path = os.environ.get(ERROR_LOG_ENV)
-    if path:
-        with open(path, "a") as f:
-            f.write(f"{case:<52s} {tensor:<11s} {who} {err_engine:10.3e}   ref32 {err_ref32:10.3e}   "
-                    f"floor {floor:7.1e}   {verdict}\n")
+    ROWS.row(case, tensor, who, err_engine, err_ref32, f"floor {floor:7.1e}", verdict)
     return bad
 
 
-def log_value(case, tensor, text):
-    path = os.environ.get(ERROR_LOG_ENV)
-    if path:
-        with open(path, "a") as f:
-            f.write(f"{case:<52s} {tensor:<11s} {text}\n")
+log_value = ROWS.write
 
 
 def _d(t):

@@ -3,7 +3,7 @@ FusedAdam.reset_state) is held to: the fixture, the restatements of run_control.
 own dtypes, the closed forms the kernels evaluate, the comparison and the error log.  A helper module, not a conftest; shared
 by tests/test_policy_opt_host.py (CPU) and tests/test_policy_opt_gpu.py.
 
-Comparison (tests/step_tail_cases.accept):  err == 0 or err < max(floor, BUDGET_SLACK * err_ref32), err = relative L2 against
+Comparison (tests/judging.py::accept, judge_budget):  err == 0 or err < max(floor, BUDGET_SLACK * err_ref32), err = relative L2 against
 the float64 restatement, err_ref32 = the error of the reference's own dtypes on the same inputs (float32 oracle networks,
 torch autograd, torch.optim.Adam's float32 arithmetic).  Floor 1e-5 for losses and gradients, none for the elementwise kernels.
 Every figure goes to profiles/r17_policy_opt_errors.txt, one block per case, before anything is asserted.
@@ -16,6 +16,7 @@ The Adam step is judged on the whole flat parameter vector, as the DISPLACEMENT 
 would hide behind |p| >> lr): both float32 evaluations end in one rounding at the parameter's own ulp, which is what the
 displacement's error is made of, and only over many elements do two draws of that rounding have comparable norms (a single
 element, pred_net.fc2.bias, does not), hence the flat vector and not one tensor at a time."""
+import functools
 import math
 import os
 
@@ -23,10 +24,12 @@ import torch
 
 from oracle import observers_oracle as OO
 from tests import action_opt_cases as A
-from tests.step_tail_cases import accept, rel_err        # noqa: F401
+from tests.judging import SectionLog, judge_budget, rejected, rel_err  # noqa: F401  (re-exported to the tests)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG = os.path.join(ROOT, "profiles", "r17_policy_opt_errors.txt")
+LOG = SectionLog(os.path.join(ROOT, "profiles", "r17_policy_opt_errors.txt"))
+log_block = LOG.replace
+judge = functools.partial(judge_budget, LOG, width=52)      # rows: (name, err, err_ref32, floor)
 FLOOR = 1e-5
 RE, LR, BETAS, ADAM_EPS, EPOCHS = 180.0, 1e-4, (0.9, 0.999), 1e-8, 3
 NX = NZ = 32
@@ -36,32 +39,6 @@ KEYS = (["fc0.weight", "fc0.bias"] + [f"multiplicative_net{i}.{n}" for i in (1, 
         + [f"pred_net.sp_convs.{i}.weights{j}" for i in range(4) for j in (1, 2, 3, 4)]
         + [f"pred_net.ws.{i}.{n}" for i in range(4) for n in ("weight", "bias")]
         + [f"pred_net.{fc}.{n}" for fc in ("fc1", "fc2") for n in ("weight", "bias")])
-
-
-def log_block(section, lines):
-    """replace `section` of the error log by `lines` (one file, one block per case), as action_opt_cases.log_block"""
-    keep, A.LOG = A.LOG, LOG
-    try:
-        A.log_block(section, lines)
-    finally:
-        A.LOG = keep
-
-
-def judge(section, rows, who="engine"):
-    """rows: (name, err, err_ref32, floor).  Logs all, then asserts all."""
-    lines, bad = [], []
-    for name, err, ref, floor in rows:
-        ok = accept(err, ref, floor)
-        lines.append(f"{name:52s} {who} {err:10.3e}   ref32 {ref:10.3e}   floor {floor:7.1e}   {'ok' if ok else 'MISS'}")
-        print(section, lines[-1])
-        if not ok:
-            bad.append(lines[-1])
-    log_block(section, lines)
-    assert not bad, "\n".join([section] + bad)
-
-
-def rejected(rows):
-    return [name for name, err, ref, floor in rows if not accept(err, ref, floor)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -4,8 +4,8 @@ error table.  Shared by tests/test_spec_conv_gpu.py (the HIP kernels, each case 
 tests/test_spec_conv_reference.py (the float32 oracle alone, and planted faults that the slices must refuse).
 
 Evaluations: ref64 = oracle/fno_oracle.py on float64 copies of the float32 inputs, ref32 = the same oracle in float32 on the
-CPU, and the engine.  Criterion (tests/step_tail_cases.py::accept, the numbers of DESIGN 4l / 4n) for every quantity:
-    e_engine == 0 or e_engine < max(FLOOR = 2e-6, BUDGET_SLACK = 1.75 * e_ref32),
+CPU, and the engine.  Criterion (tests/judging.py::accept, the numbers of DESIGN 4l / 4n) for every quantity:
+    e_engine == 0 or e_engine < max(FLOOR, BUDGET_SLACK * e_ref32),   FLOOR = 2e-6,
 both errors taken against ref64, a sliced quantity being the WORST slice of the engine against the WORST slice of ref32.
 The whole-tensor line of tests/test_parity_gpu.py (relative L2 against ref32 under TOL_COMP = 5e-6) is judged beside it.
 
@@ -26,7 +26,6 @@ structurally zero - planes [live, wl) of dialect C in 3-D, the first corner's ro
 BE zero and are left out of the slices.  dbias: worst channel, |error| over rms(dy) sqrt(B PW) (the size of a sum of B PW terms).
 Every row goes to the file $SPEC_CONV_ERROR_LOG names."""
 import functools
-import os
 import typing
 
 import numpy as np
@@ -35,11 +34,11 @@ import torch.nn.functional as TF
 
 from oracle import fno_oracle as O
 from oracle.detfill import fill_named
-from tests.step_tail_cases import FLOOR_GATE, accept, rel_err
-from tests.test_parity_gpu import BUDGET_SLACK, TOL_COMP  # noqa: F401
+from tests.judging import TOL_COMP, RowLog, accept, rel_err
+from tests.step_tail_cases import FLOOR_GATE
 
 FLOOR = FLOOR_GATE
-ERROR_LOG_ENV = "SPEC_CONV_ERROR_LOG"
+ROWS = RowLog("SPEC_CONV_ERROR_LOG", widths=(26, 14))
 NORM = {"A": "forward", "B": "ortho", "C": "backward"}
 
 
@@ -276,11 +275,8 @@ def dbias_error(case, a, ref64, dy):
 def judge(case, quantity, err, err_ref32, who="engine", floor=FLOOR, fixed=None):
     """One row of the table and a description of the failure, or None.  fixed: a plain bound instead of the budget."""
     ok = (err < fixed) if fixed is not None else accept(err, err_ref32, floor)
-    path = os.environ.get(ERROR_LOG_ENV)
-    if path:
-        with open(path, "a") as f:
-            bound = f"bound {fixed:7.1e}" if fixed is not None else f"floor {floor:7.1e}"
-            f.write(f"{case:<26s} {quantity:<14s} {who} {err:10.3e}   ref32 {err_ref32:10.3e}   {bound}   {'ok' if ok else 'FAIL'}\n")
+    ROWS.row(case, quantity, who, err, err_ref32, f"bound {fixed:7.1e}" if fixed is not None else f"floor {floor:7.1e}",
+             "ok" if ok else "FAIL")
     return None if ok else f"{case} [{quantity}] {who} {err:.3e}, float32 reference {err_ref32:.3e}, " + \
         (f"bound {fixed:.1e}" if fixed is not None else f"floor {floor:.1e}")
 

@@ -3,12 +3,11 @@ float32 torch references, the one comparison, and the error table.  Shared by te
 on the GPU) and tests/test_step_tail_reference.py (the same cases and the same comparison on the CPU, with a float32
 restatement of each kernel's arithmetic standing in for the engine - and with three planted faults that must be rejected).
 
-Criterion (tests/test_parity_gpu.py::_within_budget): with err = relative L2 against plain torch in float64 on float64 copies
-of the same float32 inputs,   err_engine < max(floor, BUDGET_SLACK * err_ref32),   err_ref32 being the error of the same
-torch expressions in float32.  Floors: 2e-6 gate fields, 2e-5 the four scalar-bias gradients, 1e-5 loss value and gradient,
-none for Adam's p / exp_avg / exp_avg_sq.  A result that equals the float64 one exactly (err_engine == 0: an all-zero
-gradient without weight decay, a bias gradient with h = 0) is inside any budget - there 0 < 1.75 * 0 would refuse a perfect
-answer.  NaN compares false and is refused.
+Criterion (tests/judging.py::accept, the float32-budget rule): with err = relative L2 against plain torch in float64 on float64
+copies of the same float32 inputs,   err_engine == 0 or err_engine < max(floor, BUDGET_SLACK * err_ref32),   err_ref32 being the
+error of the same torch expressions in float32.  Floors: 2e-6 gate fields, 2e-5 the four scalar-bias gradients, 1e-5 loss value
+and gradient, none for Adam's p / exp_avg / exp_avg_sq.  The exact results the rule's first clause is there for: an all-zero
+gradient without weight decay, a bias gradient with h = 0.
 
 Adam at n <= 5 runs ADAM_TINY_K independent instances of the n-element problem (the engine once per instance, each in its
 own 8-float slot of the buffers) and pools them into one error: with no floor, the ratio of two float32 roundings of one to
@@ -16,37 +15,20 @@ five numbers is a coin toss, the ratio over 256 draws of them is not; every elem
 path, and the slots' padding must come back untouched."""
 import itertools
 import math
-import os
 
 import torch
 
-from tests.test_parity_gpu import BUDGET_SLACK
+from tests.judging import RowLog, accept, rel_err  # noqa: F401  (re-exported to the tests)
 
 FLOOR_GATE, FLOOR_GATE_BIAS, FLOOR_LOSS, FLOOR_ADAM = 2e-6, 2e-5, 1e-5, 0.0
-ERROR_LOG_ENV = "STEP_TAIL_ERROR_LOG"       # names a file: one line per (case, tensor) appended to it
-
-
-def rel_err(a, ref64):
-    """relative L2 of `a` against the float64 reference, evaluated in float64 where the reference lives"""
-    b = ref64.detach().to(torch.float64)
-    a = a.detach().to(device=b.device, dtype=torch.float64)
-    den = float(b.norm())
-    return float((a - b).norm()) / (den if den > 0 else 1.0)
-
-
-def accept(err_engine, err_ref32, floor):
-    return err_engine == 0.0 or err_engine < max(floor, BUDGET_SLACK * err_ref32)
+ROWS = RowLog("STEP_TAIL_ERROR_LOG")         # names a file: one line per (case, tensor) appended to it
 
 
 def judge(case, tensor, err_engine, err_ref32, floor, who="engine"):
     """Record one row of the error table (appended to the file $STEP_TAIL_ERROR_LOG names) and return a description of the
     failure, or None.  Callers collect the failures of a case and assert once, so that every row of the case is recorded."""
     ok = accept(err_engine, err_ref32, floor)
-    path = os.environ.get(ERROR_LOG_ENV)
-    if path:
-        with open(path, "a") as f:
-            f.write(f"{case:<52s} {tensor:<11s} {who} {err_engine:10.3e}   ref32 {err_ref32:10.3e}   "
-                    f"floor {floor:7.1e}   {'ok' if ok else 'FAIL'}\n")
+    ROWS.row(case, tensor, who, err_engine, err_ref32, f"floor {floor:7.1e}", "ok" if ok else "FAIL")
     return None if ok else f"{case} {tensor}: {who} {err_engine:.3e}, float32 reference {err_ref32:.3e}, floor {floor:.1e}"
 
 

@@ -12,17 +12,9 @@ import torch
 from tests import action_opt_cases as A
 from tests import chanflow_step_reference as R
 from tests import control_loop_cases as K
+from tests.judging import EPS64, dev, judge_floor  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-EPS64 = float(np.finfo(np.float64).eps)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _plane_stats(plane, seed=3):
@@ -297,13 +289,12 @@ def _gpu_record(pol, b):
 
 @pytest.mark.parametrize("reg", [0.0, 0.1])
 @pytest.mark.parametrize("B", [1, 2])
-def test_policy_on_control_loop(dev, observer_fixture, B, reg, monkeypatch):
+def test_policy_on_control_loop(dev, observer_fixture, B, reg):
     """two control iterations: displacement, per-epoch loss and final opV2 against the float64 restatement fed the GPU's own
     start action, under the rule; opV1 is opposition control bit for bit; state and dPdx after the step against the
-    restated rollout fed the GPU's own actions, under control_loop_cases.judge.  (The environment has Re = -1, which the
-    policy hands to the observer as the reference would.)"""
+    restated rollout fed the GPU's own actions, under the float64 floor rule, in the same table.  (The environment has
+    Re = -1, which the policy hands to the observer as the reference would.)"""
     from pde_policylearning_amd.control import ControlLoop, OptimalObserverPolicy
-    monkeypatch.setattr(K, "LOG", A.LOG)              # control_loop_cases.judge writes this case's state rows to the r16 log too
     g, states, norm, mean, std = _setup()
     env = K.make_env(dev, g, states[:B], PLANE)
     pol = OptimalObserverPolicy(observer_fixture[0], norm, reg_weight=reg)
@@ -332,7 +323,7 @@ def test_policy_on_control_loop(dev, observer_fixture, B, reg, monkeypatch):
         pert = K.restated_rollout(g, states[b], steps, actions=mine, perturb=21 + b)
         gpu = [{"state": tuple(x[b] for x in after[t][0]), "dPdx": float(after[t][1][b]), "obs": obs[t][b]} for t in range(steps)]
         srows += K.loop_rows(g, f"[{b}]", gpu, base, pert)
-    K.judge(f"optimal-observer policy B={B} reg={reg:g}: state", srows)
+    judge_floor(A.LOG, f"optimal-observer policy B={B} reg={reg:g}: state", srows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

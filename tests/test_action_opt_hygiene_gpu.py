@@ -14,23 +14,10 @@ import torch
 
 from tests import action_opt_cases as A
 from tests import hygiene as H
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1, 1), (2, 3, 257), (3, 3, 1024), (2, 2, 1020)]          # (B, P, plane)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def _run(case, fn, inputs, mutable=()):
-    out, findings = H.run_case(fn, inputs, mutable)
-    assert not findings, "\n".join([case] + findings[:40])
-    return out
 
 
 def _inputs(dev, B, P, plane):
@@ -54,7 +41,7 @@ def test_begin_and_finish(dev, B, P, plane):
         opV2 = F.ctrl_action_finish(inp["a0"], shape=(B, plane, 1))
         after_forward()
         return {"a": a, "x channel 0": x[:, 0], "x dense": dense, "opV2": opV2}
-    _run(f"ctrl_action_begin / _finish B={B} plane={plane}", fn, _inputs(dev, B, P, plane))
+    H.assert_clean(f"ctrl_action_begin / _finish B={B} plane={plane}", fn, _inputs(dev, B, P, plane))
 
 
 @pytest.mark.parametrize("B,P,plane", SHAPES)
@@ -65,7 +52,7 @@ def test_objective(dev, B, P, plane):
         parts, dy = F.ctrl_action_objective(inp["y"], inp["a0"], inp["mean"], inp["std"], A.EPS, reg=0.1)
         after_forward()
         return {"parts": parts, "dy": dy}
-    _run(f"ctrl_action_objective B={B} P={P} plane={plane}", fn, _inputs(dev, B, P, plane))
+    H.assert_clean(f"ctrl_action_objective B={B} P={P} plane={plane}", fn, _inputs(dev, B, P, plane))
 
 
 @pytest.mark.parametrize("B,P,plane", SHAPES)
@@ -83,7 +70,7 @@ def test_update(dev, B, P, plane):
             F.ctrl_action_update(dx, parts, inp["mean"], inp["std"], A.EPS, a, m, v, x, step, reg=0.1, batch_stride=3 * plane)
         after_forward()
         return {"a": a, "exp_avg": m, "exp_avg_sq": v, "x channel 0": x[:, 0]}
-    _run(f"ctrl_action_update B={B} plane={plane}", fn, _inputs(dev, B, P, plane))
+    H.assert_clean(f"ctrl_action_update B={B} plane={plane}", fn, _inputs(dev, B, P, plane))
 
 
 @pytest.mark.parametrize("B,cin,C,plane", [(1, 1, 64, 1024), (2, 4, 32, 128), (3, 1, 32, 3072)])
@@ -99,4 +86,4 @@ def test_lifting_input_gradient(dev, B, cin, C, plane):
         after_forward()
         dx, dw, db = torch.autograd.grad(y, (inp["x"], inp["w"], inp["b"]), inp["dy"])
         return {"y": y, "dx": dx, "dw": dw, "db": db}
-    _run(f"lifting with dx B={B} cin={cin} C={C} plane={plane}", fn, inputs)
+    H.assert_clean(f"lifting with dx B={B} cin={cin} C={C} plane={plane}", fn, inputs)

@@ -9,19 +9,12 @@ import pytest
 import torch
 
 from oracle import fno_oracle as O
+from tests.judging import dev  # noqa: F401
 from tests.util import load_golden, rebuild_params, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5          # north star: relative L2, outputs and gradients
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _t(a, dev, grad=False):

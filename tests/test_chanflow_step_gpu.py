@@ -1,7 +1,7 @@
 """Channel-flow environment step on the GPU against the float64 restatement of tests/chanflow_step_reference.py.
 
-Tolerances.  Nothing here is tuned to what the kernels give.  For every compared quantity the test first measures, on the CPU
-and at the size at hand, the FLOOR: the distance between the restatement solved by dense numpy.linalg.solve and the same
+Tolerances (the float64 floor rule, tests/judging.py).  Nothing here is tuned to what the kernels give.  For every compared
+quantity the test first measures, on the CPU and at the size at hand, the FLOOR: the distance between the restatement solved by dense numpy.linalg.solve and the same
 restatement solved by a float64 Thomas recurrence.  The GPU gets 16 x that floor (its transforms sum in another order and
 contract to FMA), never more than 1e-9 = cond * eps of the worst Poisson system (7e6 x 1.1e-16).  Two remarks on the floor:
   - a floor cannot be below the resolution of the number format: two float64 evaluations of one quantity differ by eps =
@@ -15,97 +15,29 @@ contract to FMA), never more than 1e-9 = cond * eps of the worst Poisson system 
 Every measured value goes to profiles/r11_chanflow_step_errors.txt: floor, resolution, bound and GPU distance, beside them the
 bound of the plain rule (16 x the measured floor, cap 1e-9, no resolution) and, for the entries measured against a scale, the
 raw errors relative to the entry's own magnitude - so that what the two remarks loosen stays visible."""
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.detfill import fill_named
 from tests import chanflow_step_reference as R
-from tests.util import load_golden
+from tests import control_loop_cases as K
+from tests.judging import CAP64, EPS64, SectionLog, dev, judge_floor  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOG = os.path.join(ROOT, "profiles", "r11_chanflow_step_errors.txt")
-EPS = float(np.finfo(np.float64).eps)
-CAP = 1e-9
-DT = 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    torch.set_num_threads(min(torch.get_num_threads(), 16))
-    return torch.device("cuda:0")
+LOG = SectionLog(os.path.join(ROOT, "profiles", "r11_chanflow_step_errors.txt"))
+DT = K.DT
+_log = LOG.replace
+# rows: (name, gpu distance, floor, resolution[, (raw gpu, raw floor)]), with the plain rule's bound beside each (module docstring)
+_judge = functools.partial(judge_floor, LOG, width=46, plain_rule=True)
 
 
 def _F():
     from pde_policylearning_amd import functional as F
     return F
-
-
-def _log(section, lines):
-    """replace `section` of the error log by `lines` (one file, one block per test case)"""
-    try:
-        old = open(LOG).read().split("\n## ") if os.path.exists(LOG) else []
-        keep = [b for b in old if b.strip() and not b.lstrip("# ").startswith(section + "\n")]
-        body = "\n## ".join([b.lstrip("# ").rstrip("\n") for b in keep] + [section + "\n" + "\n".join(lines)])
-        os.makedirs(os.path.dirname(LOG), exist_ok=True)
-        with open(LOG, "w") as f:
-            f.write("## " + body + "\n")
-    except OSError as e:
-        import warnings
-        warnings.warn(f"the error log {LOG} could not be written ({e}); the figures of `{section}` are on stdout only")
-
-
-def bound(floor, resolution=EPS):
-    return min(16.0 * max(floor, resolution), CAP)
-
-
-def _judge(section, rows):
-    """rows: (name, gpu distance, floor, resolution[, (raw gpu, raw floor)]), raw = relative to the entry's own magnitude where
-    the distance is measured against a scale.  Logs all, then asserts all."""
-    lines, bad = [], []
-    for name, got, floor, res, *raw in rows:
-        b = bound(floor, res)
-        lines.append(f"{name:46s} gpu {got:.3e}   floor {floor:.3e}   resolution {res:.3e}   bound {b:.3e}   {'ok' if got <= b else 'MISS'}"
-                     f"   [plain rule: bound {min(16 * floor, CAP):.3e}]")
-        if raw:
-            lines[-1] += f"   [own magnitude: gpu {raw[0][0]:.3e}   floor {raw[0][1]:.3e}   plain-rule bound {min(16 * raw[0][1], CAP):.3e}]"
-        print(section, lines[-1])
-        if not got <= b:
-            bad.append(lines[-1])
-    _log(section, lines)
-    assert not bad, "\n".join([section] + bad)
-
-
-def _fixture_state(tag, b=0):
-    """the deterministic sample behind tests/golden/chanflow_<tag>.npz in float64 (V's wall planes are random like the rest);
-    b > 0: further samples of a batch"""
-    Nx, Ny, Nz = (int(v) for v in load_golden("chanflow_" + tag)["meta"][:3])
-    sfx = f"{tag}" if b == 0 else f"{tag}.b{b}"
-    f = lambda n, shp, s: fill_named(f"input:chanflow.{n}.{sfx}", shp, s, dtype=np.float64)
-    U = 1.0 + f("U", (Nx, Ny + 1, Nz), 0.5)
-    V = f("Vgt", (Nx, Ny, Nz), 0.3) + f("dV", (Nx, Ny, Nz), 0.1)
-    W = f("W", (Nx, Ny + 1, Nz), 0.3)
-    return R.Grid(Nx, Ny, Nz), U, V, W
-
-
-def _engine(g):
-    F = _F()
-    grid = F.ChannelGrid(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, g.yg, g.nu)
-    return grid, F.ChannelPoisson(grid)
-
-
-def _dev(dev, *arrs):
-    return [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrs]
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -117,18 +49,18 @@ def test_projection_parity_and_property(dev, tag, B):
     discrete divergence is at most 1e-10 of the largest divergence entry before (every wavenumber pair but (0,0) is solved
     exactly; (0,0) is singular-regularised).  The restatement itself is held to the same property first."""
     F = _F()
-    states = [_fixture_state(tag, b) for b in range(B)]
+    states = [K.fixture_state(tag, b) for b in range(B)]
     g = states[0][0]
-    grid, poisson = _engine(g)
-    U, V, W = _dev(dev, *[np.stack([s[k] for s in states]) for k in (1, 2, 3)])
+    grid, poisson = K.engine(g)
+    U, V, W = K.to_dev(dev, *[np.stack([s[k] for s in states]) for k in (1, 2, 3)])
     F.chanflow_project(grid, poisson, U, V, W)
-    got = [_np(t) for t in (U, V, W)]
+    got = [K.to_np(t) for t in (U, V, W)]
     rows, prop = [], []
     for b, (_, U0, V0, W0) in enumerate(states):
         dense, thomas = R.project(g, U0, V0, W0), R.project(g, U0, V0, W0, "thomas")
         for n, k in (("U", 0), ("V", 1), ("W", 2)):
-            rows.append((f"{n}[{b}]", R.rel(got[k][b], dense[k]), R.rel(thomas[k], dense[k]), EPS))
-        rows.append((f"p_hat[{b}] (floor only)", 0.0, R.rel(thomas[3], dense[3]), EPS))
+            rows.append((f"{n}[{b}]", R.rel(got[k][b], dense[k]), R.rel(thomas[k], dense[k]), EPS64))
+        rows.append((f"p_hat[{b}] (floor only)", 0.0, R.rel(thomas[3], dense[3]), EPS64))
         before = np.abs(R.divergence(g, U0, V0, W0)).max()
         off = lambda X: np.abs((lambda d: d - d.mean(axis=(0, 2), keepdims=True))(R.divergence(g, *X))).max() / before
         prop.append((b, off(dense[:3]), off([got[0][b], got[1][b], got[2][b]])))
@@ -146,29 +78,25 @@ def test_projection_parity_and_property(dev, tag, B):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 3: one RK3 step
 # ---------------------------------------------------------------------------------------------------------------------------
-def _dpdx_resolution(m0, dpdx):
-    return EPS * abs(m0) / DT / abs(dpdx)
-
-
 @pytest.mark.parametrize("tag", ["small", "odd", "shipped"])
 @pytest.mark.parametrize("control", ["opposition", "opV1_zero"])
 def test_rk3_step(dev, tag, control):
     F = _F()
-    g, U0, V0, W0 = _fixture_state(tag)
-    grid, poisson = _engine(g)
+    g, U0, V0, W0 = K.fixture_state(tag)
+    grid, poisson = K.engine(g)
     v1, v2 = R.gt_control(V0, min(10, g.Ny // 3))
     if control == "opV1_zero":
         v1 = np.zeros_like(v1)
     m0 = R.bulk_velocity(g, U0) * 1.001              # so that the pressure-gradient update has something to hold
     dense = R.rk3_step(g, U0, V0, W0, v1, v2, R.DPDX0, m0, DT)
     thomas = R.rk3_step(g, U0, V0, W0, v1, v2, R.DPDX0, m0, DT, "thomas")
-    U, V, W, a1, a2 = _dev(dev, U0[None], V0[None], W0[None], v1[None], v2[None])
+    U, V, W, a1, a2 = K.to_dev(dev, U0[None], V0[None], W0[None], v1[None], v2[None])
     dp = torch.full((1,), R.DPDX0, dtype=torch.float64, device=dev)
     mu = torch.full((1,), m0, dtype=torch.float64, device=dev)
     F.chanflow_rk3_step(grid, poisson, U, V, W, a1, a2, dp, mu, DT)
-    got = [_np(U)[0], _np(V)[0], _np(W)[0], _np(dp)[0]]
-    rows = [(n, R.rel(got[k], dense[k]), R.rel(thomas[k], dense[k]), EPS) for k, n in enumerate("UVW")]
-    rows.append(("dPdx", R.rel(got[3], dense[3]), R.rel(thomas[3], dense[3]), _dpdx_resolution(m0, dense[3])))
+    got = [K.to_np(U)[0], K.to_np(V)[0], K.to_np(W)[0], K.to_np(dp)[0]]
+    rows = [(n, R.rel(got[k], dense[k]), R.rel(thomas[k], dense[k]), EPS64) for k, n in enumerate("UVW")]
+    rows.append(("dPdx", R.rel(got[3], dense[3]), R.rel(thomas[3], dense[3]), K.dpdx_resolution(m0, dense[3])))
     assert np.array_equal(got[1][:, 0], v1) and np.array_equal(got[1][:, -1], v2)       # the wall condition holds exactly
     _judge(f"rk3 step {tag} {control}", rows)
 
@@ -181,13 +109,13 @@ def test_rollout_small(dev):
     state carries a relative 1e-16 seeded perturbation.  At every step the GPU state (U, V, W as one vector) stays within
     16 x the distance between the two CPU runs."""
     F = _F()
-    g, U0, V0, W0 = _fixture_state("small")
-    grid, poisson = _engine(g)
+    g, U0, V0, W0 = K.fixture_state("small")
+    grid, poisson = K.engine(g)
     plane, steps = 3, 20
     m0 = R.bulk_velocity(g, U0)
     rng = np.random.default_rng(11)
     cpu = [(U0, V0, W0, R.DPDX0), tuple(a * (1 + 1e-16 * rng.standard_normal(a.shape)) for a in (U0, V0, W0)) + (R.DPDX0,)]
-    U, V, W = _dev(dev, U0[None], V0[None], W0[None])
+    U, V, W = K.to_dev(dev, U0[None], V0[None], W0[None])
     dp = torch.full((1,), R.DPDX0, dtype=torch.float64, device=dev)
     mu = torch.full((1,), m0, dtype=torch.float64, device=dev)
     cat = lambda s: np.concatenate([np.asarray(a).ravel() for a in s[:3]])
@@ -196,9 +124,9 @@ def test_rollout_small(dev):
         cpu = [R.rk3_step(g, *s[:3], *R.gt_control(s[1], plane), s[3], m0, DT) for s in cpu]
         F.chanflow_rk3_step(grid, poisson, U, V, W, -V[:, :, plane, :], -V[:, :, -plane, :], dp, mu, DT)
         floor = R.rel(cat(cpu[1]), cat(cpu[0]))
-        got = R.rel(cat([_np(U)[0], _np(V)[0], _np(W)[0]]), cat(cpu[0]))
-        ok = got <= min(16 * floor, CAP)
-        lines.append(f"step {it + 1:2d}   cpu perturbed vs cpu {floor:.3e}   gpu vs cpu {got:.3e}   bound {min(16 * floor, CAP):.3e}   {'ok' if ok else 'MISS'}")
+        got = R.rel(cat([K.to_np(U)[0], K.to_np(V)[0], K.to_np(W)[0]]), cat(cpu[0]))
+        ok = got <= min(16 * floor, CAP64)
+        lines.append(f"step {it + 1:2d}   cpu perturbed vs cpu {floor:.3e}   gpu vs cpu {got:.3e}   bound {min(16 * floor, CAP64):.3e}   {'ok' if ok else 'MISS'}")
         print(lines[-1])
         if not ok:
             bad.append(lines[-1])
@@ -209,33 +137,23 @@ def test_rollout_small(dev):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 5: wall pressure, diagnostics, the environment's step
 # ---------------------------------------------------------------------------------------------------------------------------
-def _info_scales(g, U, V, W, p2):
-    """what one rounding of each `info` entry is relative to (module docstring); None: the entry's own magnitude"""
-    hy = np.diff(g.y)[None, :, None]
-    grads = np.abs((np.roll(U, -1, 0) - U)[:, 1:-1] / g.dx).sum() + np.abs((V[:, 1:] - V[:, :-1]) / hy).sum() + \
-        np.abs((np.roll(W, -1, 2) - W)[:, 1:-1] / g.dz).sum()
-    shear = np.mean(np.abs(U[:, -1] * V[:, -1]) + np.abs(g.nu * (U[:, -2] - U[:, -3]) / (g.y[-1] - g.y[-2])))
-    return {"drag_reduction/4_1_-|divergence|": grads, "drag_reduction/1_shear_stress": shear,
-            "drag_reduction/3_1_pressure_mean": np.abs(p2).mean()}
-
-
 @pytest.mark.parametrize("tag", ["small", "odd", "shipped"])
 def test_wall_pressure_and_step_info(dev, tag):
     """p1, p2, the full P of cal_pressure and every `info` key of ChannelFlowEnv.step against the restatement"""
     from pde_policylearning_amd.libs.envs.control_env import ChannelFlowEnv
-    g, U0, V0, W0 = _fixture_state(tag)
+    g, U0, V0, W0 = K.fixture_state(tag)
     env = ChannelFlowEnv(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, U0, V0, W0, dt=DT, detect_plane=min(10, g.Ny // 3), device=dev)
     m0 = R.bulk_velocity(g, U0)
-    rows = [("meanU0", abs(float(env.meanU0[0]) - m0) / abs(m0), 0.0, EPS)]
+    rows = [("meanU0", abs(float(env.meanU0[0]) - m0) / abs(m0), 0.0, EPS64)]
     dense, thomas = R.pressure(g, U0, V0, W0, R.DPDX0), R.pressure(g, U0, V0, W0, R.DPDX0, "thomas")
     p1, p2 = env.get_boundary_pressures()
     P = env.cal_pressure()
     assert tuple(P.shape) == (g.Nx, g.Ny - 1, g.Nz)
     for n, t, k in (("p1", p1, 0), ("p2", p2, 1), ("P", P, 2)):
-        rows.append((n, R.rel(_np(t), dense[k]), R.rel(thomas[k], dense[k]), EPS))
+        rows.append((n, R.rel(K.to_np(t), dense[k]), R.rel(thomas[k], dense[k]), EPS64))
     v1, v2 = env.gt_control()
     w1, w2 = R.gt_control(V0, env.detect_plane)
-    assert np.array_equal(_np(v1), w1) and np.array_equal(_np(v2), w2)
+    assert np.array_equal(K.to_np(v1), w1) and np.array_equal(K.to_np(v2), w2)
     p2g, div, done, info = env.step(v1, v2)
     assert done is False and div == info["drag_reduction/4_1_-|divergence|"]
     ref = {}
@@ -243,13 +161,13 @@ def test_wall_pressure_and_step_info(dev, tag):
         U, V, W, dp = R.rk3_step(g, U0, V0, W0, w1, w2, R.DPDX0, m0, DT, solver)
         p2r = R.pressure(g, U, V, W, dp, solver)[1]
         ref[name] = (R.step_info(g, U, V, W, p2r, dp), p2r, (U, V, W))
-    rows.append(("step p2", R.rel(_np(p2g), ref["dense"][1]), R.rel(ref["thomas"][1], ref["dense"][1]), EPS))
-    scales = _info_scales(g, *ref["dense"][2], ref["dense"][1])
+    rows.append(("step p2", R.rel(K.to_np(p2g), ref["dense"][1]), R.rel(ref["thomas"][1], ref["dense"][1]), EPS64))
+    scales = K.info_scales(g, *ref["dense"][2], ref["dense"][1])
     assert set(R.INFO_KEYS) <= set(info)
     for k in R.INFO_KEYS:
         want, alt = ref["dense"][0][k], ref["thomas"][0][k]
         s = scales.get(k, abs(want))
-        res = _dpdx_resolution(m0, want) if k.endswith("dPdx_reverse_cal") else EPS
+        res = K.dpdx_resolution(m0, want) if k.endswith("dPdx_reverse_cal") else EPS64
         own = abs(want) if want != 0 else 1.0
         rows.append((k, abs(info[k] - want) / s, abs(alt - want) / s, res, (abs(info[k] - want) / own, abs(alt - want) / own)))
     rel_keys = [k for k in info if k.startswith("drag_reduction_relative")]
@@ -262,7 +180,7 @@ def test_env_graph_mode_and_state_files(dev, tmp_path):
     p2 survives the next step, dump_state / load_state round-trip through the environment and the graph is rebuilt after
     load_state; the host view of dPdx follows the device value."""
     from pde_policylearning_amd.libs.envs.control_env import ChannelFlowEnv
-    g, U0, V0, W0 = _fixture_state("small")
+    g, U0, V0, W0 = K.fixture_state("small")
     mk = lambda graph: ChannelFlowEnv(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, U0, V0, W0, dt=DT, detect_plane=3, device=dev, graph=graph)
     eager, graphed = mk(False), mk(True)
     assert eager.dPdx == R.DPDX0
@@ -272,24 +190,24 @@ def test_env_graph_mode_and_state_files(dev, tmp_path):
         for env in (eager, graphed):
             p2, div, done, info = env.step(*env.gt_control())
             outs.append((p2, info))
-        assert _bits_equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1], f"step {it}"
+        assert K.bits_equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1], f"step {it}"
         kept.append((outs[1][0], outs[1][0].clone()))
         for n in ("U", "V", "W", "dPdx_dev"):
-            assert _bits_equal(getattr(eager, n), getattr(graphed, n)), n
-    assert all(_bits_equal(a, b) for a, b in kept), "a returned p2 was overwritten by a later step"
+            assert K.bits_equal(getattr(eager, n), getattr(graphed, n)), n
+    assert all(K.bits_equal(a, b) for a, b in kept), "a returned p2 was overwritten by a later step"
     assert eager.dPdx == float(eager.dPdx_dev[0]) != R.DPDX0
     Fu = eager.compute_rhs_py(eager.U[0], eager.V[0], eager.W[0])[0]
-    assert _bits_equal(Fu, eager.compute_rhs_py(eager.U[0], eager.V[0], eager.W[0], eager.dPdx)[0])
+    assert K.bits_equal(Fu, eager.compute_rhs_py(eager.U[0], eager.V[0], eager.W[0], eager.dPdx)[0])
     path = str(tmp_path / "state.mat")
     eager.dump_state(path)
     for env in (eager, graphed):
         before = [t.clone() for t in (eager.U, eager.V, eager.W)]
         env.load_state(path)
         for a, n in zip(before, "UVW"):
-            assert _bits_equal(a, getattr(env, n)), n
+            assert K.bits_equal(a, getattr(env, n)), n
     graphed.dPdx_dev.copy_(eager.dPdx_dev)
     pe, pg = eager.step(*eager.gt_control())[0], graphed.step(*graphed.gt_control())[0]
-    assert _bits_equal(pe, pg) and _bits_equal(eager.U, graphed.U)
+    assert K.bits_equal(pe, pg) and K.bits_equal(eager.U, graphed.U)
     z = ChannelFlowEnv(g.Nx, g.Nz, g.dx, g.dz, g.y, g.ym, U0, V0 * 0, W0, dt=DT, detect_plane=3, device=dev)
     z.V_gt.zero_()
     assert np.isfinite(z.reward_gt())                    # a zero reference field costs 0, not nan
@@ -298,19 +216,15 @@ def test_env_graph_mode_and_state_files(dev, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 6: batch, graph, repeatability
 # ---------------------------------------------------------------------------------------------------------------------------
-def _bits_equal(a, b):
-    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
 def test_batch_graph_and_repeatability_are_bitwise(dev):
     F = _F()
-    states = [_fixture_state("shipped", b) for b in range(3)]
+    states = [K.fixture_state("shipped", b) for b in range(3)]
     g = states[0][0]
-    grid, poisson = _engine(g)
+    grid, poisson = K.engine(g)
     plane = 10
 
     def run(idx, steps, graphed=False):
-        U, V, W = _dev(dev, *[np.stack([states[b][k] for b in idx]) for k in (1, 2, 3)])
+        U, V, W = K.to_dev(dev, *[np.stack([states[b][k] for b in idx]) for k in (1, 2, 3)])
         dp = torch.full((len(idx),), R.DPDX0, dtype=torch.float64, device=dev)
         mu = torch.tensor([R.bulk_velocity(g, states[b][1]) for b in idx], dtype=torch.float64, device=dev)
         if graphed:
@@ -328,11 +242,11 @@ def test_batch_graph_and_repeatability_are_bitwise(dev):
     whole = run([0, 1, 2], 2)
     for b in range(3):
         for a, w in zip(run([b], 2), whole):
-            assert _bits_equal(a[0], w[b]), f"sample {b} of a batch differs from the single run"
+            assert K.bits_equal(a[0], w[b]), f"sample {b} of a batch differs from the single run"
     eager, again, graph = run([0], 10), run([0], 10), run([0], 10, graphed=True)
     for a, b, c in zip(eager, again, graph):
-        assert _bits_equal(a, b), "two runs from one state differ"
-        assert _bits_equal(a, c), "graph replay differs from eager"
+        assert K.bits_equal(a, b), "two runs from one state differ"
+        assert K.bits_equal(a, c), "graph replay differs from eager"
     assert all(torch.isfinite(t).all() for t in eager)
 
 
@@ -342,9 +256,9 @@ def test_batch_graph_and_repeatability_are_bitwise(dev):
 def test_refusals_launch_nothing(dev):
     F = _F()
     from pde_policylearning_amd import _lib
-    g, U0, V0, W0 = _fixture_state("small")
-    grid, poisson = _engine(g)
-    U, V, W = _dev(dev, U0[None], V0[None], W0[None])
+    g, U0, V0, W0 = K.fixture_state("small")
+    grid, poisson = K.engine(g)
+    U, V, W = K.to_dev(dev, U0[None], V0[None], W0[None])
     keep = [t.clone() for t in (U, V, W)]
     lib = _lib.lib()
     lib.fno_profile_reset()
@@ -380,9 +294,9 @@ def test_every_power_of_two_projects(dev, N):
     F = _F()
     g = R.Grid(N, 6, N)
     U0, V0, W0 = R.analytic_state(g, N, noise=0.2)
-    grid, poisson = _engine(g)
-    U, V, W = _dev(dev, U0[None], V0[None], W0[None])
+    grid, poisson = K.engine(g)
+    U, V, W = K.to_dev(dev, U0[None], V0[None], W0[None])
     F.chanflow_project(grid, poisson, U, V, W)
     dense, thomas = R.project(g, U0, V0, W0), R.project(g, U0, V0, W0, "thomas")
     _judge(f"projection parity {N} x 6 x {N}",
-           [(n, R.rel(_np(t)[0], dense[k]), R.rel(thomas[k], dense[k]), EPS) for k, (n, t) in enumerate(zip("UVW", (U, V, W)))])
+           [(n, R.rel(K.to_np(t)[0], dense[k]), R.rel(thomas[k], dense[k]), EPS64) for k, (n, t) in enumerate(zip("UVW", (U, V, W)))])

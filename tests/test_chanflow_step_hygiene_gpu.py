@@ -12,17 +12,10 @@ import torch
 
 from tests import chanflow_step_reference as R
 from tests import hygiene as H
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DT = 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _case(dev, Nx, Ny, Nz, B):
@@ -39,12 +32,6 @@ def _case(dev, Nx, Ny, Nz, B):
 SHAPES = [(6, 7, 10, 1), (8, 10, 6, 3), (32, 130, 32, 2)]
 
 
-def _run(case, fn, inputs, mutable=()):
-    out, findings = H.run_case(fn, inputs, mutable)
-    assert not findings, "\n".join([case] + findings[:40])
-    return out
-
-
 @pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
 def test_project(dev, Nx, Ny, Nz, B):
     F, grid, poisson, inputs = _case(dev, Nx, Ny, Nz, B)
@@ -53,7 +40,7 @@ def test_project(dev, Nx, Ny, Nz, B):
         F.chanflow_project(grid, poisson, inp["U"], inp["V"], inp["W"])
         after_forward()
         return {k: inp[k] for k in "UVW"}
-    _run(f"chanflow_project {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W"))
+    H.assert_clean(f"chanflow_project {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W"))
 
 
 @pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
@@ -65,7 +52,7 @@ def test_wall_pressure(dev, Nx, Ny, Nz, B):
         after_forward()
         q1, q2, P = F.chanflow_wall_pressure(grid, poisson, inp["U"], inp["V"], inp["W"], inp["dp"], full=True)
         return {"p1": p1, "p2": p2, "q1": q1, "q2": q2, "P": P}
-    out = _run(f"chanflow_wall_pressure {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
+    out = H.assert_clean(f"chanflow_wall_pressure {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
     assert torch.equal(out["p1"], out["q1"]) and torch.equal(out["p2"], out["q2"])
 
 
@@ -80,5 +67,5 @@ def test_rk3_step_and_diagnostics(dev, Nx, Ny, Nz, B):
         p2 = F.chanflow_wall_pressure(grid, poisson, inp["U"], inp["V"], inp["W"], inp["dp"])[1]
         d1 = F.chanflow_diagnostics(grid, poisson, inp["U"], inp["V"], inp["W"], p2)
         return {"U": inp["U"], "V": inp["V"], "W": inp["W"], "dp": inp["dp"], "d0": d0, "d1": d1}
-    out = _run(f"chanflow_rk3_step {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W", "dp"))
+    out = H.assert_clean(f"chanflow_rk3_step {Nx}x{Ny}x{Nz} B={B}", fn, inputs, mutable=("U", "V", "W", "dp"))
     assert np.all(out["d0"][:, 9:11].cpu().numpy() == 0)        # no p2 given: the two pressure columns are 0

@@ -1,7 +1,7 @@
 """Closed-loop control on the GPU: the two bridges bit for bit, the two-level diagnostics, the running statistics, the loop
 under opposition control and under a neural policy against the float64 restatement, graph replay, dataset collection and the
-refusals.  The tolerance rule and its floors are stated in tests/control_loop_cases.py; every figure is logged to
-profiles/r13_control_loop_errors.txt before it is asserted.
+refusals.  The tolerance rule is the float64 floor rule of tests/judging.py, the floors are stated per case; every figure is
+logged to profiles/r13_control_loop_errors.txt before it is asserted.
 
 Figures of the statistics case (3), hostile set (mean / spread = 1000): the std is measured against || |mean| + std ||, what one
 rounding of the samples is relative to; the raw error relative to the std's own norm is logged beside it."""
@@ -15,18 +15,10 @@ import torch
 from oracle.detfill import fill_named
 from tests import chanflow_step_reference as R
 from tests import control_loop_cases as K
+from tests.judging import BUDGET_SLACK, TOL_Y, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 EPS, DT = K.EPS, K.DT
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    torch.set_num_threads(min(torch.get_num_threads(), 16))
-    return torch.device("cuda:0")
 
 
 def _F():
@@ -283,7 +275,6 @@ def test_closed_loop_fno_policy(dev, B):
     from oracle import fno_oracle as O
     from pde_policylearning_amd.control import ControlLoop, FnoPolicy
     from pde_policylearning_amd.libs.models.fno_models import FNO2dObserver
-    from tests.test_parity_gpu import BUDGET_SLACK
     steps = 4
     g, states, p_norm, v_norm = _neural_setup()
     torch.manual_seed(0)
@@ -332,7 +323,6 @@ def test_rno_policy_action(dev):
     from oracle import observers_oracle as OO
     from pde_policylearning_amd.control import ControlLoop, RnoPolicy
     from pde_policylearning_amd.neuralop.models.rno import RNO2d
-    from tests.test_parity_gpu import TOL_Y
     g, states, p_norm, v_norm = _neural_setup()
     torch.manual_seed(0)
     model = RNO2d(8, 8, 32, recurrent_index=0, layer_num=1).eval()

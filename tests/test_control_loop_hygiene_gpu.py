@@ -11,23 +11,10 @@ import torch
 
 from tests import chanflow_step_reference as R
 from tests import hygiene as H
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(6, 7, 10, 1), (8, 10, 6, 3), (32, 130, 32, 2)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def _run(case, fn, inputs, mutable=()):
-    out, findings = H.run_case(fn, inputs, mutable)
-    assert not findings, "\n".join([case] + findings[:40])
-    return out
 
 
 def _planes(dev, Nx, Nz, B):
@@ -50,7 +37,7 @@ def test_bridges(dev, Nx, Ny, Nz, B):
         w1, w2 = F.ctrl_decode(inp["y"], inp["mean"], inp["std"], shape=(B, Nx, Nz), batch_stride=3 * plane)
         after_forward()
         return {"dense": dense, "x0": x[:, 0], "opV1": v1, "opV2": v2, "plain opV1": w1, "plain opV2": w2}
-    _run(f"ctrl bridges {Nx}x{Nz} B={B}", fn, _planes(dev, Nx, Nz, B))
+    H.assert_clean(f"ctrl bridges {Nx}x{Nz} B={B}", fn, _planes(dev, Nx, Nz, B))
 
 
 @pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
@@ -68,7 +55,7 @@ def test_diagnostics2(dev, Nx, Ny, Nz, B):
         none = F.chanflow_diagnostics2(grid, poisson, inp["U"], inp["V"], inp["W"], None, inp["dp"])
         after_forward()
         return {"row": log[1], "without p2": none}
-    _run(f"chanflow_diagnostics2 {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
+    H.assert_clean(f"chanflow_diagnostics2 {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
 
 
 @pytest.mark.parametrize("Nx,Ny,Nz,B", SHAPES)
@@ -87,4 +74,4 @@ def test_running_stats(dev, Nx, Ny, Nz, B):
         out = {f"mean{k}": m for k, m in enumerate(means)}
         out.update({f"m2.{k}": m for k, m in enumerate(m2s)})
         return out
-    _run(f"running_stats_update {Nx}x{Ny}x{Nz} B={B}", fn, inputs)
+    H.assert_clean(f"running_stats_update {Nx}x{Ny}x{Nz} B={B}", fn, inputs)

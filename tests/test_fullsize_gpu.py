@@ -13,26 +13,12 @@ import torch
 from oracle import fno_oracle as O
 from oracle import observers_oracle as OO
 from oracle.detfill import fill_named
+from tests.judging import BUDGET_SLACK_FULLSIZE, dev  # noqa: F401
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-# An ill-conditioned gradient is allowed BUDGET_SLACK x the float32 oracle's own distance from float64.  Round 4 needed 2.0 for
-# RNO2d: two float evaluations that decide a ReLU input of the regressor within rounding of zero differently differentiate
-# different piecewise-linear functions, and every tensor upstream moves together by ~1e-5.  Round 5
-# compares MASK-CONDITIONED instead: the float64 / float32 oracles take the ENGINE's decisions for the regressor's two
-# spectral layers (oracle/observers_oracle.py::ReluMasks; read off the engine's layer outputs), so all three evaluations
-# differentiate the same function and what is left is arithmetic.
-BUDGET_SLACK = 1.25
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 ORACLE_THREADS = 16      # torch's CPU FFT / einsum stop scaling long before a many-core host is full (bench.py's sweep: 8-16 best)
@@ -75,9 +61,9 @@ def _rounded_inputs(params, x, seed=1):
     return {k: move(v) for k, v in params.items()}, move(x)
 
 
-def _compare(model, y, params, y64, g64, g32, gcond=None, slack=BUDGET_SLACK):
+def _compare(model, y, params, y64, g64, g32, gcond=None, slack=BUDGET_SLACK_FULLSIZE):
     """gcond: the float64 gradients of the problem with inputs moved by one float32 rounding (_rounded_inputs); where given,
-    the budget of an ill-conditioned gradient is BUDGET_SLACK x the larger of the reference's own float32 error and that
+    the budget of an ill-conditioned gradient is BUDGET_SLACK_FULLSIZE x the larger of the reference's own float32 error and that
     conditioning floor (the float32 error alone is ONE draw: for the scalar biases of the RNO cell it moved between 4e-6
     and 5e-5 with the batch split and the host's thread count, tools/rno_debug.py)."""
     assert rel_l2(y.detach().cpu().numpy().reshape(y64.shape), y64) < TOL

@@ -24,11 +24,11 @@ import torch
 
 from oracle import fno_oracle as O
 from oracle.detfill import fill_named
+from tests.judging import TOL_Y, dev  # noqa: F401
 from tests.test_parity_gpu import _fno_params, _run_fused, _within_budget
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
-TOL_Y = 1e-5
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -45,14 +45,6 @@ def _record(test, case, name, e, e32):
 def _check_output(case, ey, ey32):
     # plain 1e-5 wherever the float32 evaluation of the reference is itself comfortably inside it; otherwise twice its distance
     assert np.isfinite(ey) and ey < (TOL_Y if ey32 < 5e-6 else max(TOL_Y, 2.0 * ey32)), (case, ey, ey32)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _hostile(case, B, dims, C, L, half, cin=3):

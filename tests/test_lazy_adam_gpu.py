@@ -11,17 +11,10 @@ import pytest
 import torch
 from torch import nn
 
+from tests.judging import dev  # noqa: F401
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 class Tiny(nn.Module):

@@ -50,20 +50,12 @@ import torch
 from oracle import fno_oracle as O
 from oracle.detfill import fill_named
 from tests import hygiene as H
+from tests.judging import dev  # noqa: F401
 from tests.test_hostile_ranges_gpu import ROWS
 from tests.test_parity_gpu import _fno_params, _oracle_fno_fp64, _within_budget
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    torch.set_num_threads(min(torch.get_num_threads(), 16))
-    return torch.device("cuda:0")
 
 
 def _F():

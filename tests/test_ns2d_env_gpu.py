@@ -16,20 +16,13 @@ import torch
 from tests import hygiene as H
 from tests import ns2d_cases as N
 from tests.control_loop_cases import bits_equal, to_dev, to_np
+from tests.judging import dev  # noqa: F401
 from tests.util import load_golden
 
 pytestmark = pytest.mark.gpu
 EPS = N.EPS
 LD = np.longdouble
 N_IDX = {"p": 0, "u": 1, "v": 2}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -423,5 +416,4 @@ def test_hygiene(dev, ny, nx, B):
         res["solve"] = F.ns2d_solve(g.engine(), P, U, V, inp["F"], inp["nu"], inp["lo"], inp["hi"], max_step=3, un=un, vn=vn)
         res.update({"P": P, "U": U, "V": V, "un": un, "vn": vn})
         return res
-    _, findings = H.run_case(fn, inputs)
-    assert not findings, "\n".join(findings[:40])
+    H.assert_clean(f"ns2d hygiene {ny}x{nx} B={B}", fn, inputs)

@@ -17,18 +17,11 @@ import pytest
 import torch
 
 from tests import pino_loss_cases as C
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BUDGET_CASES = [(fam, d, n, B, nt) for n, B, nt in C.BUDGET_SHAPES for fam, d in C.budget_families(n)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()   # fails loudly when the HIP library is absent
-    return torch.device("cuda:0")
 
 
 def _forward(inp, dev, t_interval):

@@ -11,18 +11,11 @@ from tests import action_opt_cases as A
 from tests import chanflow_step_reference as R
 from tests import control_loop_cases as K
 from tests import policy_opt_cases as C
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 PLANES = [1024, 1020, 257, 1]
 DETECT = 3                 # detect_plane of the loop tests
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _rand(shape, seed, dtype=torch.float32, scale=1.0):

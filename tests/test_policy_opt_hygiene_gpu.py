@@ -8,23 +8,10 @@ import pytest
 import torch
 
 from tests import hygiene as H
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1), (3, 1), (2, 1020), (3, 1020)]          # (B, plane)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-def _run(case, fn, inputs, mutable=()):
-    out, findings = H.run_case(fn, inputs, mutable)
-    assert not findings, "\n".join([case] + findings[:40])
-    return out
 
 
 def _inputs(dev, B, plane):
@@ -47,7 +34,7 @@ def test_begin(dev, B, plane):
         F.ctrl_policy_begin(inp["v0"], inp["p2"], a0, pin)
         after_forward()
         return {"a0": a0, "pin": pin}
-    _run(f"ctrl_policy_begin B={B} plane={plane}", fn, _inputs(dev, B, plane))
+    H.assert_clean(f"ctrl_policy_begin B={B} plane={plane}", fn, _inputs(dev, B, plane))
 
 
 @pytest.mark.parametrize("B,plane", SHAPES)
@@ -60,7 +47,7 @@ def test_compose(dev, B, plane):
         F.ctrl_policy_compose(inp["a0"], inp["res"], x, opV2)
         after_forward()
         return {"x": x, "opV2": opV2}
-    _run(f"ctrl_policy_compose B={B} plane={plane}", fn, _inputs(dev, B, plane))
+    H.assert_clean(f"ctrl_policy_compose B={B} plane={plane}", fn, _inputs(dev, B, plane))
 
 
 @pytest.mark.parametrize("B,plane", SHAPES)
@@ -73,4 +60,4 @@ def test_grad(dev, B, plane):
         F.ctrl_policy_grad(inp["dx"], inp["x"], inp["parts"], reg=0.0, out=given)
         after_forward()
         return {"g": g, "g at reg 0": given}
-    _run(f"ctrl_policy_grad B={B} plane={plane}", fn, _inputs(dev, B, plane))
+    H.assert_clean(f"ctrl_policy_grad B={B} plane={plane}", fn, _inputs(dev, B, plane))

@@ -15,17 +15,10 @@ import pytest
 import torch
 
 from tests import spec_conv_cases as C
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROUTE_LOG_ENV = "SPEC_CONV_ROUTE_LOG"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()   # fails loudly when the HIP library is absent
-    return torch.device("cuda:0")
 
 
 # variant -> what every launch of it in the case must show.  rb / ntiles / grid (x extent) / block (x extent): equal;

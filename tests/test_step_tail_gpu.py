@@ -17,18 +17,11 @@ import pytest
 import torch
 
 from tests import step_tail_cases as T
+from tests.judging import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GATE_CASES, LOSS_CASES, ADAM_CASES = T.gate_cases(), T.loss_cases(), T.adam_cases()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from pde_policylearning_amd import _lib
-    _lib.lib()   # fails loudly when the HIP library is absent
-    return torch.device("cuda:0")
 
 
 def _ids(cases):
