@@ -369,6 +369,26 @@ int fno_projection_backward_act(int batch, int channels, int hidden, int cout, s
                                 void* stream);
 
 /* ------------------------------------------------------------------------
+ * Channel MLP of an FNO block built with use_mlp=True (neuralop/models/fno_block.py:123-170, mlp.py:26-54,
+ * skip_connections.py:38-74), one fused kernel per direction:
+ *     y = [gelu]( gelu(W2 gelu(W1 u + b1) + b2) + gate (.) x )
+ * u (B, C, PW): the Fourier part's (activated) output, x (B, C, PW): the block's input, w1 (hidden, C), w2 (C, hidden),
+ * gate (C): the soft-gating weight, or null for the identity skip; gelu_out: GELU on the sum (every block but the last).
+ * (C, hidden) in {(64, 32), (64, 64), (32, 32)}, PW % 128 == 0; anything else is an error code and launches nothing.
+ * backward recomputes every intermediate from u and x and writes du, dx (null: not wanted) and the parameter
+ * gradients (dgate null iff gate is null); partial sums go through the workspace and a fixed-order reduction, so results are
+ * bitwise repeatable.  The GEMMs are exact fp32 in either GEMM mode (fno_set_gemm_mode).
+ * ---------------------------------------------------------------------- */
+size_t fno_channel_mlp_workspace_bytes(int channels, int hidden, int batch, size_t plane);
+int fno_channel_mlp_forward(int batch, int channels, int hidden, size_t plane, const float* u, const float* x,
+                            const float* w1, const float* b1, const float* w2, const float* b2, const float* gate,
+                            int gelu_out, float* y, void* stream);
+int fno_channel_mlp_backward(int batch, int channels, int hidden, size_t plane, const float* u, const float* x,
+                             const float* w1, const float* b1, const float* w2, const float* b2, const float* gate,
+                             int gelu_out, const float* dy, float* du, float* dx, float* dw1, float* db1, float* dw2,
+                             float* db2, float* dgate, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Lifting layer on its own:  y = W x + b,  x (B, Cin <= 4, PW) -> y (B, C, PW), C in {32, 64}, PW % 128 == 0
  * (neuralop/models/tfno.py:11-20; also the `fc0` + Re-conditioning front of the PINO observers,
  * libs/models/pino_models/pinobserver.py:205-207, once its two linear maps are composed).  backward gives the

@@ -28,6 +28,7 @@
 #include "k_projection.h"
 #include "k_projection2.h"
 #include "k_projection_h2.h"
+#include "k_channel_mlp.h"
 #include "k_spectral_mid.h"
 #include "k_pino_loss.h"
 #include "k_pino_loss2.h"
@@ -3060,6 +3061,90 @@ extern "C" int fno_projection_backward(int B, int C, int hidden, int Cout, size_
                                        float* db1, float* dw2, float* db2, void* ws, size_t ws_bytes, void* stream) {
   return fno_projection_backward_act(B, C, hidden, Cout, PW, x, w1, b1, w2, dy, FNO_ACT_GELU, dx, dw1, db1, dw2, db2, ws,
                                      ws_bytes, stream);
+}
+
+// ===========================================================================
+// Channel MLP of an FNO block built with use_mlp=True:  y = [gelu]( gelu(W2 gelu(W1 u + b1) + b2) + g (.) x )
+// (neuralop/models/fno_block.py:123-170, mlp.py:26-54, skip_connections.py:38-74; k_channel_mlp.h).  Exact-fp32 MFMA in
+// either GEMM mode.
+// ===========================================================================
+static int cmlp_check(int B, int C, int HID, size_t PW) {
+  LAUNCHCHK(pw_check(B, C, PW));
+  if (!((C == 64 && (HID == 32 || HID == 64)) || (C == 32 && HID == 32)))
+    return fail(FNO_EUNSUPPORTED, "channel MLP: (channels, hidden) is one of (64, 32), (64, 64), (32, 32) (got (%d, %d))", C, HID);
+  return FNO_OK;
+}
+struct CmlpWs { float *dw1_part, *db1_part, *dw2_part, *db2_part, *dg_part; int grid, ks; size_t total; bool ok; };
+static CmlpWs carve_cmlp(int C, int HID, int B, size_t PW, void* ws, size_t ws_bytes) {
+  Carver c(ws, ws_bytes);
+  CmlpWs w;
+  w.grid = (int)std::min<size_t>((size_t)B * (PW / 128), (size_t)FNO_GRID_BWD * dev_ncu());
+  w.ks = cmlp_bwd_ksplit(C, HID);
+  w.dw1_part = c.take<float>((size_t)w.grid * w.ks * HID * C);
+  w.db1_part = c.take<float>((size_t)w.grid * 4 * HID);
+  w.dw2_part = c.take<float>((size_t)w.grid * w.ks * C * HID);
+  w.db2_part = c.take<float>((size_t)w.grid * 4 * C);
+  w.dg_part = c.take<float>((size_t)w.grid * C);
+  w.total = c.off;
+  w.ok = c.ok;
+  return w;
+}
+extern "C" size_t fno_channel_mlp_workspace_bytes(int C, int hidden, int B, size_t PW) {
+  if (cmlp_check(B, C, hidden, PW) != FNO_OK) return 0;
+  return carve_cmlp(C, hidden, B, PW, nullptr, 0).total;
+}
+template <int C, int HID>
+static int cmlp_fwd_launch(hipStream_t st, const CmlpFwdArgs& a) {
+  const size_t lds = cmlp_fwd_lds_bytes(C, HID);
+  const int grid = std::min(a.ntiles, (2 * lds <= FNO_LDS_MAX ? 2 : 1) * dev_ncu());      // workgroups a CU holds
+  return GT(1), LV(C == 32 ? "k_cmlp_fwd<32, 32>" : HID == 32 ? "k_cmlp_fwd<64, 32>" : "k_cmlp_fwd<64, 64>", 0, a.ntiles),
+         launch("k_cmlp_fwd", k_cmlp_fwd<C, HID>, dim3(grid), dim3(256), lds, st, a);
+}
+template <int C, int HID>
+static int cmlp_bwd_launch(hipStream_t st, int grid, const CmlpBwdArgs& a) {
+  return GT(1), LV(C == 32 ? "k_cmlp_bwd<32, 32>" : HID == 32 ? "k_cmlp_bwd<64, 32>" : "k_cmlp_bwd<64, 64>", 0, a.ntiles),
+         launch("k_cmlp_bwd", k_cmlp_bwd<C, HID>, dim3(grid), dim3(256), cmlp_bwd_lds_bytes(C, HID), st, a);
+}
+extern "C" int fno_channel_mlp_forward(int B, int C, int hidden, size_t PW, const float* u, const float* x, const float* w1,
+                                       const float* b1, const float* w2, const float* b2, const float* gate, int gelu_out,
+                                       float* y, void* stream) {
+  LAUNCHCHK(cmlp_check(B, C, hidden, PW));
+  if (!u || !x || !w1 || !b1 || !w2 || !b2 || !y) return fail(FNO_EINVAL, "fno_channel_mlp_forward: null argument");
+  CmlpFwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.u = u; a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.g = gate; a.y = y; a.gelu_out = gelu_out ? 1 : 0;
+  a.PW = (int)PW; a.tiles_per_plane = (int)(PW / 128); a.ntiles = B * a.tiles_per_plane;
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 32) return cmlp_fwd_launch<32, 32>(st, a);
+  return hidden == 32 ? cmlp_fwd_launch<64, 32>(st, a) : cmlp_fwd_launch<64, 64>(st, a);
+}
+extern "C" int fno_channel_mlp_backward(int B, int C, int hidden, size_t PW, const float* u, const float* x, const float* w1,
+                                        const float* b1, const float* w2, const float* b2, const float* gate, int gelu_out,
+                                        const float* dy, float* du, float* dx, float* dw1, float* db1, float* dw2, float* db2,
+                                        float* dgate, void* ws, size_t ws_bytes, void* stream) {
+  LAUNCHCHK(cmlp_check(B, C, hidden, PW));
+  if (!u || !x || !w1 || !b1 || !w2 || !b2 || !dy || !du || !dw1 || !db1 || !dw2 || !db2 || !ws)
+    return fail(FNO_EINVAL, "fno_channel_mlp_backward: null argument");
+  if ((gate == nullptr) != (dgate == nullptr)) return fail(FNO_EINVAL, "fno_channel_mlp_backward: dgate is null iff gate is null");
+  CmlpWs w = carve_cmlp(C, hidden, B, PW, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  CmlpBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.u = u; a.x = x; a.dy = dy; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.g = gate; a.du = du; a.dx = dx;
+  a.dw1_part = w.dw1_part; a.db1_part = w.db1_part; a.dw2_part = w.dw2_part; a.db2_part = w.db2_part;
+  a.dg_part = gate ? w.dg_part : nullptr;
+  a.gelu_out = gelu_out ? 1 : 0;
+  a.PW = (int)PW; a.tiles_per_plane = (int)(PW / 128); a.ntiles = B * a.tiles_per_plane;
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 32) LAUNCHCHK((cmlp_bwd_launch<32, 32>(st, w.grid, a)));
+  else LAUNCHCHK((hidden == 32 ? cmlp_bwd_launch<64, 32>(st, w.grid, a) : cmlp_bwd_launch<64, 64>(st, w.grid, a)));
+  JobList jobs;
+  jobs.add(w.dw1_part, dw1, w.grid * w.ks, hidden, C, C, C);
+  jobs.add(w.db1_part, db1, w.grid * 4, 1, hidden, hidden, hidden);
+  jobs.add(w.dw2_part, dw2, w.grid * w.ks, C, hidden, hidden, hidden);
+  jobs.add(w.db2_part, db2, w.grid * 4, 1, C, C, C);
+  if (gate) jobs.add(w.dg_part, dgate, w.grid, 1, C, C, C);
+  return jobs.run(st);
 }
 
 // ===========================================================================

@@ -2071,3 +2071,61 @@ def projection_head(x, w1, b1, w2, b2, act="gelu"):
     (FNO projection, PINO observer tails; Cout <= 4: PlanePredHead's out_dim * plane_num, pinobserver.py:257-273) or 'relu'
     (RNO2d's regressor head, rno.py:171-175; hidden 256, Cout 1)."""
     return _ProjectionHeadFn.apply(x, w1, b1, w2, b2, _ACT_CODES[act])
+
+
+# ----------------------------------------------------------------------------
+# channel MLP of an FNO block built with use_mlp=True:  y = [gelu]( gelu(W2 gelu(W1 u + b1) + b2) + gate * x )
+# ----------------------------------------------------------------------------
+CHANNEL_MLP_WIDTHS = ((64, 32), (64, 64), (32, 32))        # (channels, hidden) pairs k_channel_mlp.h is built for
+
+
+def channel_mlp_supported(x, hidden):
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and (x.shape[1], int(hidden)) in CHANNEL_MLP_WIDTHS
+            and plane_size(x.shape) % 128 == 0)
+
+
+class _ChannelMlpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, x, w1, b1, w2, b2, gate, gelu_out):
+        e = "channel_mlp"
+        _require_cuda(u, "u")
+        u = u.contiguous()
+        B, Cc = u.shape[0], u.shape[1]
+        pw = u.numel() // (B * Cc)
+        hid = w1.shape[0]
+        xc = _operand(e, "x", x, u, shape=u.shape)
+        w1c = _operand(e, "w1", w1, u, numel=hid * Cc).reshape(hid, Cc)
+        b1c = _operand(e, "b1", b1, u, numel=hid)
+        w2c = _operand(e, "w2", w2, u, numel=Cc * hid).reshape(Cc, hid)
+        b2c = _operand(e, "b2", b2, u, numel=Cc)
+        gc = _operand(e, "gate", gate, u, numel=Cc, optional=True)
+        y = torch.empty_like(u)
+        _call("channel_mlp_forward", u.device, "fno_channel_mlp_forward", B, Cc, hid, pw, u, xc, w1c, b1c, w2c, b2c, gc,
+              int(bool(gelu_out)), y, STREAM)
+        ctx.save_for_backward(u, xc, w1c, b1c, w2c, b2c, *(() if gc is None else (gc,)))
+        ctx.meta = (B, Cc, hid, pw, w1.shape, w2.shape, None if gate is None else gate.shape, int(bool(gelu_out)))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, xc, w1c, b1c, w2c, b2c, *rest = ctx.saved_tensors
+        gc = rest[0] if rest else None
+        B, Cc, hid, pw, w1shape, w2shape, gshape, gelu_out = ctx.meta
+        dy = _operand("channel_mlp backward", "dy", dy, u, numel=u.numel())
+        du = torch.empty_like(u)
+        dx = torch.empty_like(xc) if ctx.needs_input_grad[1] else None
+        dw1, db1, dw2, db2 = torch.empty_like(w1c), torch.empty_like(b1c), torch.empty_like(w2c), torch.empty_like(b2c)
+        dg = None if gc is None else torch.empty_like(gc)
+        nws = _lib.lib().fno_channel_mlp_workspace_bytes(Cc, hid, B, pw)
+        ws = _bytes(nws, u.device)
+        _call("channel_mlp_backward", u.device, "fno_channel_mlp_backward", B, Cc, hid, pw, u, xc, w1c, b1c, w2c, b2c, gc,
+              gelu_out, dy, du, dx, dw1, db1, dw2, db2, dg, ws, nws, STREAM)
+        return (du, dx, dw1.view(w1shape), db1, dw2.view(w2shape), db2, None if dg is None else dg.view(gshape), None)
+
+
+def channel_mlp(u, x, w1, b1, w2, b2, gate=None, gelu_out=False):
+    """The MLP tail of an FNO block (fno_block.py:137-169 with use_mlp=True): (B, C, ...) -> (B, C, ...),
+    gelu(fcs.1(gelu(fcs.0(u)))) + gate * x, GELU on the sum when `gelu_out`.  u: the Fourier part's output, x: the block's
+    input, w1 (H, C[, 1..]), w2 (C, H[, 1..]), gate (C) / (1, C, 1..) or None (identity skip); (C, H) in CHANNEL_MLP_WIDTHS.
+    One kernel per direction; the backward recomputes the intermediates from u and x and skips dx when x needs no gradient."""
+    return _ChannelMlpFn.apply(u, x, w1, b1, w2, b2, gate, gelu_out)

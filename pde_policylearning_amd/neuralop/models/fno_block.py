@@ -1,11 +1,12 @@
-"""FNOBlocks with the reference surface (neuralop/models/fno_block.py:10-170), default
-path only: linear (bias-free 1x1 conv) skip, no MLP, no norm, no preactivation."""
+"""FNOBlocks with the reference surface (neuralop/models/fno_block.py:10-170): linear (bias-free 1x1 conv) skip, no norm, no
+preactivation; with `use_mlp` the channel MLP and its soft-gating / identity skip (mlp.py:26-54, skip_connections.py:38-74)."""
 import itertools
 
 import torch
 import torch.nn.functional as TF
 from torch import nn
 
+from ... import functional as F
 from .spectral_convolution import SpectralConv, _unsupported
 
 
@@ -31,6 +32,39 @@ def _resample(x, scales):
     return torch.fft.irfftn(out, s=new, norm='forward', dim=dims)
 
 
+class MLP(nn.Module):
+    """The parameters of the reference's two-layer channel MLP (mlp.py:26-54: `fcs`, two 1x1 convolutions C -> H -> C, a GELU
+    after EACH of them, :49).  Its arithmetic exists only as the engine kernel (functional.channel_mlp), which computes it
+    together with the skip it is added to (FNOBlocks.forward)."""
+
+    def __init__(self, in_channels, hidden_channels, n_dim=2):
+        super().__init__()
+        self.in_channels, self.out_channels, self.hidden_channels, self.n_layers = in_channels, in_channels, hidden_channels, 2
+        Conv = getattr(nn, f'Conv{n_dim}d')
+        self.fcs = nn.ModuleList([Conv(in_channels, hidden_channels, 1), Conv(hidden_channels, in_channels, 1)])
+
+    def forward(self, x):
+        return F.channel_mlp(x, torch.zeros_like(x), self.fcs[0].weight, self.fcs[0].bias, self.fcs[1].weight, self.fcs[1].bias)
+
+
+class SoftGating(nn.Module):
+    """x * w with w (1, C, 1, ..) initialised to ones, no bias (skip_connections.py:38-74)"""
+
+    def __init__(self, in_features, out_features=None, n_dim=2, bias=False):
+        super().__init__()
+        if out_features is not None and in_features != out_features:
+            raise ValueError(f"Got in_features={in_features} and out_features={out_features} "
+                             "but these two must be the same for soft-gating")
+        if bias:
+            _unsupported("SoftGating(bias=True)")
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.ones(1, in_features, *(1,) * n_dim))
+        self.bias = None
+
+    def forward(self, x):
+        return self.weight * x
+
+
 class FNOBlocks(nn.Module):
     def __init__(self, in_channels, out_channels, n_modes, output_scaling_factor=None, n_layers=1,
                  incremental_n_modes=None, use_mlp=False, mlp_dropout=0, mlp_expansion=0.5,
@@ -40,8 +74,6 @@ class FNOBlocks(nn.Module):
                  fixed_rank_modes=False, implementation='factorized', decomposition_kwargs=dict(),
                  fft_norm='forward', **kwargs):
         super().__init__()
-        if use_mlp:
-            _unsupported("use_mlp=True")
         if norm is not None:
             _unsupported(f"norm={norm!r}")
         if preactivation:
@@ -73,12 +105,58 @@ class FNOBlocks(nn.Module):
         Conv = getattr(nn, f'Conv{self.n_dim}d')
         self.fno_skips = nn.ModuleList([Conv(in_channels, out_channels, kernel_size=1, bias=False)
                                         for _ in range(n_layers)])
+        self.mlp = None
+        if use_mlp:
+            # the channel MLP exists only as the engine kernel: what the kernel does not cover is refused here
+            hidden = int(round(out_channels * mlp_expansion))
+            if in_channels != out_channels or (out_channels, hidden) not in F.CHANNEL_MLP_WIDTHS:
+                _unsupported(f"use_mlp=True with (channels, mlp hidden width) = ({out_channels}, {hidden}); the channel-MLP kernel "
+                             f"is built for {F.CHANNEL_MLP_WIDTHS}")
+            if mlp_dropout > 0:
+                _unsupported(f"mlp_dropout={mlp_dropout!r}")
+            if str(mlp_skip).lower() not in ('soft-gating', 'identity'):
+                if str(mlp_skip).lower() != 'linear':
+                    raise ValueError(f"Got skip-connection type={mlp_skip!r}, expected one of 'soft-gating', 'linear', 'identity'.")
+                _unsupported(f"mlp_skip={mlp_skip!r}")
+            if output_scaling_factor is not None:
+                _unsupported("use_mlp=True with output_scaling_factor")
+            self.mlp = nn.ModuleList([MLP(out_channels, hidden, n_dim=self.n_dim) for _ in range(n_layers)])
+            self.mlp_skips = nn.ModuleList([SoftGating(in_channels, out_channels, n_dim=self.n_dim)
+                                            if str(mlp_skip).lower() == 'soft-gating' else nn.Identity()
+                                            for _ in range(n_layers)])
 
     def gelu_after(self, index):
         return index < (self.n_layers - index)          # fno_block.py:149
 
+    def _forward_mlp(self, x, index):
+        """fno_block.py:137-169 with an MLP: u = gelu(conv(x) + skip(x)) on EVERY layer (:147-150), then
+        gelu(fcs.1(gelu(fcs.0(u)))) + mlp_skip(x) - the skip takes the block's INPUT (:137) - and a GELU unless this is the
+        last layer (:167-169).  The Fourier part is one fused engine layer (+ its GELU) where the block kernels cover the shape,
+        the MLP part is functional.channel_mlp: without its kernel there is no MLP, so an uncovered shape raises."""
+        F._require_cuda(x, "x")
+        mlp, hidden = self.mlp[index], self.mlp[index].hidden_channels
+        if not F.channel_mlp_supported(x, hidden):
+            raise RuntimeError(f"fnoengine FNOBlocks(use_mlp=True): no channel-MLP kernel for input {tuple(x.shape)} {x.dtype} "
+                               f"(float32, planes a multiple of 128 elements, (channels, hidden) in {F.CHANNEL_MLP_WIDTHS})")
+        convs = self.convs
+        if convs.bias is not None and not convs.separable and F.blocks_supported(x, 1, convs.half_n_modes, self.fft_norm, 0):
+            # one fused engine layer (spectral convolution + skip + bias, fixed-order weight-gradient reductions).  Its GELU is
+            # a torch operation: the engine's block stacks end without activation unless a projection follows
+            # (fno_model_plan_create), so `gelu_mask=1` on a one-layer stack is refused
+            pre = F.fno_blocks(x, [self.fno_skips[index].weight], convs.layer_weights(index),
+                               convs.bias[index:index + 1].reshape(1, -1), convs.half_n_modes, self.fft_norm, gelu_mask=0)
+        else:
+            pre = convs(x, index) + self.fno_skips[index](x)
+        u = self.non_linearity(pre)
+        skip = self.mlp_skips[index]
+        gate = skip.weight if isinstance(skip, SoftGating) else None
+        return F.channel_mlp(u, x, mlp.fcs[0].weight, mlp.fcs[0].bias, mlp.fcs[1].weight, mlp.fcs[1].bias, gate,
+                             gelu_out=index < self.n_layers - 1)
+
     def forward(self, x, index=0):
         """Unfused composition (one block on its own); FNO.forward uses the fused engine path."""
+        if getattr(self, "mlp", None) is not None:      # (modules pickled before the channel MLP existed carry no `mlp`)
+            return self._forward_mlp(x, index)
         x_skip = self.fno_skips[index](x)
         if self.convs.output_scaling_factor is not None:
             x_skip = _resample(x_skip, self.output_scaling_factor[index])

@@ -1,6 +1,7 @@
 """FNO / FNO2d / FNO3d with the reference constructor surface (neuralop/models/tfno.py:
 Lifting :11-20, Projection :23-38, FNO :107-211, FNO2d :342-458, FNO3d :467-580).
-forward() runs the whole model in the HIP engine (functional.fno_model)."""
+forward() runs the whole model in the HIP engine (functional.fno_model); with `use_mlp` it runs layer by layer, every block
+as one fused Fourier layer and one channel-MLP kernel."""
 import torch
 import torch.nn.functional as TF
 from torch import nn
@@ -85,6 +86,8 @@ class FNO(nn.Module):
         160 x 160, 192 x 192 grids ...; split-precision GEMM mode)."""
         if self.fno_blocks.convs.separable or self.fno_blocks.convs.output_scaling_factor is not None:
             return False           # torch compositions (SpectralConv._torch_composition): layer by layer
+        if getattr(self.fno_blocks, "mlp", None) is not None:
+            return False           # the whole-model plan knows no channel MLP: layer by layer (FNOBlocks._forward_mlp)
         if not (self.hidden_channels in (32, 64) and self.in_channels <= 4 and self.out_channels <= 4
                 and self.projection_channels == 256 and x.is_cuda and F.row_tiling(tuple(x.shape[2:])) is not None
                 and (not x.requires_grad or self.in_channels <= 4)):
@@ -109,10 +112,27 @@ class FNO(nn.Module):
             for p in self.parameters():
                 if p.grad is not None:
                     p.grad.zero_()
+        if getattr(self.fno_blocks, "mlp", None) is not None:
+            return self._forward_mlp(x)
         x = self.lifting(x)
         for l in range(self.n_layers):
             x = self.fno_blocks(x, l)
         return self.projection(x)
+
+    def _forward_mlp(self, x):
+        """The layer loop of a model with channel MLPs: lifting and projection head on their engine kernels where those cover
+        the shape, the torch modules otherwise; every block is one fused Fourier layer + one channel-MLP kernel."""
+        F._require_cuda(x, "x")
+        if F.lifting_supported(x, self.hidden_channels):
+            x = F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
+        else:
+            x = self.lifting(x)
+        for l in range(self.n_layers):
+            x = self.fno_blocks(x, l)
+        prj = self.projection
+        if F.projection_supported(x, self.projection_channels, self.out_channels):
+            return F.projection_head(x, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
+        return prj(x)
 
 
 class FNO2d(FNO):
