@@ -72,16 +72,22 @@ int fno_get_fused_mid(void);
  * fp32 pairs, shape (Cin, Cout, modes[0], [modes[1],] weight_last_extent), in the
  * canonical corner order (lo), (hi) in 2-D and (lo,lo), (lo,hi), (hi,lo), (hi,hi)
  * over the two leading dims in 3-D.
+ * One-dimensional grids (ndim = 1; neuralop FNO1d / dialect A, libs/models/pino_models/basics.py:30-58 SpectralConv1d /
+ * dialect C) have ONE corner weight (Cin, Cout, weight_last_extent) and their own kernels: the truncated DFT of a whole
+ * sample as a GEMM against the plan's twiddle tables, in slabs of 256 points, three launches per direction.  Limits,
+ * each refused by name at plan creation: Cin, Cout in {32, 64} (they may differ); dims[0] a multiple of 128 in
+ * [128, 8192]; 1 <= modes[0] <= 64 (so never the Nyquist bin); weight_planes = 0.  input_gelu is supported at every such
+ * shape.  1-D arithmetic is exact fp32 in either GEMM mode: fno_set_gemm_mode does not change 1-D results.
  * ---------------------------------------------------------------------- */
 typedef struct FnoSpecDesc {
-  int ndim;                /* 2 or 3 */
+  int ndim;                /* 1, 2 or 3 */
   int Cin, Cout;
   int dims[3];             /* spatial extents */
   int modes[3];            /* kept extent per corner along each dim */
   int weight_last_extent;  /* last-dim extent of the stored weights (>= modes[ndim-1]) */
   int norm;                /* FNO_NORM_* */
   int input_gelu;          /* 1: the input is a PRE-activation tensor u and the convolution acts on gelu(u) (applied while
-                              the rows are staged; <= 64 channels, rows <= 320 floats, <= 32 kept last-dim bins).  backward
+                              the rows are staged; 2-D / 3-D: <= 64 channels, rows <= 320 floats, <= 32 kept last-dim bins).  backward
                               then returns dL/d gelu(u); the caller (fno_pointwise_backward) applies gelu'(u). */
   int weight_planes;       /* 1: the corner weights (and their gradients) are stored PLANE-MAJOR - the memory order is
                               (weight_last_extent, Cin, Cout, modes[0], [modes[1]]), i.e. the reference's tensor permuted so

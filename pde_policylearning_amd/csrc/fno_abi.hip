@@ -30,6 +30,7 @@
 #include "k_projection_h2.h"
 #include "k_channel_mlp.h"
 #include "k_spectral_mid.h"
+#include "k_spec1d.h"
 #include "k_pino_loss.h"
 #include "k_pino_loss2.h"
 #include "k_rno_gates.h"
@@ -265,8 +266,11 @@ static int upload(Tables& t, const void* host, size_t bytes, void** dev) {
   return FNO_OK;
 }
 
-static int make_geom(Geom& g, int ndim, const int* dims, const int* modes, int wl_stride, int norm, int w_planes = 0) {
-  if (ndim != 2 && ndim != 3) return fail(FNO_EUNSUPPORTED, "ndim=%d (2 or 3 supported)", ndim);
+// allow_1d: the standalone spectral convolution has one-dimensional kernels (k_spec1d.h); the whole-model plan has none
+static int make_geom(Geom& g, int ndim, const int* dims, const int* modes, int wl_stride, int norm, int w_planes = 0,
+                     bool allow_1d = false) {
+  if (ndim != 2 && ndim != 3 && !(allow_1d && ndim == 1))
+    return fail(FNO_EUNSUPPORTED, allow_1d ? "ndim=%d (1, 2 or 3 supported)" : "ndim=%d (2 or 3 supported)", ndim);
   g.ndim = ndim;
   g.nlead = ndim - 1;
   g.PW = 1;
@@ -331,7 +335,8 @@ static int make_tables(const Geom& g, Tables& t) {
   if ((rc = upload(t, fb.data(), fb.size() * 4, (void**)&t.tfwd_b))) return rc;
   if ((rc = upload(t, vf.data(), vf.size() * 4, (void**)&t.tinv_f))) return rc;
   if ((rc = upload(t, vb.data(), vb.size() * 4, (void**)&t.tinv_b))) return rc;
-  t.K2P = g.Klast <= 8 ? 8 : g.Klast <= 16 ? 16 : g.Klast <= 32 ? 32 : 0;
+  // (1-D plans: no kernel of k_spec1d.h reads the transposed tables - up to 4 x 2 MB at N = 8192 that a cached plan would hold)
+  t.K2P = g.ndim == 1 ? 0 : g.Klast <= 8 ? 8 : g.Klast <= 16 ? 16 : g.Klast <= 32 ? 32 : 0;
   if (t.K2P) {
     const std::vector<float>* src[4] = {&ff, &fb, &vf, &vb};
     for (int q = 0; q < 4; ++q) {
@@ -689,19 +694,35 @@ struct FnoSpecPlan {
 };
 
 static bool row_chan_ok(const Geom& g, int K2P, int C) { return K2P && C <= 64 && g.W <= 320; }
+// the limits of the one-dimensional kernels (k_spec1d.h), each refused under its own name before any HIP call
+static int spec1d_check(const FnoSpecDesc* d) {
+  const int N = d->dims[0], M = d->modes[0];
+  if ((d->Cin != 32 && d->Cin != 64) || (d->Cout != 32 && d->Cout != 64))
+    return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: channels Cin=%d, Cout=%d (each 32 or 64)", d->Cin, d->Cout);
+  if (N < 128 || N > 8192 || N % 128 != 0)
+    return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: dims[0]=%d (a multiple of 128 in [128, 8192])", N);
+  // (M <= 64 <= N / 2: the Nyquist bin is never kept)
+  if (M < 1 || M > 64) return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: modes[0]=%d (1..64 kept bins, below the Nyquist bin)", M);
+  if (d->weight_planes) return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: weight_planes=1 (plane-major weights are a 3-D layout)");
+  return FNO_OK;
+}
 extern "C" int fno_spec_plan_create(const FnoSpecDesc* d, FnoSpecPlan** out) {
   if (!d || !out) return fail(FNO_EINVAL, "null argument");
+  if (d->ndim == 1) {
+    const int rc1 = spec1d_check(d);
+    if (rc1 != FNO_OK) return rc1;
+  }
   FnoSpecPlan* p = new FnoSpecPlan();
   p->d = *d;
-  int rc = make_geom(p->g, d->ndim, d->dims, d->modes, d->weight_last_extent, d->norm, d->weight_planes);
+  int rc = make_geom(p->g, d->ndim, d->dims, d->modes, d->weight_last_extent, d->norm, d->weight_planes, true);
   if (rc == FNO_OK && (d->Cin < 1 || d->Cout < 1 || d->Cin > 256 || d->Cout > 256))
     rc = fail(FNO_EUNSUPPORTED, "channels must be in [1, 256]");
-  if (rc == FNO_OK) {
+  if (rc == FNO_OK && d->ndim != 1) {      // (1-D: the "row" is the whole sample and is cut into slabs, nothing to hold in LDS)
     const size_t lds1 = (size_t)std::max(d->Cin, d->Cout) * (p->g.W + 1) * 4;
     if (lds1 > FNO_LDS_MAX) rc = fail(FNO_EUNSUPPORTED, "row tile C*(W+1)*4=%zu exceeds LDS", lds1);
   }
   if (rc == FNO_OK) rc = make_tables(p->g, p->t);
-  if (rc == FNO_OK && d->input_gelu && !row_chan_ok(p->g, p->t.K2P, d->Cin))
+  if (rc == FNO_OK && d->ndim != 1 && d->input_gelu && !row_chan_ok(p->g, p->t.K2P, d->Cin))
     rc = fail(FNO_EUNSUPPORTED, "input_gelu needs <= 64 input channels, rows of <= 320 floats and <= 32 kept last-dim bins");
   if (rc != FNO_OK) { p->t.release(); delete p; return rc; }
   *out = p;
@@ -711,6 +732,72 @@ extern "C" void fno_spec_plan_destroy(FnoSpecPlan* p) {
   if (!p) return;
   p->t.release();
   delete p;
+}
+
+// ---- one-dimensional grids (k_spec1d.h): analysis -> mix -> synthesis, three launches per direction ----
+struct Spec1dWs { float *part, *hat, *dbpart, *xhat; size_t total; };
+static Spec1dWs carve_spec1d(const FnoSpecPlan* p, int B, void* ws, size_t cap, bool* ok) {
+  const int Cm = std::max(p->d.Cin, p->d.Cout), N = p->g.W, J = p->g.J, T = (N + S1_TILE - 1) / S1_TILE;
+  Carver c(ws, cap);
+  Spec1dWs w;
+  w.part = c.take<float>((size_t)B * T * J * Cm);      // partial spectra of the slabs
+  w.hat = c.take<float>((size_t)B * J * Cm);           // the mixed spectrum the synthesis reads
+  w.dbpart = c.take<float>((size_t)B * T * Cm);        // slab sums of dy
+  w.xhat = c.take<float>((size_t)B * J * p->d.Cin);    // the input spectrum of a forward that saves nothing
+  w.total = c.off;
+  if (ok) *ok = c.ok;
+  return w;
+}
+static int spec1d_ana(hipStream_t st, int C, int B, int T, const float* x, const float* tab, float* part, float* dbpart, int N,
+                      int J, int act) {
+  const dim3 grid(T, B), blk(256);
+  const size_t lds = (size_t)C * S1_TILE * 4;
+  if (C == 32) return LV("k_s1_ana<32>", 0, T * B), launch("k_s1_ana", k_s1_ana<32>, grid, blk, lds, st, x, tab, part, dbpart, N, J, act);
+  return LV("k_s1_ana<64>", 0, T * B), launch("k_s1_ana", k_s1_ana<64>, grid, blk, lds, st, x, tab, part, dbpart, N, J, act);
+}
+static int spec1d_syn(hipStream_t st, int C, int B, int T, const float* hat, const float* tab, const float* bias, float* y, int N,
+                      int J) {
+  const dim3 grid(T, B), blk(256);
+  const size_t lds = (size_t)J * C * 4;
+  if (C == 32) return LV("k_s1_syn<32>", 0, T * B), launch("k_s1_syn", k_s1_syn<32>, grid, blk, lds, st, hat, tab, bias, y, N, J);
+  return LV("k_s1_syn<64>", 0, T * B), launch("k_s1_syn", k_s1_syn<64>, grid, blk, lds, st, hat, tab, bias, y, N, J);
+}
+static size_t spec_xhat_floats(const FnoSpecPlan* p, int B);
+static int spec1d_forward(const FnoSpecPlan* p, hipStream_t st, int B, const float* x, const float* w0, const float* bias, float* y,
+                          float* xhat_save, void* ws, size_t ws_bytes) {
+  const Geom& g = p->g;
+  const int Cin = p->d.Cin, Cout = p->d.Cout, N = g.W, M = g.Klast, J = g.J, T = (N + S1_TILE - 1) / S1_TILE;
+  if (!w0) return fail(FNO_EINVAL, "fno_spec_forward: null corner weight");
+  if (B > 65535) return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: batch %d (at most 65535)", B);
+  bool ok;
+  Spec1dWs w = carve_spec1d(p, B, ws, ws_bytes, &ok);
+  if (!ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  LAUNCHCHK(spec1d_ana(st, Cin, B, T, x, p->t.tfwd_f, w.part, nullptr, N, J, p->d.input_gelu));
+  const S1Weights sw{(const float2*)w0, Cout * g.wl_stride, g.wl_stride, 1};
+  const size_t lds = ((size_t)Cin * (Cout + 1) + 16 * Cin) * 8;
+  LAUNCHCHK((LV("k_s1_mix_fwd", 16, 0), launch("k_s1_mix", k_s1_mix_fwd, dim3(M, (B + 15) / 16), dim3(256), lds, st, w.part, sw,
+                   (float2*)(xhat_save ? xhat_save : w.xhat), (float2*)(xhat_save ? xhat_save + spec_xhat_floats(p, B) : nullptr),
+                   w.hat, B, T, M, Cin, Cout, (float)g.s_f)));
+  return spec1d_syn(st, Cout, B, T, w.hat, p->t.tinv_f, bias, y, N, J);
+}
+static int spec1d_backward(const FnoSpecPlan* p, hipStream_t st, int B, const float* dy, const float* xhat, const float* w0,
+                           float* dx, float* dw0, float* dbias, void* ws, size_t ws_bytes) {
+  const Geom& g = p->g;
+  const int Cin = p->d.Cin, Cout = p->d.Cout, N = g.W, M = g.Klast, J = g.J, T = (N + S1_TILE - 1) / S1_TILE;
+  if (B > 65535) return fail(FNO_EUNSUPPORTED, "1-D spectral convolution: batch %d (at most 65535)", B);
+  bool ok;
+  Spec1dWs w = carve_spec1d(p, B, ws, ws_bytes, &ok);
+  if (!ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  if (!dx && !dw0 && !dbias) return FNO_OK;
+  LAUNCHCHK(spec1d_ana(st, Cout, B, T, dy, p->t.tfwd_b, w.part, dbias ? w.dbpart : nullptr, N, J, 0));
+  // the weights for dx: the packed copy behind the saved spectrum, else the caller's tensor
+  S1Weights sw{(const float2*)w0, Cout * g.wl_stride, g.wl_stride, 1};
+  if (xhat) sw = S1Weights{(const float2*)(xhat + spec_xhat_floats(p, B)), Cout, 1, Cin * Cout};
+  const size_t lds = ((size_t)Cin * (Cout + 1) + 8 * Cout + 8 * Cin) * 8;
+  LAUNCHCHK((LV("k_s1_mix_bwd", 8, 0), launch("k_s1_mix", k_s1_mix_bwd, dim3(M), dim3(256), lds, st, w.part, (const float2*)xhat, sw,
+                   (float2*)dw0, g.wl_stride, dx ? w.hat : nullptr, w.dbpart, dbias, B, T, M, Cin, Cout, (float)g.s_i)));
+  if (!dx) return FNO_OK;
+  return spec1d_syn(st, Cin, B, T, w.hat, p->t.tinv_b, nullptr, dx, N, J);
 }
 
 struct SpecWs {
@@ -740,6 +827,7 @@ static SpecWs carve_spec(const FnoSpecPlan* p, int B, void* ws, size_t cap, bool
   return w;
 }
 extern "C" size_t fno_spec_workspace_bytes(const FnoSpecPlan* p, int B) {
+  if (p->g.ndim == 1) return carve_spec1d(p, B, nullptr, 0, nullptr).total;
   return carve_spec(p, B, nullptr, 0, nullptr).total;
 }
 // saved for the backward: the truncated input spectrum [B][Ktot][Cin] and the transposed packed weights [Ktot][Cout][Cin]
@@ -899,6 +987,7 @@ extern "C" int fno_spec_forward(const FnoSpecPlan* p, int B, const float* x, con
                                 float* y, float* xhat_save, void* ws, size_t ws_bytes, void* stream) {
   if (!p || !x || !wc || !y || B < 1) return fail(FNO_EINVAL, "fno_spec_forward: bad argument");
   hipStream_t st = (hipStream_t)stream;
+  if (p->g.ndim == 1) return spec1d_forward(p, st, B, x, wc[0], bias, y, xhat_save, ws, ws_bytes);
   const Geom& g = p->g;
   const int Cin = p->d.Cin, Cout = p->d.Cout;
   bool ok;
@@ -920,6 +1009,8 @@ extern "C" int fno_spec_backward(const FnoSpecPlan* p, int B, const float* dy, c
   if (dwc && !xhat) return fail(FNO_EINVAL, "weight gradients need the saved spectrum");
   if (dx && !wc && !xhat) return fail(FNO_EINVAL, "input gradient needs the weights (or the buffer saved by the forward)");
   hipStream_t st = (hipStream_t)stream;
+  if (p->g.ndim == 1)
+    return spec1d_backward(p, st, B, dy, xhat, wc ? wc[0] : nullptr, dx, dwc ? dwc[0] : nullptr, dbias, ws, ws_bytes);
   const Geom& g = p->g;
   const int Cin = p->d.Cin, Cout = p->d.Cout;
   bool ok;

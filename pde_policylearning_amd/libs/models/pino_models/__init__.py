@@ -1,2 +1,3 @@
-from .basics import SpectralConv2d, SpectralConv3d  # noqa: F401
+from .basics import SpectralConv1d, SpectralConv2d, SpectralConv3d  # noqa: F401
+from .fourier1d import FNO1d  # noqa: F401
 from .pinobserver import MultiplicativeNet, PINObserver2d, PINObserverFullField, PlanePredHead, PolicyModel2D  # noqa: F401

@@ -1,5 +1,5 @@
 """Dialect-C spectral convolutions with the reference surface
-(libs/models/pino_models/basics.py:64-96 SpectralConv2d, :99-143 SpectralConv3d): complex64
+(libs/models/pino_models/basics.py:30-58 SpectralConv1d, :64-96 SpectralConv2d, :99-143 SpectralConv3d): complex64
 parameters weights1..N initialised scale * U[0,1), torch-default ('backward') FFT norm, no bias.
 forward() runs in the HIP engine."""
 import torch
@@ -13,6 +13,24 @@ def _cweight(cin, cout, *modes, planes=False):
     outermost in memory (functional.plane_major) - shape, values and every tensor operation on it are unchanged"""
     w = (1.0 / (cin * cout)) * torch.rand(cin, cout, *modes, dtype=torch.cfloat)
     return nn.Parameter(F.to_plane_major(w) if planes else w)
+
+
+class SpectralConv1d(nn.Module):
+    """(B, Cin, N) -> (B, Cout, N): the first `modes1` bins of the real FFT times weights1 (basics.py:47-58).  Channels 32 / 64,
+    N a multiple of 128 in [128, 8192], modes1 <= 64 (fno_spec_plan_create); anything else raises."""
+
+    def __init__(self, in_channels, out_channels, modes1):
+        super().__init__()
+        self.in_channels, self.out_channels, self.modes1 = in_channels, out_channels, modes1
+        self.scale = 1 / (in_channels * out_channels)
+        self.weights1 = _cweight(in_channels, out_channels, modes1)
+
+    def direct_grad_params(self):
+        return [self.weights1]
+
+    def forward(self, x):
+        return F.spectral_conv(x, [self.weights1], None, (self.modes1,), "backward",
+                               direct_grads=getattr(self, "_direct_grads", False))
 
 
 class SpectralConv2d(nn.Module):

@@ -1,5 +1,5 @@
-"""The names `neuralop.models` exports in the reference (neuralop/models/__init__.py:1-7).  FNO / FNO2d / FNO3d, RNO2d and
-SpectralRegressor run on the HIP engine; FNO1d, TFNO*, SFNO and UNO keep their names and signatures and raise when
+"""The names `neuralop.models` exports in the reference (neuralop/models/__init__.py:1-7).  FNO / FNO1d / FNO2d / FNO3d, RNO2d and
+SpectralRegressor run on the HIP engine; TFNO*, SFNO and UNO keep their names and signatures and raise when
 constructed (outside the accelerated path)."""
 from .tfno import TFNO, TFNO1d, TFNO2d, TFNO3d  # noqa: F401
 from .tfno import FNO, FNO1d, FNO2d, FNO3d, Lifting, Projection  # noqa: F401

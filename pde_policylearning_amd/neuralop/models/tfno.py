@@ -1,5 +1,5 @@
-"""FNO / FNO2d / FNO3d with the reference constructor surface (neuralop/models/tfno.py:
-Lifting :11-20, Projection :23-38, FNO :107-211, FNO2d :342-458, FNO3d :467-580).
+"""FNO / FNO1d / FNO2d / FNO3d with the reference constructor surface (neuralop/models/tfno.py:
+Lifting :11-20, Projection :23-38, FNO :107-211, FNO1d :222-340, FNO2d :342-458, FNO3d :467-580).
 forward() runs the whole model in the HIP engine (functional.fno_model); with `use_mlp` it runs layer by layer, every block
 as one fused Fourier layer and one channel-MLP kernel."""
 import torch
@@ -180,8 +180,12 @@ class FNO3d(FNO):
 
 
 class FNO1d(FNO):
-    """Name kept for `from neuralop.models import FNO1d` (tfno.py:222-340).  One-dimensional grids are not on the
-    accelerated path (configs 1-5 are 2-D / 3-D): constructing one raises."""
+    """neuralop.models.FNO1d (tfno.py:222-340) on (B, in_channels, N) grids.  One-dimensional models exist only on the engine's
+    1-D kernels (k_spec1d.h): hidden width 32 or 64, N a multiple of 128 in [128, 8192], at most 64 kept bins.  forward() is
+    the lifting, one spectral + pointwise layer per block chained on PRE-activation tensors (the GELU behind block l - 1 is
+    applied while block l loads its input), and the projection head."""
+
+    WIDTHS = (32, 64)
 
     def __init__(self, n_modes_height, hidden_channels, in_channels=3, out_channels=1, lifting_channels=256,
                  projection_channels=256, incremental_n_modes=None, n_layers=4, output_scaling_factor=None,
@@ -190,7 +194,70 @@ class FNO1d(FNO):
                  joint_factorization=False, fixed_rank_modes=False, implementation='factorized',
                  decomposition_kwargs=dict(), domain_padding=None, domain_padding_mode='one-sided',
                  fft_norm='forward', **kwargs):
-        _unsupported("FNO1d (one-dimensional grids)")
+        if hidden_channels not in self.WIDTHS:
+            raise NotImplementedError(f"fnoengine FNO1d: hidden_channels={hidden_channels}; the one-dimensional kernels are built "
+                                      f"for hidden widths {self.WIDTHS}")
+        for name, on in (("use_mlp=True", use_mlp), ("separable=True", separable),
+                         ("output_scaling_factor", output_scaling_factor is not None)):
+            if on:
+                raise NotImplementedError(f"fnoengine FNO1d: {name} has no one-dimensional kernel")
+        super().__init__(
+            n_modes=(n_modes_height,), hidden_channels=hidden_channels,
+            in_channels=in_channels, out_channels=out_channels, lifting_channels=lifting_channels,
+            projection_channels=projection_channels, n_layers=n_layers, output_scaling_factor=None,
+            non_linearity=non_linearity, use_mlp=False, mlp_dropout=mlp_dropout,
+            mlp_expansion=mlp_expansion, incremental_n_modes=incremental_n_modes, norm=norm,
+            separable=False, preactivation=preactivation, factorization=factorization, rank=rank,
+            joint_factorization=joint_factorization, fixed_rank_modes=fixed_rank_modes,
+            implementation=implementation, decomposition_kwargs=decomposition_kwargs,
+            domain_padding=domain_padding, domain_padding_mode=domain_padding_mode, fft_norm=fft_norm)
+        self.n_modes_height = n_modes_height
+
+    def fused_supported(self, x):
+        """the whole-model plan (fno_model_plan_create) has no one-dimensional form: forward() below is the layer chain"""
+        return False
+
+    def _covered(self, x, modes, gelu_in):
+        """whether the 1-D kernels take this input; decided once per (shape, device, kept bins) - the probe needs a tensor of
+        the hidden shape, which a forward pass should not allocate every time"""
+        key = (tuple(x.shape), x.device, modes)
+        seen = self.__dict__.setdefault("_covered_shapes", {})
+        if key not in seen:
+            ok = x.dim() == 3 and x.shape[1] == self.in_channels
+            if ok:
+                u = x.new_empty((x.shape[0], self.hidden_channels, x.shape[2]))
+                ok = all(F.spectral_layer_supported(u, 1, modes, self.fft_norm, modes[0], g) for g in set(gelu_in))
+            seen[key] = ok
+        return seen[key]
+
+    def forward(self, x):
+        F._require_cuda(x, "x")
+        blk, convs, c = self.fno_blocks, self.fno_blocks.convs, self.hidden_channels
+        modes = tuple(convs.half_n_modes)
+        gelu_in = [l > 0 and blk.gelu_after(l - 1) for l in range(self.n_layers)]
+        if not self._covered(x, modes, gelu_in):
+            raise RuntimeError(f"fnoengine FNO1d: no one-dimensional kernel for input {tuple(x.shape)} with {modes[0]} kept bins "
+                               f"(needs (B, {self.in_channels}, N), N a multiple of 128 in [128, 8192], at most 64 kept bins)")
+        if getattr(self, "_direct_grads", False) and torch.is_grad_enabled():
+            # a direct-write bucket (trainer.FlatGradBucket(direct_module=...)) does not clear this model's gradients: it
+            # expects the engine to overwrite them.  This forward hands every gradient to autograd, which accumulates into
+            # the bucket's views, so they are cleared here (as FNO.forward does on its layer-by-layer route)
+            for p in self.parameters():
+                if p.grad is not None:
+                    p.grad.zero_()
+        if F.lifting_supported(x, c):
+            u = F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
+        else:
+            u = self.lifting(x)
+        for l in range(self.n_layers):
+            u = F.spectral_pointwise_layer(u, convs.layer_weights(l), modes, self.fft_norm, blk.fno_skips[l].weight,
+                                           convs.bias[l].reshape(-1), input_gelu=gelu_in[l])
+        if blk.gelu_after(self.n_layers - 1):          # only a one-layer stack ends on an activation (fno_block.py:149)
+            u = self.non_linearity(u)
+        prj = self.projection
+        if F.projection_supported(u, self.projection_channels, self.out_channels):
+            return F.projection_head(u, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
+        return prj(u)
 
 
 def _with_defaults(new_name, cls, **defaults):
