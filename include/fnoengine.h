@@ -307,6 +307,23 @@ int fno_pino_loss_backward(int batch, int n, int nt, const float* u, const float
                            size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Burgers residual loss of the PINO models: FDM_Burgers + PINO_loss (libs/pino_utils/losses.py:200-243; the loss of
+ * train_2d_burger, libs/pino_utils/train_2d.py:119-194).
+ *   u (B, nt, nx) model output with x contiguous, u0 (B, nx) initial condition, visc a host scalar, domain length 1,
+ *   dt = 1 / (nt - 1);  Du[b, j] = (u[b, j+1] - u[b, j-1]) / (2 dt) + ux u - visc uxx on the rows j = 1 .. nt - 2,
+ *   ux / uxx the spectral derivatives along x (no Nyquist term in ux, -(pi nx)^2 in uxx);
+ *   loss_f = mean Du^2, loss_u = mean (u[:, 0] - u0)^2 (F.mse_loss), both float64 sums in a fixed order.
+ * forward leaves Du (B, nt - 2, nx) first in `ws`, then ux and the partial sums (fno_burgers_loss_workspace_bytes);
+ * backward reads them and writes du = g_u * dloss_u/du + g_f * dloss_f/du (device scalars, NULL = 1) into all of (B, nt, nx).
+ * nx must be 32, 64 or 128 (FNO_EUNSUPPORTED otherwise; odd nx, nt < 3 and batch < 1 are FNO_EINVAL); the checks need no GPU.
+ * ---------------------------------------------------------------------- */
+size_t fno_burgers_loss_workspace_bytes(int batch, int nt, int nx);
+int fno_burgers_loss_forward(int batch, int nt, int nx, const float* u, const float* u0, float visc, float* loss_u,
+                             float* loss_f, void* ws, size_t ws_bytes, void* stream);
+int fno_burgers_loss_backward(int batch, int nt, int nx, const float* u, const float* u0, float visc, const float* g_u,
+                              const float* g_f, float* du, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Gates of the recurrent neural operator cell, neuralop/models/rno.py:254-260 (all tensors (B, C, X, Y) fp32,
  * n elements, 16-byte aligned, n % 4 == 0; b* are the cell's SCALAR biases on the device):
  *   reset gate : r = sigmoid(a3 + a4 + b2), rh = r * h                                   (:256-257)

@@ -33,6 +33,7 @@
 #include "k_spec1d.h"
 #include "k_pino_loss.h"
 #include "k_pino_loss2.h"
+#include "k_burgers_loss.h"
 #include "k_rno_gates.h"
 #include "k_train.h"
 
@@ -2319,6 +2320,80 @@ extern "C" int fno_pino_loss_backward(int B, int n, int T, const float* u, const
                    (const float*)w.dws, (const float*)(w.fields + 4 * np), (const float*)w.coef_f, (const float*)w.coef_ic,
                    g_f, g_ic, B, n * n, T, a.inv2dt, du));
   return FNO_OK;
+}
+
+// ===========================================================================
+// Burgers residual loss (k_burgers_loss.h): FDM_Burgers + PINO_loss, libs/pino_utils/losses.py:200-243
+// ===========================================================================
+static int burgers_check(int B, int nt, int nx) {
+  if (B < 1) return fail(FNO_EINVAL, "burgers loss: batch=%d (at least 1)", B);
+  if (nt < 3) return fail(FNO_EINVAL, "burgers loss: nt=%d (at least 3 time rows: one interior row)", nt);
+  if (nx < 2 || (nx & 1)) return fail(FNO_EINVAL, "burgers loss: nx=%d (even: the wavenumber table has 2 (nx / 2) entries)", nx);
+  if (nx != 32 && nx != 64 && nx != 128)
+    return fail(FNO_EUNSUPPORTED, "burgers loss: nx=%d (rows of 32, 64 or 128 points)", nx);
+  if ((size_t)B * (size_t)((nt + BURG_TJ - 1) / BURG_TJ) > 0x7fffffffull)
+    return fail(FNO_EUNSUPPORTED, "burgers loss: batch=%d times nt=%d exceeds the grid limit", B, nt);
+  return FNO_OK;
+}
+static int burgers_tiles_fwd(int nt) { return (nt - 2 + BURG_TJ - 1) / BURG_TJ; }
+static int burgers_tiles_bwd(int nt) { return (nt + BURG_TJ - 1) / BURG_TJ; }
+struct BurgersWs { float *Du, *ux; double *part_f, *part_u; size_t total; bool ok; };
+static BurgersWs carve_burgers(int B, int nt, int nx, void* ws, size_t ws_bytes) {
+  Carver c(ws, ws_bytes);
+  const size_t np = (size_t)B * (nt - 2) * nx;
+  BurgersWs w;
+  w.Du = c.take<float>(np);
+  w.ux = c.take<float>(np);
+  w.part_f = c.take<double>((size_t)B * burgers_tiles_fwd(nt));
+  w.part_u = c.take<double>(B);
+  w.total = c.off;
+  w.ok = c.ok;
+  return w;
+}
+extern "C" size_t fno_burgers_loss_workspace_bytes(int batch, int nt, int nx) {
+  if (batch < 1 || nt < 3 || nx < 1) return 0;
+  return carve_burgers(batch, nt, nx, nullptr, 0).total;
+}
+static BurgersArgs burgers_args(int B, int nt, int nx, const float* u, const float* u0, float visc, const BurgersWs& w) {
+  BurgersArgs a;
+  memset(&a, 0, sizeof(a));
+  a.u = u; a.u0 = u0; a.Du = w.Du; a.ux = w.ux; a.part_f = w.part_f; a.part_u = w.part_u;
+  a.B = B; a.nt = nt; a.visc = visc;
+  a.inv2dt = (float)((double)(nt - 1) / 2.0);
+  a.scale_f = (float)(2.0 / ((double)B * (nt - 2) * nx));
+  a.scale_u = (float)(2.0 / ((double)B * nx));
+  return a;
+}
+extern "C" int fno_burgers_loss_forward(int B, int nt, int nx, const float* u, const float* u0, float visc, float* loss_u,
+                                        float* loss_f, void* ws, size_t ws_bytes, void* stream) {
+  LAUNCHCHK(burgers_check(B, nt, nx));
+  if (!u || !u0 || !loss_u || !loss_f || !ws) return fail(FNO_EINVAL, "fno_burgers_loss_forward: null argument");
+  BurgersWs w = carve_burgers(B, nt, nx, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  BurgersArgs a = burgers_args(B, nt, nx, u, u0, visc, w);
+  a.tiles = burgers_tiles_fwd(nt);
+  const dim3 grid((unsigned)(B * a.tiles)), blk(BURG_NT);
+  if (nx == 32) LAUNCHCHK(launch("k_burgers_fwd", k_burgers_fwd<32>, grid, blk, 0, st, a));
+  else if (nx == 64) LAUNCHCHK(launch("k_burgers_fwd", k_burgers_fwd<64>, grid, blk, 0, st, a));
+  else LAUNCHCHK(launch("k_burgers_fwd", k_burgers_fwd<128>, grid, blk, 0, st, a));
+  return launch("k_burgers_finish", k_burgers_finish, dim3(1), dim3(256), 0, st, (const double*)w.part_f, B * a.tiles,
+                (const double*)w.part_u, B, 1.0 / ((double)B * (nt - 2) * nx), 1.0 / ((double)B * nx), loss_u, loss_f);
+}
+extern "C" int fno_burgers_loss_backward(int B, int nt, int nx, const float* u, const float* u0, float visc, const float* g_u,
+                                         const float* g_f, float* du, void* ws, size_t ws_bytes, void* stream) {
+  LAUNCHCHK(burgers_check(B, nt, nx));
+  if (!u || !u0 || !du || !ws) return fail(FNO_EINVAL, "fno_burgers_loss_backward: null argument");
+  BurgersWs w = carve_burgers(B, nt, nx, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  BurgersArgs a = burgers_args(B, nt, nx, u, u0, visc, w);
+  a.g_u = g_u; a.g_f = g_f; a.du = du;
+  a.tiles = burgers_tiles_bwd(nt);
+  const dim3 grid((unsigned)(B * a.tiles)), blk(BURG_NT);
+  hipStream_t st = (hipStream_t)stream;
+  if (nx == 32) return launch("k_burgers_bwd", k_burgers_bwd<32>, grid, blk, 0, st, a);
+  if (nx == 64) return launch("k_burgers_bwd", k_burgers_bwd<64>, grid, blk, 0, st, a);
+  return launch("k_burgers_bwd", k_burgers_bwd<128>, grid, blk, 0, st, a);
 }
 
 // ===========================================================================

@@ -24,8 +24,8 @@ FNO_DEV void lds_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 FNO_DEV int opaque_tid(int tid) { asm volatile("" : "+v"(tid)); return tid; }
 
 // N-point FFTs of the N lines `G + line * line_stride` (elements `elem_stride` apart) by NWV waves.
-// tw[k] = exp(-2 pi i k / N), k < N/2.
-template <int N, bool INVERSE, int NWV>
+// tw[k] = exp(-2 pi i k / N), k < N/2.  NLINES: fewer lines than N (k_burgers_loss.h: a tile of time rows).
+template <int N, bool INVERSE, int NWV, int NLINES = N>
 FNO_DEV void fft_lines(float2* G, int line_stride, int elem_stride, const float2* tw, int wave, int lane) {
   constexpr int LPL = N / 2;            // butterflies (lanes) per line
   constexpr int LW = 64 / LPL;          // lines per wave pass
@@ -35,7 +35,7 @@ FNO_DEV void fft_lines(float2* G, int line_stride, int elem_stride, const float2
   // registers per direction for the whole kernel, which has 128 per lane - the lane's butterfly index is made opaque per line so that
   // they are recomputed per line: a handful of integer operations beside four LDS accesses per stage)
   const int jl = lane % LPL;
-  for (int line = wave * LW + sub; line < N; line += NWV * LW) {
+  for (int line = wave * LW + sub; line < NLINES; line += NWV * LW) {
     float2* L = G + line * line_stride;
     int j = jl;
     if (N >= 128) asm volatile("" : "+v"(j));

@@ -903,6 +903,78 @@ def pino_loss(u, u0, forcing, visc, t_interval=1.0):
 
 
 # ----------------------------------------------------------------------------
+# Burgers residual loss (FDM_Burgers + PINO_loss, libs/pino_utils/losses.py:200-243)
+# ----------------------------------------------------------------------------
+BURGERS_NX = (32, 64, 128)
+
+
+def _burgers_rows(e, u):
+    """u as (B, nt, nx): a trailing singleton channel is dropped (the model's output is (B, nt, nx, 1))"""
+    if u.dim() == 4 and u.shape[-1] == 1:
+        u = u[..., 0]
+    if u.dim() != 3:
+        raise RuntimeError(f"fnoengine {e}: `u` must be (B, nt, nx) or (B, nt, nx, 1) (got {tuple(u.shape)})")
+    return u
+
+
+def burgers_loss_supported(u):
+    """the shapes k_burgers_loss.h takes: float32 on the GPU, (B, nt, nx[, 1]) with nt >= 3 and nx in BURGERS_NX"""
+    if u.dim() == 4 and u.shape[-1] == 1:
+        u = u[..., 0]
+    return bool(u.is_cuda and u.dtype == torch.float32 and u.dim() == 3 and u.shape[0] >= 1 and u.shape[1] >= 3
+                and u.shape[2] in BURGERS_NX)
+
+
+def _burgers_forward(e, u, u0, visc):
+    """(u_c, u0_c, losses (2,), ws, nws) of one forward call; `u0` None: the initial-condition term is taken against u[:, 0]"""
+    _require_cuda(u, "u")
+    u_c = _burgers_rows(e, u).contiguous()
+    B, nt, nx = u_c.shape
+    u0_c = u_c[:, 0].contiguous() if u0 is None else _operand(e, "u0", u0, u, numel=B * nx).reshape(B, nx)
+    nws = _lib.lib().fno_burgers_loss_workspace_bytes(B, nt, nx)
+    ws = _bytes(nws, u.device)
+    losses = torch.empty(2, dtype=torch.float32, device=u.device)
+    _call("burgers_loss_forward", u.device, "fno_burgers_loss_forward", B, nt, nx, u_c, u0_c, float(visc), losses[0:1],
+          losses[1:2], ws, nws, STREAM)
+    return u_c, u0_c, losses, ws, nws
+
+
+class _BurgersLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, u0, visc):
+        u_c, u0_c, losses, ws, nws = _burgers_forward("burgers_loss", u, u0, visc)
+        ctx.save_for_backward(u_c, u0_c, ws)
+        ctx.meta = (float(visc), nws, u.shape)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_u, g_f):
+        u_c, u0_c, ws = ctx.saved_tensors
+        visc, nws, shape = ctx.meta
+        B, nt, nx = u_c.shape
+        du = torch.empty_like(u_c)
+        gu = _operand("burgers_loss backward", "g_u", g_u.contiguous().to(torch.float32), u_c, numel=1).reshape(1)
+        gf = _operand("burgers_loss backward", "g_f", g_f.contiguous().to(torch.float32), u_c, numel=1).reshape(1)
+        _call("burgers_loss_backward", du.device, "fno_burgers_loss_backward", B, nt, nx, u_c, u0_c, visc, gu, gf, du, ws, nws,
+              STREAM)
+        return du.view(shape), None, None
+
+
+def burgers_loss(u, u0, visc):
+    """(loss_u, loss_f) of PINO_loss (libs/pino_utils/losses.py:223-243): u (B, nt, nx) or (B, nt, nx, 1) model output,
+    u0 (B, nx) initial condition, visc a host float; domain length 1.  Differentiable w.r.t. u.  nx in {32, 64, 128}."""
+    return _BurgersLossFn.apply(u, u0, visc)
+
+
+def burgers_residual(u, visc):
+    """Du (B, nt - 2, nx) of FDM_Burgers (libs/pino_utils/losses.py:200-220) as the forward kernel of burgers_loss stores
+    it: the first array of its workspace (fno_abi.hip carve_burgers).  Not differentiable."""
+    u_c, _, _, ws, _ = _burgers_forward("burgers_residual", u.detach(), None, visc)
+    B, nt, nx = u_c.shape
+    return ws[:4 * B * (nt - 2) * nx].view(torch.float32).reshape(B, nt - 2, nx)
+
+
+# ----------------------------------------------------------------------------
 # channel-flow RHS and the physics-informed loss (libs/envs/control_env.py:429-530, 627-633)
 # ----------------------------------------------------------------------------
 class ChannelGrid:

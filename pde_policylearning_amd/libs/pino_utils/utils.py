@@ -1,5 +1,7 @@
 """libs/pino_utils/utils.py surface used by the PINO fine-tuning loop: the space-time input grid, checkpointing, small helpers
-(get_grid3d :107-115, save_ckpt :178-194, count_params, dict2str :197-201)."""
+(get_grid3d :107-115, save_checkpoint :156-174, save_ckpt :178-194, count_params, dict2str :197-201)."""
+import os
+
 import numpy as np
 import torch
 
@@ -16,6 +18,16 @@ def get_grid3d(S, T, time_scale=1.0, device='cpu'):
 
 def count_params(model):
     return sum(p.numel() * (2 if p.is_complex() else 1) for p in model.parameters())
+
+
+def save_checkpoint(path, name, model, optimizer=None):
+    """{'model', 'optim'} under checkpoints/<path>/<name>; a wrapped model (DistributedDataParallel) saves its module's state,
+    no optimizer saves 0.0 (utils.py:156-174)."""
+    ckpt_dir = 'checkpoints/%s/' % path
+    os.makedirs(ckpt_dir, exist_ok=True)
+    state = model.module.state_dict() if hasattr(model, 'module') else model.state_dict()
+    torch.save({'model': state, 'optim': optimizer.state_dict() if optimizer is not None else 0.0}, ckpt_dir + name)
+    print('Checkpoint is saved at %s' % ckpt_dir + name)
 
 
 def save_ckpt(path, model, optimizer=None, scheduler=None):
