@@ -324,6 +324,26 @@ int fno_burgers_loss_backward(int batch, int nt, int nx, const float* u, const f
                               const float* g_f, float* du, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Darcy residual loss of the PINO models: FDM_Darcy + darcy_loss (libs/pino_utils/losses.py:6-65) with the mollifier and
+ * the relative-L2 data term of train_2d_operator (libs/pino_utils/train_2d.py:58-82) in the same launches.
+ *   out, a, y (B, S, S) with the first grid index x, h = 1 / (S - 1);  pred = out * mol, mol (S, S) or NULL (pred = out);
+ *   Du[b, p, q] = -( a[p+1,q] (pred[p+2,q] - pred[p,q]) - a[p-1,q] (pred[p,q] - pred[p-2,q])
+ *                  + a[p,q+1] (pred[p,q+2] - pred[p,q]) - a[p,q-1] (pred[p,q] - pred[p,q-2]) ) / (4 h^2),  p, q = 2 .. S-3;
+ *   loss_f = mean_b ||Du_b - 1||_2 / (S - 4);  loss_data = mean_b ||pred_b - y_b||_2 / ||y_b||_2, only with y (y and
+ *   loss_data are given together or both NULL, FNO_EINVAL otherwise).  Sums are float64 in a fixed order.
+ * forward leaves Du (B, S - 4, S - 4) first in `ws`, then the partial sums and the per-sample norms
+ * (fno_darcy_loss_workspace_bytes); backward reads them and writes dout = g_data * dloss_data/dout + g_f * dloss_f/dout
+ * (device scalars, NULL = 1; `a` is data and gets no gradient) into all of (B, S, S).  A sample whose residual norm is
+ * exactly zero contributes a zero gradient (the reference's 0 / 0 is NaN there).
+ * Every S from 5 to 4096: S < 5 and batch < 1 are FNO_EINVAL, S > 4096 FNO_EUNSUPPORTED; the checks need no GPU.
+ * ---------------------------------------------------------------------- */
+size_t fno_darcy_loss_workspace_bytes(int batch, int S);
+int fno_darcy_loss_forward(int batch, int S, const float* out, const float* mol, const float* a, const float* y,
+                           float* loss_data, float* loss_f, void* ws, size_t ws_bytes, void* stream);
+int fno_darcy_loss_backward(int batch, int S, const float* out, const float* mol, const float* a, const float* y,
+                            const float* g_data, const float* g_f, float* dout, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Gates of the recurrent neural operator cell, neuralop/models/rno.py:254-260 (all tensors (B, C, X, Y) fp32,
  * n elements, 16-byte aligned, n % 4 == 0; b* are the cell's SCALAR biases on the device):
  *   reset gate : r = sigmoid(a3 + a4 + b2), rh = r * h                                   (:256-257)

@@ -209,6 +209,10 @@ def lib():
     L.fno_burgers_loss_workspace_bytes.restype = sz
     L.fno_burgers_loss_forward.argtypes = [ci, ci, ci, vp, vp, fl, vp, vp, vp, sz, vp]
     L.fno_burgers_loss_backward.argtypes = [ci, ci, ci, vp, vp, fl, vp, vp, vp, vp, sz, vp]
+    L.fno_darcy_loss_workspace_bytes.argtypes = [ci, ci]
+    L.fno_darcy_loss_workspace_bytes.restype = sz
+    L.fno_darcy_loss_forward.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.fno_darcy_loss_backward.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.fno_model_backward_dx.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
                                         C.POINTER(FnoModelGrads), vp, vp, sz, vp]
     L.fno_model_backward_part.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
@@ -255,6 +259,7 @@ EXPORTED_SYMBOLS = [
     "fno_rno_output_gate_forward", "fno_rno_output_gate_backward",
     "fno_pino_loss_workspace_bytes", "fno_pino_loss_forward", "fno_pino_loss_backward",
     "fno_burgers_loss_workspace_bytes", "fno_burgers_loss_forward", "fno_burgers_loss_backward",
+    "fno_darcy_loss_workspace_bytes", "fno_darcy_loss_forward", "fno_darcy_loss_backward",
     "fno_chanflow_pack_metrics", "fno_chanflow_rhs", "fno_chanflow_pde_loss_workspace_bytes",
     "fno_chanflow_pde_loss_forward", "fno_chanflow_pde_loss_backward",
     "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",

@@ -34,6 +34,7 @@
 #include "k_pino_loss.h"
 #include "k_pino_loss2.h"
 #include "k_burgers_loss.h"
+#include "k_darcy_loss.h"
 #include "k_rno_gates.h"
 #include "k_train.h"
 
@@ -2394,6 +2395,70 @@ extern "C" int fno_burgers_loss_backward(int B, int nt, int nx, const float* u, 
   if (nx == 32) return launch("k_burgers_bwd", k_burgers_bwd<32>, grid, blk, 0, st, a);
   if (nx == 64) return launch("k_burgers_bwd", k_burgers_bwd<64>, grid, blk, 0, st, a);
   return launch("k_burgers_bwd", k_burgers_bwd<128>, grid, blk, 0, st, a);
+}
+
+// ===========================================================================
+// Darcy residual loss (k_darcy_loss.h): FDM_Darcy + darcy_loss, libs/pino_utils/losses.py:6-65, with the mollifier and the
+// relative-L2 data term of train_2d.py:58-82
+// ===========================================================================
+static int darcy_tiles(int S) { return (S - 4 + DARCY_T - 1) / DARCY_T; }
+static int darcy_check(int B, int S) {
+  if (B < 1) return fail(FNO_EINVAL, "darcy loss: batch=%d (at least 1)", B);
+  if (S < 5) return fail(FNO_EINVAL, "darcy loss: S=%d (at least 5 points a side: one residual cell)", S);
+  if (S > DARCY_SMAX) return fail(FNO_EUNSUPPORTED, "darcy loss: S=%d (at most %d points a side)", S, DARCY_SMAX);
+  if ((size_t)B * (size_t)darcy_tiles(S) * (size_t)darcy_tiles(S) > 0x7fffffffull)
+    return fail(FNO_EUNSUPPORTED, "darcy loss: batch=%d times S=%d exceeds the grid limit", B, S);
+  return FNO_OK;
+}
+struct DarcyWs { float* Du; double *part, *norms; size_t total; bool ok; };
+static DarcyWs carve_darcy(int B, int S, void* ws, size_t ws_bytes) {
+  Carver c(ws, ws_bytes);
+  DarcyWs w;
+  w.Du = c.take<float>((size_t)B * (S - 4) * (S - 4));
+  w.part = c.take<double>((size_t)B * darcy_tiles(S) * darcy_tiles(S) * 3);
+  w.norms = c.take<double>((size_t)B * 3);
+  w.total = c.off;
+  w.ok = c.ok;
+  return w;
+}
+extern "C" size_t fno_darcy_loss_workspace_bytes(int batch, int S) {
+  if (batch < 1 || S < 5 || S > DARCY_SMAX) return 0;
+  return carve_darcy(batch, S, nullptr, 0).total;
+}
+static DarcyArgs darcy_args(int B, int S, const float* out, const float* mol, const float* a, const float* y, const DarcyWs& w) {
+  DarcyArgs d;
+  memset(&d, 0, sizeof(d));
+  d.out = out; d.mol = mol; d.a = a; d.y = y; d.Du = w.Du; d.part = w.part; d.norms = w.norms;
+  d.B = B; d.S = S; d.tiles = darcy_tiles(S);
+  d.inv4h2 = (float)((double)(S - 1) * (double)(S - 1) / 4.0);
+  return d;
+}
+extern "C" int fno_darcy_loss_forward(int B, int S, const float* out, const float* mol, const float* a, const float* y,
+                                      float* loss_data, float* loss_f, void* ws, size_t ws_bytes, void* stream) {
+  LAUNCHCHK(darcy_check(B, S));
+  if ((y != nullptr) != (loss_data != nullptr))
+    return fail(FNO_EINVAL, "fno_darcy_loss_forward: y=%p and loss_data=%p (both or neither: the data term needs its target and its "
+                "result)", (const void*)y, (void*)loss_data);
+  if (!out || !a || !loss_f || !ws) return fail(FNO_EINVAL, "fno_darcy_loss_forward: null argument");
+  DarcyWs w = carve_darcy(B, S, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  DarcyArgs d = darcy_args(B, S, out, mol, a, y, w);
+  const int per = d.tiles * d.tiles;
+  LAUNCHCHK(launch("k_darcy_fwd", k_darcy_fwd, dim3((unsigned)(B * per)), dim3(DARCY_NT), 0, st, d));
+  return launch("k_darcy_finish", k_darcy_finish, dim3(1), dim3(256), 0, st, (const double*)w.part, B, per, S, w.norms, loss_data,
+                loss_f);
+}
+extern "C" int fno_darcy_loss_backward(int B, int S, const float* out, const float* mol, const float* a, const float* y,
+                                       const float* g_data, const float* g_f, float* dout, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  LAUNCHCHK(darcy_check(B, S));
+  if (!out || !a || !dout || !ws) return fail(FNO_EINVAL, "fno_darcy_loss_backward: null argument");
+  DarcyWs w = carve_darcy(B, S, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_ENOMEM, "workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  DarcyArgs d = darcy_args(B, S, out, mol, a, y, w);
+  d.g_data = g_data; d.g_f = g_f; d.dout = dout;
+  return launch("k_darcy_bwd", k_darcy_bwd, dim3((unsigned)(B * d.tiles * d.tiles)), dim3(DARCY_NT), 0, (hipStream_t)stream, d);
 }
 
 // ===========================================================================

@@ -975,6 +975,86 @@ def burgers_residual(u, visc):
 
 
 # ----------------------------------------------------------------------------
+# Darcy residual loss (FDM_Darcy + darcy_loss, libs/pino_utils/losses.py:6-65; mollifier and data term of train_2d.py:58-82)
+# ----------------------------------------------------------------------------
+DARCY_S_MIN, DARCY_S_MAX = 5, 4096           # csrc/k_darcy_loss.h DARCY_SMAX
+
+
+def _darcy_plane(e, name, t):
+    """t as (B, S, S): a trailing singleton channel is dropped (the model's output is (B, S, S, 1))"""
+    if t.dim() == 4 and t.shape[-1] == 1:
+        t = t[..., 0]
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise RuntimeError(f"fnoengine {e}: `{name}` must be (B, S, S) or (B, S, S, 1) on a square grid (got {tuple(t.shape)})")
+    return t
+
+
+def darcy_loss_supported(u):
+    """the shapes k_darcy_loss.h takes: float32 on the GPU, (B, S, S[, 1]) with DARCY_S_MIN <= S <= DARCY_S_MAX"""
+    if u.dim() == 4 and u.shape[-1] == 1:
+        u = u[..., 0]
+    return bool(u.is_cuda and u.dtype == torch.float32 and u.dim() == 3 and u.shape[0] >= 1 and u.shape[1] == u.shape[2]
+                and DARCY_S_MIN <= u.shape[1] <= DARCY_S_MAX)
+
+
+def _darcy_forward(e, u, a, y, mollifier):
+    """(u_c, a_c, y_c, mol_c, losses (2,): data, f, ws, nws) of one forward call"""
+    _require_cuda(u, "u")
+    u_c = _darcy_plane(e, "u", u).contiguous()
+    B, S, _ = u_c.shape
+    a_c = _operand(e, "a", _darcy_plane(e, "a", a), u, shape=u_c.shape)
+    y_c = None if y is None else _operand(e, "y", y, u, numel=B * S * S).reshape(B, S, S)
+    mol_c = None if mollifier is None else _operand(e, "mollifier", mollifier, u, numel=S * S).reshape(S, S)
+    nws = _lib.lib().fno_darcy_loss_workspace_bytes(B, S)
+    ws = _bytes(nws, u.device)
+    losses = torch.empty(2, dtype=torch.float32, device=u.device)
+    _call("darcy_loss_forward", u.device, "fno_darcy_loss_forward", B, S, u_c, mol_c, a_c, y_c,
+          None if y_c is None else losses[0:1], losses[1:2], ws, nws, STREAM)
+    return u_c, a_c, y_c, mol_c, losses, ws, nws
+
+
+class _DarcyLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, a, y, mollifier):
+        u_c, a_c, y_c, mol_c, losses, ws, nws = _darcy_forward("darcy_loss", u, a, y, mollifier)
+        empty = u_c.new_empty(0)
+        ctx.save_for_backward(u_c, a_c, empty if y_c is None else y_c, empty if mol_c is None else mol_c, ws)
+        ctx.meta = (y_c is not None, mol_c is not None, nws, u.shape)
+        return losses[0], losses[1]                  # without y, losses[0] is never written and darcy_loss drops it
+
+    @staticmethod
+    def backward(ctx, g_data, g_f):
+        u_c, a_c, y_c, mol_c, ws = ctx.saved_tensors
+        has_y, has_mol, nws, shape = ctx.meta
+        B, S, _ = u_c.shape
+        dout = torch.empty_like(u_c)
+        e = "darcy_loss backward"
+        gd = _operand(e, "g_data", g_data.contiguous().to(torch.float32), u_c, numel=1).reshape(1) if has_y else None
+        gf = _operand(e, "g_f", g_f.contiguous().to(torch.float32), u_c, numel=1).reshape(1)
+        _call("darcy_loss_backward", dout.device, "fno_darcy_loss_backward", B, S, u_c, mol_c if has_mol else None, a_c,
+              y_c if has_y else None, gd, gf, dout, ws, nws, STREAM)
+        return dout.view(shape), None, None, None
+
+
+def darcy_loss(u, a, y=None, mollifier=None):
+    """loss_f, or (loss_data, loss_f) when `y` is given: darcy_loss (libs/pino_utils/losses.py:39-65) of pred = u * mollifier
+    and LpLoss(size_average=True)(pred, y) (train_2d.py:75-82) in one fused call.  u (B, S, S) or (B, S, S, 1) model output,
+    a (B, S, S) coefficient (data: no gradient; `x[..., 0]`, non-contiguous, is copied), y (B, S, S) solution, mollifier
+    (S, S); any S from 5 up.  Differentiable w.r.t. u.  A sample whose residual norm ||Du_b - 1|| is exactly zero contributes
+    a zero gradient (the reference's autograd gives NaN there)."""
+    loss_data, loss_f = _DarcyLossFn.apply(u, a, y, mollifier)
+    return loss_f if y is None else (loss_data, loss_f)
+
+
+def darcy_residual(u, a, mollifier=None):
+    """Du (B, S - 4, S - 4) of FDM_Darcy (libs/pino_utils/losses.py:6-36) on u * mollifier as the forward kernel of
+    darcy_loss stores it: the first array of its workspace (fno_abi.hip carve_darcy).  Not differentiable."""
+    u_c, _, _, _, _, ws, _ = _darcy_forward("darcy_residual", u.detach(), a, None, mollifier)
+    B, S, _ = u_c.shape
+    return ws[:4 * B * (S - 4) * (S - 4)].view(torch.float32).reshape(B, S - 4, S - 4)
+
+
+# ----------------------------------------------------------------------------
 # channel-flow RHS and the physics-informed loss (libs/envs/control_env.py:429-530, 627-633)
 # ----------------------------------------------------------------------------
 class ChannelGrid:

@@ -1,14 +1,15 @@
 """libs/pino_utils/datasets.py surface used by the PINO fine-tuning loop (train_pino.py:188-204):
 `MultipleReynoldsKFaDataset` (:548-617) on the reference's files - an `.npz` with `data1` (N, T, S, S) vorticity
 trajectories and `data2` (N,) Reynolds numbers when the path contains "multi_reynolds", otherwise one `.npy` whose
-name carries `Re<digits>` - and `sample_data` (:24-27)."""
+name carries `Re<digits>` - and `sample_data` (:24-27); and the Darcy sets of train_2d_operator / eval_darcy: `DarcyFlow`
+(:368-387) and `DarcyCombo` (:416-442) on a MATLAB file with `coeff` and `sol` (N, nx, nx)."""
 import re as _re
 
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from .utils import get_grid3d
+from .utils import get_grid3d, torch2dgrid
 
 
 def sample_data(loader):
@@ -77,3 +78,59 @@ class MultipleReynoldsKFaDataset(Dataset):
 
     def __len__(self):
         return self.data.shape[0]
+
+
+def _darcy_arrays(datapath):
+    """`coeff` and `sol` of a MATLAB file (scipy.io is needed for that alone), or of a mapping that holds both arrays"""
+    if hasattr(datapath, 'keys'):
+        return datapath['coeff'], datapath['sol']
+    import scipy.io
+    data = scipy.io.loadmat(datapath)
+    return data['coeff'], data['sol']
+
+
+def _darcy_points(nx, sub):
+    return int(nx // sub) + 1 if sub > 1 else nx
+
+
+class DarcyFlow(Dataset):
+    """Items (x [S, S, 3] = (a, mesh x, mesh y), u [S, S]) of samples offset .. offset + num, every `sub`-th grid point:
+    S = nx // sub + 1 (nx itself when sub is 1).  `mesh` is torch2dgrid(S, S)."""
+
+    def __init__(self, datapath, nx, sub, offset=0, num=1):
+        self.S = _darcy_points(nx, sub)
+        a, u = _darcy_arrays(datapath)
+        self.a = torch.tensor(np.asarray(a[offset: offset + num, ::sub, ::sub]), dtype=torch.float)
+        self.u = torch.tensor(np.asarray(u[offset: offset + num, ::sub, ::sub]), dtype=torch.float)
+        self.mesh = torch2dgrid(self.S, self.S)
+
+    def __len__(self):
+        return self.a.shape[0]
+
+    def __getitem__(self, item):
+        return torch.cat([self.a[item].unsqueeze(2), self.mesh], dim=2), self.u[item]
+
+
+class DarcyCombo(Dataset):
+    """Items (data_ic [S, S, 3], u [S, S], pde_ic [pde_S, pde_S, 3]): the coefficient with its solution on the data grid
+    (every `sub`-th point) and the same coefficient alone on the equation grid (every `pde_sub`-th); `mesh`, `pde_mesh`.
+    As in the reference, pde_S is nx when `sub` (not pde_sub) is 1 (:424)."""
+
+    def __init__(self, datapath, nx, sub, pde_sub, num=1000, offset=0):
+        super().__init__()
+        self.S = _darcy_points(nx, sub)
+        self.pde_S = int(nx // pde_sub) + 1 if sub > 1 else nx
+        a, u = _darcy_arrays(datapath)
+        self.a = torch.tensor(np.asarray(a[offset: offset + num, ::sub, ::sub]), dtype=torch.float)
+        self.u = torch.tensor(np.asarray(u[offset: offset + num, ::sub, ::sub]), dtype=torch.float)
+        self.mesh = torch2dgrid(self.S, self.S)
+        self.pde_a = torch.tensor(np.asarray(a[offset: offset + num, ::pde_sub, ::pde_sub]), dtype=torch.float)
+        self.pde_mesh = torch2dgrid(self.pde_S, self.pde_S)
+
+    def __len__(self):
+        return self.a.shape[0]
+
+    def __getitem__(self, item):
+        data_ic = torch.cat([self.a[item].unsqueeze(2), self.mesh], dim=2)
+        pde_ic = torch.cat([self.pde_a[item].unsqueeze(2), self.pde_mesh], dim=2)
+        return data_ic, self.u[item], pde_ic

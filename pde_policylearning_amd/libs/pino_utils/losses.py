@@ -1,8 +1,9 @@
 """PINO residual losses with the reference surface (libs/pino_utils/losses.py): the FDM-in-time / spectral-in-space
 Navier-Stokes vorticity residual and the two relative-L2 terms the fine-tuning loop (train_pino.py:98-101) combines
-(:68-104, 246-262, 288-291), the Burgers residual and its two mean-square terms (:200-243: FDM_Burgers, PINO_loss) and the
-relative L2 data loss (:151-197: LpLoss).  The arithmetic runs in the HIP engine (functional.pino_loss, burgers_loss,
-burgers_residual, lp_loss_rel); there is no CPU path."""
+(:68-104, 246-262, 288-291), the Burgers residual and its two mean-square terms (:200-243: FDM_Burgers, PINO_loss), the Darcy
+residual and its relative-L2 term (:6-65: FDM_Darcy, darcy_loss) and the relative L2 data loss (:151-197: LpLoss).  The
+arithmetic runs in the HIP engine (functional.pino_loss, burgers_loss, burgers_residual, darcy_loss, darcy_residual,
+lp_loss_rel); there is no CPU path."""
 import math
 
 import torch
@@ -61,3 +62,19 @@ def FDM_Burgers(u, v, D=1):
 def PINO_loss(u, u0, v):
     """(loss_u, loss_f): mean squares of u[:, 0] - u0 and of the Burgers residual (losses.py:223-243)."""
     return F.burgers_loss(u.reshape(u.size(0), u.size(1), u.size(2)), u0, float(v))
+
+
+def FDM_Darcy(u, a, D=1):
+    """Du (B, S - 4, S - 4) = -div(a grad u) of u, a (B, S, S[, 1]) by two central differences on the unit square
+    (losses.py:6-36).  Not differentiable; darcy_loss is what training differentiates."""
+    if D != 1:
+        raise NotImplementedError(f"FDM_Darcy: D={D} (the engine's kernel is built for the unit domain, D=1)")
+    B, S = u.size(0), u.size(1)
+    return F.darcy_residual(u.reshape(B, S, S), a.reshape(B, S, S))
+
+
+def darcy_loss(u, a):
+    """LpLoss(size_average=True).rel of the Darcy residual against ones (losses.py:39-65).  functional.darcy_loss also
+    takes the mollifier and the data target, which the training loop passes for one fused call."""
+    B, S = u.size(0), u.size(1)
+    return F.darcy_loss(u.reshape(B, S, S), a.reshape(B, S, S))

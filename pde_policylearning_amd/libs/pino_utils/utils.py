@@ -1,9 +1,17 @@
 """libs/pino_utils/utils.py surface used by the PINO fine-tuning loop: the space-time input grid, checkpointing, small helpers
-(get_grid3d :107-115, save_checkpoint :156-174, save_ckpt :178-194, count_params, dict2str :197-201)."""
+(torch2dgrid :97-104, get_grid3d :107-115, save_checkpoint :156-174, save_ckpt :178-194, count_params, dict2str :197-201)."""
 import os
 
 import numpy as np
 import torch
+
+
+def torch2dgrid(num_x, num_y, bot=(0, 0), top=(1, 1)):
+    """(num_x, num_y, 2) float32 mesh of the box bot .. top, end points included, first index x."""
+    xs = torch.linspace(bot[0], top[0], steps=num_x)
+    ys = torch.linspace(bot[1], top[1], steps=num_y)
+    xx, yy = torch.meshgrid(xs, ys, indexing='ij')
+    return torch.stack([xx, yy], dim=2)
 
 
 def get_grid3d(S, T, time_scale=1.0, device='cpu'):
