@@ -1,67 +1,143 @@
-"""ctypes binding of the fnoengine C ABI (include/fnoengine.h).
+"""ctypes binding of the fnoengine C ABI, derived from include/fnoengine.h when this module is imported: constants, structs,
+the symbol list and every function's types are read from the header (read_header), never written out a second time.
 
 The shared library is built in-tree by `python -m pde_policylearning_amd.build`
 (or __graft_entry__.build()) with hipcc for gfx950.  There is NO fallback: if
 the library is missing or a call fails, a RuntimeError is raised.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FNO_LIB_PATH") or os.path.join(_HERE, "libfnoengine.so")      # (FNO_LIB_PATH: experiment builds of tools/)
 
-FNO_MAX_LAYERS = 16
-NORM_CODES = {"backward": 0, None: 0, "forward": 1, "ortho": 2}
+Header = collections.namedtuple("Header", "consts structs protos")
 
-c_float_p = C.POINTER(C.c_float)
-
-
-class FnoSpecDesc(C.Structure):
-    _fields_ = [("ndim", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
-                ("dims", C.c_int * 3), ("modes", C.c_int * 3),
-                ("weight_last_extent", C.c_int), ("norm", C.c_int), ("input_gelu", C.c_int),
-                ("weight_planes", C.c_int)]
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double,
+            "long long": C.c_longlong, "unsigned long long": C.c_ulonglong}
 
 
-class FnoModelDesc(C.Structure):
-    _fields_ = [("ndim", C.c_int), ("Cin", C.c_int), ("C", C.c_int), ("Cout", C.c_int),
-                ("hidden_proj", C.c_int), ("n_layers", C.c_int),
-                ("dims", C.c_int * 3), ("modes", C.c_int * 3),
-                ("norm", C.c_int), ("gelu_mask", C.c_uint), ("weight_planes", C.c_int)]
+def _ctype(text, where, structs, opaque, role):
+    """The ctypes type of the C type `text` as a return type, argument or struct field (role "ret" / "arg" / "field").
+    A type outside the rules below raises, naming `where`: nothing defaults to a pointer or an int."""
+    words = re.findall(r"[A-Za-z_]\w*", text)
+    base, stars = " ".join(w for w in words if w != "const"), text.count("*")
+    bad = RuntimeError(f"fnoengine header: {where}: unknown type '{' '.join(text.split())}'")
+    if re.sub(r"[\w\s*]", "", text):
+        raise bad
+    if stars == 0:
+        if base in _SCALARS:
+            return _SCALARS[base]
+        if base == "void" and role == "ret":
+            return None
+        raise bad
+    if stars > 2 or not (base in _SCALARS or base in ("void", "char") or base in structs or base in opaque):
+        raise bad
+    if role == "ret":
+        if words == ["const", "char"] and stars == 1:
+            return C.c_char_p
+        raise bad
+    if role == "field":
+        return C.c_void_p
+    if stars == 1:
+        return C.POINTER(structs[base]) if base in structs else C.c_void_p
+    if base in opaque or re.search(r"\*\s*const\s*\*", text):       # plan out-parameters; tables of device pointers
+        return C.POINTER(C.c_void_p)
+    return C.c_void_p
 
 
-class FnoBlockTail(C.Structure):        # include/fnoengine.h: one-layer block stacks with a tail (RNO regressor layers)
-    _fields_ = [("relu_out", C.c_int), ("drop_p", C.c_float), ("drop_seed", C.c_void_p), ("y", C.c_void_p)]
+def read_header(text, consts=None, structs=None):
+    """Header(consts, structs, protos) of a C header in the style of include/fnoengine.h: every `#define NAME integer` and
+    enumerator of an anonymous enum; every `typedef struct Name {...} Name;` as a ctypes.Structure (pointer fields as
+    c_void_p); every prototype as name -> (restype, argtypes), in header order.  `consts` / `structs` carry the names of a
+    header read before.  Whatever the reader does not recognise raises, naming the function and parameter or the field."""
+    consts, structs, opaque, protos = dict(consts or {}), dict(structs or {}), set(), {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).replace("\\\n", " ")
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M):
+        consts[name] = int(value)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text, n_extern = re.subn(r'extern\s+"C"\s*\{', " ", text)
+
+    def enum(m):
+        value = -1
+        for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+            em = re.fullmatch(r"(\w+)(?:\s*=\s*(-?\d+))?", item)
+            if not em:
+                raise RuntimeError(f"fnoengine header: cannot read the enumerator '{item}'")
+            value = int(em.group(2)) if em.group(2) else value + 1
+            consts[em.group(1)] = value
+        return " "
+
+    def struct(m):
+        body, sname = m.groups()
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            fm = re.fullmatch(r"(.*?)(\w+)((?:\s*\[\s*\w+\s*\])*)", first, re.S)
+            rest = [re.fullmatch(r"()(\w+)((?:\s*\[\s*\w+\s*\])*)", d) for d in more]
+            if not fm or not all(rest) or (more and "*" in fm.group(1)):
+                raise RuntimeError(f"fnoengine header: {sname}: cannot place the field '{' '.join(decl.split())}'")
+            ctype = _ctype(fm.group(1), f"{sname}.{fm.group(2)}", structs, opaque, "field")
+            for dm in [fm] + rest:
+                t = ctype
+                for dim in reversed(re.findall(r"\w+", dm.group(3))):
+                    if not (dim.isdigit() or dim in consts):
+                        raise RuntimeError(f"fnoengine header: {sname}.{dm.group(2)}: unknown extent '{dim}'")
+                    t = t * (int(dim) if dim.isdigit() else consts[dim])
+                fields.append((dm.group(2), t))
+        structs[sname] = type(sname, (C.Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"\benum\s*\{([^{}]*)\}\s*;", enum, text)
+    text = re.sub(r"\btypedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    *statements, tail = text.split(";")
+
+    def unreadable(stmt):
+        m = re.search(r"(\w+)\s*\(", stmt)
+        return RuntimeError(f"fnoengine header: cannot read the declaration of '{m.group(1) if m else ' '.join(stmt.split())[:60]}'")
+
+    for stmt in statements:
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        om = re.fullmatch(r"typedef struct (\w+) (\w+)", stmt)
+        if om:
+            opaque.add(om.group(2))
+            continue
+        pm = re.fullmatch(r"([^()]*?)(\w+) ?\(([^()]*)\)", stmt)
+        if not pm or pm.group(2) in protos:
+            raise unreadable(stmt)
+        ret, name, params = pm.groups()
+        args = []
+        for prm in [] if params.strip() == "void" else params.split(","):
+            am = re.fullmatch(r"(.*?)(\w+)", prm.strip())
+            if not am:
+                raise RuntimeError(f"fnoengine header: {name}: cannot read the parameter '{prm.strip()}'")
+            args.append(_ctype(am.group(1), f"{name}({am.group(2)})", structs, opaque, "arg"))
+        protos[name] = (_ctype(ret, name, structs, opaque, "ret"), args)
+    if tail.split() != ["}"] * n_extern:          # what follows the last `;` is the closing brace of extern "C" and nothing else
+        raise unreadable(tail)
+    return Header(consts, structs, protos)
 
 
-class FnoModelParams(C.Structure):
-    _fields_ = [("lift_w", C.c_void_p), ("lift_b", C.c_void_p),
-                ("skip_w", C.c_void_p * FNO_MAX_LAYERS),
-                ("spec_w", (C.c_void_p * 4) * FNO_MAX_LAYERS),
-                ("spec_bias", C.c_void_p),
-                ("proj_w1", C.c_void_p), ("proj_b1", C.c_void_p),
-                ("proj_w2", C.c_void_p), ("proj_b2", C.c_void_p)]
+def _header(path, *before):
+    if not os.path.exists(path):
+        raise RuntimeError(f"fnoengine: {path} not found: the binding is derived from it (there is no second copy of the ABI).")
+    with open(path) as f:
+        return read_header(f.read(), *before)
 
 
-FnoModelGrads = FnoModelParams   # same layout, mutable pointers
-
-
-class FnoChanflowGrid(C.Structure):
-    _fields_ = [("Nx", C.c_int), ("Ny", C.c_int), ("Nz", C.c_int), ("dx", C.c_double), ("dz", C.c_double), ("nu", C.c_double)]
-
-
-class FnoNs2dGrid(C.Structure):
-    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nit", C.c_int), ("dx", C.c_double), ("dy", C.c_double), ("dt", C.c_double),
-                ("rho", C.c_double)]
-
-
-FNO_CTRL_STATS_MAX = 8
-
-
-class FnoCtrlStats(C.Structure):         # include/fnoengine.h: the pointer table of fno_ctrl_stats_update
-    _fields_ = [("x", C.c_void_p * FNO_CTRL_STATS_MAX), ("mean", C.c_void_p * FNO_CTRL_STATS_MAX),
-                ("m2", C.c_void_p * FNO_CTRL_STATS_MAX), ("n", C.c_size_t * FNO_CTRL_STATS_MAX)]
-
+# The ABI is stated once, in the header (the compiler holds csrc/fno_abi.hip to it); everything below is read from it.
+ABI = _header(os.path.join(os.path.dirname(_HERE), "include", "fnoengine.h"))
+DEBUG_ABI = _header(os.path.join(_HERE, "csrc", "fno_debug.h"), ABI.consts, ABI.structs)     # not public: bound where defined
+globals().update(ABI.structs)          # FnoSpecDesc, FnoModelDesc, FnoModelParams, FnoModelGrads, FnoBlockTail, ...
+EXPORTED_SYMBOLS = list(ABI.protos)
+FNO_MAX_LAYERS = ABI.consts["FNO_MAX_LAYERS"]
+FNO_CTRL_STATS_MAX = ABI.consts["FNO_CTRL_STATS_MAX"]
+NORM_CODES = {"backward": ABI.consts["FNO_NORM_BACKWARD"], None: ABI.consts["FNO_NORM_BACKWARD"],
+              "forward": ABI.consts["FNO_NORM_FORWARD"], "ortho": ABI.consts["FNO_NORM_ORTHO"]}
 
 _lib = None
 
@@ -81,153 +157,12 @@ def lib():
     # every later call fails with "no HIP device" (seen with build() and smoke() in one process).
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    vp, ci, sz = C.c_void_p, C.c_int, C.c_size_t
-    L.fno_version.restype = ci
-    L.fno_last_error.restype = C.c_char_p
-    L.fno_set_gemm_mode.argtypes = [ci]
-    L.fno_set_gemm_mode.restype = None
-    L.fno_get_gemm_mode.restype = ci
-    L.fno_set_mode_gemm.argtypes = [ci]
-    L.fno_set_mode_gemm.restype = None
-    L.fno_get_mode_gemm.restype = ci
-    L.fno_set_fused_mid.argtypes = [ci]
-    L.fno_set_fused_mid.restype = None
-    L.fno_get_fused_mid.restype = ci
-    L.fno_spec_plan_create.argtypes = [C.POINTER(FnoSpecDesc), C.POINTER(vp)]
-    L.fno_spec_plan_destroy.argtypes = [vp]
-    L.fno_spec_plan_destroy.restype = None
-    L.fno_spec_workspace_bytes.argtypes = [vp, ci]
-    L.fno_spec_workspace_bytes.restype = sz
-    L.fno_spec_xhat_bytes.argtypes = [vp, ci]
-    L.fno_spec_xhat_bytes.restype = sz
-    L.fno_spec_forward.argtypes = [vp, ci, vp, C.POINTER(vp), vp, vp, vp, vp, sz, vp]
-    L.fno_spec_backward.argtypes = [vp, ci, vp, vp, C.POINTER(vp), vp, C.POINTER(vp), vp, vp, sz, vp]
-    L.fno_model_plan_create.argtypes = [C.POINTER(FnoModelDesc), C.POINTER(vp)]
-    L.fno_model_plan_destroy.argtypes = [vp]
-    L.fno_model_plan_destroy.restype = None
-    L.fno_model_workspace_bytes.argtypes = [vp, ci]
-    L.fno_model_workspace_bytes.restype = sz
-    L.fno_model_saved_bytes.argtypes = [vp, ci]
-    L.fno_model_saved_bytes.restype = sz
-    L.fno_model_forward.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp, vp, sz, vp]
-    L.fno_model_backward.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
-                                     C.POINTER(FnoModelGrads), vp, sz, vp]
-    L.fno_fanout_saved_bytes.argtypes = [vp, ci, ci]
-    L.fno_fanout_saved_bytes.restype = sz
-    L.fno_fanout_workspace_bytes.argtypes = [vp, ci, ci]
-    L.fno_fanout_workspace_bytes.restype = sz
-    L.fno_fanout_forward.argtypes = [vp, ci, ci, C.POINTER(FnoModelParams), C.POINTER(vp), vp, C.POINTER(vp), vp, vp, sz, vp]
-    L.fno_fanout_backward.argtypes = [vp, ci, ci, C.POINTER(FnoModelParams), vp, C.POINTER(vp), vp,
-                                      C.POINTER(FnoModelGrads), C.POINTER(vp), vp, vp, sz, vp]
-    fl = C.c_float
-    L.fno_lploss_workspace_bytes.argtypes = [ci]
-    L.fno_lploss_workspace_bytes.restype = sz
-    L.fno_lploss_rel_forward.argtypes = [ci, sz, vp, vp, vp, vp, ci, fl, ci, vp, vp, sz, vp]
-    L.fno_lploss_rel_backward.argtypes = [ci, sz, vp, vp, vp, ci, fl, vp, vp, vp, sz, vp]
-    db = C.c_double       # Adam hyperparameters cross the ABI as the doubles torch.optim.Adam holds
-    L.fno_adam_step.argtypes = [sz, vp, vp, vp, vp, db, db, db, db, db, ci, vp]
-    L.fno_adam_step_dev.argtypes = [sz, vp, vp, vp, vp, db, db, db, db, db, vp, vp, vp]
-    L.fno_adam_scalars.argtypes = [db, db, db, ci, vp]
-    L.fno_adam_scalars.restype = None
-    L.fno_adam_prep_dev.argtypes = [vp, vp, db, db, db, vp]
-    L.fno_adam_step_range.argtypes = [sz, vp, vp, vp, vp, db, db, db, db, db, ci, vp, vp]
-    L.fno_adam_step_live.argtypes = [sz, ci, ci, vp, vp, vp, vp, db, db, db, db, db, ci, vp, vp]
-    L.fno_adam_replay_prep.argtypes = [vp, ci, ci, db, db, db, vp]
-    L.fno_adam_replay_dead.argtypes = [sz, ci, ci, vp, vp, vp, ci, vp, ci, db, db, db, db, vp]
-    L.fno_pointwise_workspace_bytes.argtypes = [ci]
-    L.fno_pointwise_workspace_bytes.restype = sz
-    L.fno_pointwise_forward.argtypes = [ci, ci, sz, vp, vp, vp, vp, ci, vp, vp]
-    L.fno_pointwise_backward.argtypes = [ci, ci, sz, vp, vp, vp, vp, ci, vp, vp, vp, vp, sz, vp]
-    L.fno_debug_pino_twopass.argtypes = [ci]
-    L.fno_debug_pino_twopass.restype = None
-    up = C.POINTER(C.c_uint)
-    L.fno_debug_launch_log.argtypes = [ci]
-    L.fno_debug_launch_log.restype = None
-    L.fno_debug_launch_count.restype = ci
-    L.fno_debug_launch_get.argtypes = [ci, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(ci), C.POINTER(ci), up, up,
-                                       C.POINTER(sz)]
-    L.fno_projection_workspace_bytes.argtypes = [ci, ci]
-    L.fno_projection_workspace_bytes.restype = sz
-    L.fno_projection_forward.argtypes = [ci, ci, ci, ci, sz] + [vp] * 7
-    L.fno_projection_backward.argtypes = [ci, ci, ci, ci, sz] + [vp] * 11 + [sz, vp]
-    L.fno_projection_forward_act.argtypes = [ci, ci, ci, ci, sz] + [vp] * 5 + [ci, vp, vp]
-    L.fno_projection_backward_act.argtypes = [ci, ci, ci, ci, sz] + [vp] * 5 + [ci] + [vp] * 6 + [sz, vp]
-    L.fno_channel_mlp_workspace_bytes.argtypes = [ci, ci, ci, sz]
-    L.fno_channel_mlp_workspace_bytes.restype = sz
-    L.fno_channel_mlp_forward.argtypes = [ci, ci, ci, sz] + [vp] * 7 + [ci, vp, vp]
-    L.fno_channel_mlp_backward.argtypes = [ci, ci, ci, sz] + [vp] * 7 + [ci] + [vp] * 9 + [sz, vp]
-    L.fno_lifting_workspace_bytes.argtypes = [ci]
-    L.fno_lifting_workspace_bytes.restype = sz
-    L.fno_lifting_forward.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp, vp]
-    L.fno_lifting_backward.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_lifting_backward_dx.argtypes = [ci, ci, ci, sz, vp, vp, vp, vp]
-    L.fno_rno_gate_partials.restype = ci
-    L.fno_rno_reset_gate_forward.argtypes = [sz] + [vp] * 7
-    L.fno_rno_reset_gate_backward.argtypes = [sz] + [vp] * 7
-    L.fno_rno_output_gate_forward.argtypes = [sz] + [vp] * 15
-    L.fno_rno_output_gate_backward.argtypes = [sz] + [vp] * 11
-    gp, dp = C.POINTER(FnoChanflowGrid), C.POINTER(C.c_double)
-    L.fno_chanflow_pack_metrics.argtypes = [ci, dp, dp, dp, dp]
-    L.fno_chanflow_rhs.argtypes = [gp, ci, ci, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp]
-    L.fno_chanflow_pde_loss_workspace_bytes.argtypes = [gp, ci]
-    L.fno_chanflow_pde_loss_workspace_bytes.restype = sz
-    L.fno_chanflow_pde_loss_forward.argtypes = [gp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_chanflow_pde_loss_backward.argtypes = [gp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_chanflow_poisson_table_bytes.argtypes = [gp]
-    L.fno_chanflow_poisson_table_bytes.restype = sz
-    L.fno_chanflow_poisson_pack.argtypes = [gp, dp, dp, dp, dp, sz]
-    L.fno_chanflow_step_workspace_bytes.argtypes = [gp, ci]
-    L.fno_chanflow_step_workspace_bytes.restype = sz
-    L.fno_chanflow_project.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, sz, vp]
-    L.fno_chanflow_wall_pressure.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_chanflow_rk3_step.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp, sz, vp]
-    L.fno_chanflow_diagnostics.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp]
-    L.fno_ctrl_encode.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, sz, vp]
-    L.fno_ctrl_decode.argtypes = [ci, sz, vp, sz, vp, vp, C.c_double, C.c_double, C.c_double, ci, vp, vp, vp]
-    L.fno_chanflow_diagnostics2_workspace_bytes.argtypes = [gp, ci]
-    L.fno_chanflow_diagnostics2_workspace_bytes.restype = sz
-    L.fno_chanflow_diagnostics2.argtypes = [gp, ci, ci, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp]
-    L.fno_ctrl_stats_update.argtypes = [C.POINTER(FnoCtrlStats), ci, C.c_longlong, vp]
-    L.fno_ctrl_action_workspace_bytes.argtypes = [ci, ci, sz]
-    L.fno_ctrl_action_workspace_bytes.restype = sz
-    L.fno_ctrl_action_begin.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, vp, sz, vp]
-    L.fno_ctrl_action_objective.argtypes = [ci, ci, sz, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
-    L.fno_ctrl_action_update.argtypes = [ci, sz, vp, vp, vp, vp] + [C.c_double] * 6 + [ci, vp, vp, vp, vp, sz, vp]
-    L.fno_ctrl_action_finish.argtypes = [ci, sz, vp, vp, vp]
-    L.fno_ctrl_policy_begin.argtypes = [ci, sz, vp, vp, vp, vp, vp]
-    L.fno_ctrl_policy_compose.argtypes = [ci, sz, vp, vp, vp, vp, vp]
-    L.fno_ctrl_policy_grad.argtypes = [ci, sz, vp, vp, vp, C.c_double, vp, vp]
-    ng = C.POINTER(FnoNs2dGrid)
-    L.fno_ns2d_solve.argtypes = [ng, ci] + [vp] * 9 + [ci, C.c_double, ci, ci, vp, vp]
-    L.fno_ns2d_fixed_mass.argtypes = [ng, ci] + [vp] * 10 + [C.c_double, ci, ci, C.c_double, vp, vp]
-    L.fno_ns2d_diagnostics.argtypes = [ng, ci] + [vp] * 8
-    L.fno_pino_loss_workspace_bytes.argtypes = [ci, ci, ci]
-    L.fno_pino_loss_workspace_bytes.restype = sz
-    L.fno_pino_loss_forward.argtypes = [ci, ci, ci, vp, vp, vp, vp, fl, vp, vp, vp, sz, vp]
-    L.fno_pino_loss_backward.argtypes = [ci, ci, ci, vp, vp, vp, vp, fl, vp, vp, vp, vp, sz, vp]
-    L.fno_burgers_loss_workspace_bytes.argtypes = [ci, ci, ci]
-    L.fno_burgers_loss_workspace_bytes.restype = sz
-    L.fno_burgers_loss_forward.argtypes = [ci, ci, ci, vp, vp, fl, vp, vp, vp, sz, vp]
-    L.fno_burgers_loss_backward.argtypes = [ci, ci, ci, vp, vp, fl, vp, vp, vp, vp, sz, vp]
-    L.fno_darcy_loss_workspace_bytes.argtypes = [ci, ci]
-    L.fno_darcy_loss_workspace_bytes.restype = sz
-    L.fno_darcy_loss_forward.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_darcy_loss_backward.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.fno_model_backward_dx.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
-                                        C.POINTER(FnoModelGrads), vp, vp, sz, vp]
-    L.fno_model_backward_part.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
-                                          C.POINTER(FnoModelGrads), vp, vp, sz, vp, ci, ci]
-    L.fno_model_forward_tail.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp, vp, sz, vp, C.POINTER(FnoBlockTail)]
-    L.fno_model_backward_tail.argtypes = [vp, ci, C.POINTER(FnoModelParams), vp, vp, vp,
-                                          C.POINTER(FnoModelGrads), vp, vp, sz, vp, C.POINTER(FnoBlockTail)]
-    L.fno_dropout_scale.argtypes = [sz, C.c_float, vp, vp, vp]
-    L.fno_profile_enable.argtypes = [ci]
-    L.fno_profile_enable.restype = None
-    L.fno_profile_reset.restype = None
-    L.fno_profile_count.restype = ci
-    L.fno_profile_get.argtypes = [ci, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(ci)]
-    L.fno_profile_get_terms.argtypes = [ci]
-    L.fno_profile_get_terms.restype = ci
+    missing = [n for n in ABI.protos if not hasattr(L, n)]
+    if missing:
+        raise RuntimeError(f"fnoengine: {LIB_PATH} does not define {missing} (include/fnoengine.h declares them): rebuild it.")
+    for name, (restype, argtypes) in list(ABI.protos.items()) + [p for p in DEBUG_ABI.protos.items() if hasattr(L, p[0])]:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -236,40 +171,6 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().fno_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"fnoengine {what} failed (code {rc}): {msg}")
-
-
-EXPORTED_SYMBOLS = [
-    "fno_version", "fno_last_error", "fno_set_gemm_mode", "fno_get_gemm_mode", "fno_set_mode_gemm", "fno_get_mode_gemm",
-    "fno_set_fused_mid", "fno_get_fused_mid",
-    "fno_spec_plan_create", "fno_spec_plan_destroy", "fno_spec_workspace_bytes", "fno_spec_xhat_bytes",
-    "fno_spec_forward", "fno_spec_backward",
-    "fno_model_plan_create", "fno_model_plan_destroy", "fno_model_workspace_bytes", "fno_model_saved_bytes",
-    "fno_model_forward", "fno_model_backward", "fno_model_backward_dx", "fno_model_backward_part",
-    "fno_model_forward_tail", "fno_model_backward_tail", "fno_dropout_scale",
-    "fno_fanout_saved_bytes", "fno_fanout_workspace_bytes", "fno_fanout_forward", "fno_fanout_backward",
-    "fno_lploss_workspace_bytes", "fno_lploss_rel_forward", "fno_lploss_rel_backward", "fno_adam_step", "fno_adam_step_dev",
-    "fno_adam_scalars", "fno_adam_prep_dev", "fno_adam_step_range", "fno_adam_step_live", "fno_adam_replay_prep",
-    "fno_adam_replay_dead",
-    "fno_pointwise_workspace_bytes", "fno_pointwise_forward", "fno_pointwise_backward",
-    "fno_projection_workspace_bytes", "fno_projection_forward", "fno_projection_backward",
-    "fno_projection_forward_act", "fno_projection_backward_act",
-    "fno_channel_mlp_workspace_bytes", "fno_channel_mlp_forward", "fno_channel_mlp_backward",
-    "fno_lifting_workspace_bytes", "fno_lifting_forward", "fno_lifting_backward", "fno_lifting_backward_dx",
-    "fno_rno_gate_partials", "fno_rno_reset_gate_forward", "fno_rno_reset_gate_backward",
-    "fno_rno_output_gate_forward", "fno_rno_output_gate_backward",
-    "fno_pino_loss_workspace_bytes", "fno_pino_loss_forward", "fno_pino_loss_backward",
-    "fno_burgers_loss_workspace_bytes", "fno_burgers_loss_forward", "fno_burgers_loss_backward",
-    "fno_darcy_loss_workspace_bytes", "fno_darcy_loss_forward", "fno_darcy_loss_backward",
-    "fno_chanflow_pack_metrics", "fno_chanflow_rhs", "fno_chanflow_pde_loss_workspace_bytes",
-    "fno_chanflow_pde_loss_forward", "fno_chanflow_pde_loss_backward",
-    "fno_chanflow_poisson_table_bytes", "fno_chanflow_poisson_pack", "fno_chanflow_step_workspace_bytes",
-    "fno_chanflow_project", "fno_chanflow_wall_pressure", "fno_chanflow_rk3_step", "fno_chanflow_diagnostics",
-    "fno_ctrl_encode", "fno_ctrl_decode", "fno_chanflow_diagnostics2_workspace_bytes", "fno_chanflow_diagnostics2",
-    "fno_ctrl_stats_update", "fno_ctrl_action_workspace_bytes", "fno_ctrl_action_begin", "fno_ctrl_action_objective",
-    "fno_ctrl_action_update", "fno_ctrl_action_finish", "fno_ctrl_policy_begin", "fno_ctrl_policy_compose",
-    "fno_ctrl_policy_grad", "fno_ns2d_solve", "fno_ns2d_fixed_mass", "fno_ns2d_diagnostics",
-    "fno_profile_enable", "fno_profile_count", "fno_profile_get", "fno_profile_get_terms", "fno_profile_reset",
-]
 
 
 def profile_summary(with_terms=False):

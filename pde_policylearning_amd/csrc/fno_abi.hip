@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/fnoengine.h"
+#include "fno_debug.h"
 #include "k_block_bwd.h"
 #include "k_block_bwd2.h"
 #include "k_chanflow.h"
@@ -93,7 +94,7 @@ static std::vector<ProfAgg> g_agg;
 // above cannot tell ("k_rowidft_chan" names three kernels, "k_mode_gemm" five) and stay as they are: bench.py prices kernels
 // by them.  A dispatch site states its variant in the launching statement itself - LV(tag, rb, ntiles), launch(...) - and
 // launch() reads and clears it like g_terms_next.  Off by default: nothing is recorded and the vector holds no storage.
-// Not part of include/fnoengine.h.
+// Not part of include/fnoengine.h: the fno_debug_* entry points are declared in fno_debug.h.
 // --------------------------------------------------------------------------
 struct LaunchTag { const char* variant; int rb, ntiles; };      // rb: rows (contractions: batch rows / input channels) per workgroup; 0 = the site has none
 struct LaunchRec { const char* name; LaunchTag tag; unsigned grid[3], block[3]; size_t lds; };

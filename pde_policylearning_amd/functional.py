@@ -150,10 +150,11 @@ class _Cfg(typing.NamedTuple):
     tail: typing.Any = None         # fno_block_tail: (relu_out, drop_p, seed tensor or None)
 
 
-def _fill_params(ncorner, skip_ws, spec_ws, spec_bias=None, ends=None):
-    """FnoModelParams (= FnoModelGrads) over checked tensors: per layer / fan-out member one skip weight and `ncorner` corner
-    weights, the bias rows, and for the whole model `ends` = (lift_w, lift_b, proj_w1, proj_b1, proj_w2, proj_b2)."""
-    s = _lib.FnoModelParams()
+def _fill_params(ncorner, skip_ws, spec_ws, spec_bias=None, ends=None, struct=_lib.FnoModelParams):
+    """FnoModelParams (`struct=_lib.FnoModelGrads`: the gradients, same fields) over checked tensors: per layer / fan-out member
+    one skip weight and `ncorner` corner weights, the bias rows, and for the whole model `ends` = (lift_w, lift_b, proj_w1,
+    proj_b1, proj_w2, proj_b2)."""
+    s = struct()
     for l, t in enumerate(skip_ws):
         s.skip_w[l] = t.data_ptr()
         for c in range(ncorner):
@@ -468,7 +469,7 @@ class _FNOModelFn(torch.autograd.Function):
             g_skip = [torch.empty_like(t) for t in skip_ws]
             g_spec = [torch.empty_like(t) for t in spec_ws]
             g_sb = torch.empty_like(sb) if sb is not None else None
-        grd = _fill_params(nc, g_skip, g_spec, g_sb, g)
+        grd = _fill_params(nc, g_skip, g_spec, g_sb, g, _lib.FnoModelGrads)
         nws = L.fno_model_workspace_bytes(ctx.plan, ctx.B)
         ws = _bytes(nws, dy.device)
         ov = ctx.overlap
@@ -703,7 +704,7 @@ class _FNOBlocksFn(torch.autograd.Function):
         g_skip = [torch.empty_like(t) for t in skip_ws]
         g_spec = ctx.direct if ctx.direct is not None else _fresh_grads(spec_ws, ctx.planes)   # direct: the weights' own .grad storage
         g_sb = torch.empty_like(sb) if sb is not None else None
-        prm, grd = _fill_params(nc, skip_ws, spec_ws, sb), _fill_params(nc, g_skip, g_spec, g_sb)
+        prm, grd = _fill_params(nc, skip_ws, spec_ws, sb), _fill_params(nc, g_skip, g_spec, g_sb, struct=_lib.FnoModelGrads)
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         nws = L.fno_model_workspace_bytes(ctx.plan, ctx.B)
         ws = _bytes(nws, dy.device)
@@ -830,7 +831,7 @@ class _FourierFanoutFn(torch.autograd.Function):
         g_skip = [torch.empty_like(t) for t in skip_ws]
         g_spec = ctx.direct if ctx.direct is not None else _fresh_grads(spec_ws, ctx.planes)     # direct: the weights' own .grad storage
         g_bias = [torch.empty(x.shape[1], dtype=torch.float32, device=x.device) for _ in range(n)]
-        prm, grd = _fill_params(nc, skip_ws, spec_ws), _fill_params(nc, g_skip, g_spec)
+        prm, grd = _fill_params(nc, skip_ws, spec_ws), _fill_params(nc, g_skip, g_spec, struct=_lib.FnoModelGrads)
         dx = torch.empty_like(x)
         nws = L.fno_fanout_workspace_bytes(ctx.plan, ctx.B, n)
         ws = _bytes(nws, x.device)
@@ -2174,7 +2175,7 @@ def spectral_pointwise_layer(u, spec_weights, modes, norm, w, bias, input_gelu=F
 # projection head  y = W2 gelu(W1 x + b1) + b2  on (B, C, ...) tensors
 # ----------------------------------------------------------------------------
 PROJ_MAXCO = 4        # k_projection.h
-_ACT_CODES = {"gelu": 0, "relu": 1}      # FNO_ACT_* (include/fnoengine.h)
+_ACT_CODES = {"gelu": _lib.ABI.consts["FNO_ACT_GELU"], "relu": _lib.ABI.consts["FNO_ACT_RELU"]}
 
 
 def projection_supported(x, hidden, cout, act="gelu"):

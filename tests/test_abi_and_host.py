@@ -49,12 +49,196 @@ def test_launch_log_is_off_by_default_and_outside_the_public_header(lib):
     assert log.records == [] and lib.fno_debug_launch_count() == 0
 
 
-def test_struct_layout_matches_header(lib):
+def _strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _toolchain(tool):
+    """a program of the ROCm toolchain's LLVM, found from the compiler the build uses; its absence is a failure, not a skip"""
+    from pde_policylearning_amd import build
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc_path())))
+    path = os.path.join(rocm, "lib", "llvm", "bin", tool)
+    assert os.path.exists(path), f"{tool} not found beside {build.hipcc_path()} ({path})"
+    return path
+
+
+_SYNTHETIC_HEADER = """
+/* a comment that names fno_fake(int) and has (parentheses); and a semicolon */
+#ifndef SYNTHETIC_H
+#define SYNTHETIC_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define FNO_MAX_LAYERS 16
+#define FNO_MINUS -3
+enum { FNO_A = 0, FNO_B = -2, FNO_C };
+// int fno_also_fake(short x);
+typedef struct FnoThing {
+  int a, b;            /* two on one line */
+  int d[3];
+  const float* w[FNO_MAX_LAYERS][4];
+  double e;
+  unsigned m;
+} FnoThing;
+typedef struct FnoSpecPlan FnoSpecPlan;
+int fno_three(const FnoSpecPlan* plan,
+              int batch, const float* const* wc,
+              float* const* y, FnoSpecPlan** out);
+int fno_scale(size_t n, float p, const unsigned* seed /*device, 2 words*/, float* out /*device, n*/, void* stream);
+size_t fno_bytes(const FnoThing* t, long long count, unsigned long long* host, double x, unsigned m, const char** name);
+void fno_reset(void);
+const char* fno_text(void);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_on_synthetic_text():
+    """_lib.read_header on small header strings: a prototype over three lines, comments that look like code, inline comments
+    between parameters, the pointer-to-pointer forms, the three kinds of return type, a struct with `int a, b;`, an array
+    and a two-dimensional array of pointers sized by a #define; and what it must refuse, by name."""
     from pde_policylearning_amd import _lib
-    # FnoSpecDesc: 3 + 3 + 3 + 4 ints ; FnoModelDesc: 6 + 3 + 3 + 3 ints
-    assert ctypes.sizeof(_lib.FnoSpecDesc) == 13 * 4
-    assert ctypes.sizeof(_lib.FnoModelDesc) == 15 * 4
-    assert ctypes.sizeof(_lib.FnoModelParams) == 8 * (2 + 16 + 64 + 1 + 4)
+    c = ctypes
+    h = _lib.read_header(_SYNTHETIC_HEADER)
+    assert h.consts == {"FNO_MAX_LAYERS": 16, "FNO_MINUS": -3, "FNO_A": 0, "FNO_B": -2, "FNO_C": -1}
+    assert list(h.protos) == ["fno_three", "fno_scale", "fno_bytes", "fno_reset", "fno_text"]
+    vpp = c.POINTER(c.c_void_p)
+    T = h.structs["FnoThing"]
+    assert list(h.structs) == ["FnoThing"] and issubclass(T, c.Structure)
+    assert h.protos["fno_three"] == (c.c_int, [c.c_void_p, c.c_int, vpp, vpp, vpp])
+    assert h.protos["fno_scale"] == (c.c_int, [c.c_size_t, c.c_float, c.c_void_p, c.c_void_p, c.c_void_p])
+    assert h.protos["fno_bytes"] == (c.c_size_t, [c.POINTER(T), c.c_longlong, c.c_void_p, c.c_double, c.c_uint, c.c_void_p])
+    assert h.protos["fno_reset"] == (None, []) and h.protos["fno_text"] == (c.c_char_p, [])
+    assert [f[0] for f in T._fields_] == ["a", "b", "d", "w", "e", "m"]
+    assert [f[1] for f in T._fields_] == [c.c_int, c.c_int, c.c_int * 3, (c.c_void_p * 4) * 16, c.c_double, c.c_uint]
+    t = T()
+    t.w[15][3] = 7                                      # [FNO_MAX_LAYERS][4], not [4][FNO_MAX_LAYERS]
+    assert c.sizeof(T) == 4 * 5 + 4 + 8 * 64 + 8 + 8 and T.w.offset == 24 and T.m.offset == 24 + 512 + 8
+    # a second header sees the structs and constants of the first
+    h2 = _lib.read_header("int fno_more(const FnoThing* t);\ntypedef struct FnoTwo { int q[FNO_MAX_LAYERS]; } FnoTwo;", h.consts, h.structs)
+    assert h2.protos["fno_more"] == (c.c_int, [c.POINTER(T)]) and c.sizeof(h2.structs["FnoTwo"]) == 64
+    for text, named in (("int fno_bad(int n, short x);", r"fno_bad\(x\)"),                        # unknown base type
+                        ("short fno_ret(void);", "fno_ret"),
+                        ("int fno_open(int a\nint fno_next(void);", "fno_open"),                 # unterminated, then another
+                        ("int fno_fine(void);\nint fno_eof(int a, float* b", "fno_eof"),         # unterminated at the end
+                        ("int fno_noname(int);", "fno_noname"),
+                        ("int fno_byvalue(FnoThing t);", r"fno_byvalue\(t\)"),
+                        ("int fno_deep(float*** p);", r"fno_deep\(p\)"),
+                        ("float* fno_ptr_ret(void);", "fno_ptr_ret"),
+                        ("int fno_twice(void);\nint fno_twice(void);", "fno_twice"),
+                        ("typedef struct S { short q; } S;", r"S\.q"),                            # a field it cannot place
+                        ("typedef struct S { int q[NOT_DEFINED]; } S;", r"S\.q"),
+                        ("typedef struct S { int *a, b; } S;", "S"),
+                        ("enum { FNO_X = 1 << 2 };", "FNO_X")):
+        with pytest.raises(RuntimeError, match=named):
+            _lib.read_header(_SYNTHETIC_HEADER.replace("void fno_reset(void);", text))
+
+
+def test_binding_is_the_whole_header_and_nothing_else(lib):
+    """every prototype of include/fnoengine.h is bound, with as many argtypes as its text has parameters and the restype its
+    text starts with; the names are found here by a second, cruder route than the reader's"""
+    from pde_policylearning_amd import _lib
+    hdr = _strip_comments(open(os.path.join(ROOT, "include", "fnoengine.h")).read())
+    assert set(re.findall(r"\b(fno_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.ABI.protos)
+    assert list(_lib.ABI.protos) == _lib.EXPORTED_SYMBOLS and len(_lib.EXPORTED_SYMBOLS) == len(set(_lib.EXPORTED_SYMBOLS)) >= 102
+    texts = re.findall(r"([\w \t*]+?)\b(fno_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert [t[1] for t in texts] == _lib.EXPORTED_SYMBOLS
+    returns = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
+    for ret, name, params in texts:
+        restype, argtypes = _lib.ABI.protos[name]
+        assert len(argtypes) == (0 if params.strip() == "void" else params.count(",") + 1), name
+        assert restype is returns[ret.strip()], name
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+        assert all(a is not None for a in argtypes), name
+    assert sum(r is ctypes.c_size_t for r, _ in _lib.ABI.protos.values()) == hdr.count("size_t fno_")
+    # typed where the header is typed: the descriptor structs by pointer, the plan out-parameter, the doubles of Adam
+    vp, vpp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)
+    assert _lib.ABI.protos["fno_spec_plan_create"] == (ctypes.c_int, [ctypes.POINTER(_lib.FnoSpecDesc), vpp])
+    assert _lib.ABI.protos["fno_adam_scalars"] == (None, [ctypes.c_double] * 3 + [ctypes.c_int, vp])
+    assert _lib.ABI.protos["fno_ctrl_stats_update"][1] == [ctypes.POINTER(_lib.FnoCtrlStats), ctypes.c_int, ctypes.c_longlong, vp]
+    assert _lib.ABI.protos["fno_model_backward"][1][6] == ctypes.POINTER(_lib.FnoModelGrads) and _lib.FnoModelGrads is not _lib.FnoModelParams
+
+
+def test_nothing_is_exported_without_a_prototype(lib):
+    """the dynamic symbols of the built library against the two headers: every fno_* symbol has a prototype the compiler
+    checked (public, or csrc/fno_debug.h), every public prototype is defined, and the debug ones the library defines are bound"""
+    import subprocess
+    from pde_policylearning_amd import _lib
+    # (the toolchain ships llvm-readelf, not llvm-nm: its dynamic symbol table, rows `Num: Value Size Type Bind Vis Ndx Name`)
+    out = subprocess.run([_toolchain("llvm-readelf"), "--dyn-syms", "-W", _lib.LIB_PATH], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    rows = [ln.split() for ln in out.stdout.splitlines()]
+    defined = {r[7] for r in rows if len(r) == 8 and r[7].startswith("fno_") and r[6] != "UND"}
+    assert all(r[3] == "FUNC" and r[4] == "GLOBAL" for r in rows if len(r) == 8 and r[7] in defined)
+    dbg = _strip_comments(open(os.path.join(ROOT, "pde_policylearning_amd", "csrc", "fno_debug.h")).read())
+    debug = set(re.findall(r"\b(fno_[a-z0-9_]+)\s*\(", dbg))
+    assert debug == set(_lib.DEBUG_ABI.protos) and len(debug) == 6 and not debug & set(_lib.EXPORTED_SYMBOLS)
+    assert all(n.startswith("fno_debug_") for n in debug)
+    assert set(_lib.EXPORTED_SYMBOLS) <= defined, sorted(set(_lib.EXPORTED_SYMBOLS) - defined)
+    assert defined <= set(_lib.EXPORTED_SYMBOLS) | debug, sorted(defined - set(_lib.EXPORTED_SYMBOLS) - debug)
+    for name in debug & defined:
+        restype, argtypes = _lib.DEBUG_ABI.protos[name]
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes, name
+    assert {"fno_debug_launch_log", "fno_debug_launch_count", "fno_debug_launch_get", "fno_debug_pino_twopass"} <= defined
+    assert '#include "fno_debug.h"' in open(os.path.join(ROOT, "pde_policylearning_amd", "csrc", "fno_abi.hip")).read()
+
+
+@pytest.fixture(scope="module")
+def header_probe(tmp_path_factory):
+    """What the C compiler makes of include/fnoengine.h: a generated program (compiled as C, so the header is C) prints the
+    size of every struct, offset and size of every field, and every constant; {("sizeof", S): n, (S, field): (offset, size),
+    ("const", NAME): value}."""
+    import subprocess
+    from pde_policylearning_amd import _lib
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "fnoengine.h"', 'int main(void) {']
+    for sname, cls in _lib.ABI.structs.items():
+        lines.append(f'  printf("sizeof {sname} %zu 0\\n", sizeof({sname}));')
+        for fname, _ in cls._fields_:
+            lines.append(f'  printf("{sname} {fname} %zu %zu\\n", offsetof({sname}, {fname}), sizeof((({sname}*)0)->{fname}));')
+    for cname in _lib.ABI.consts:
+        lines.append(f'  printf("const {cname} %lld 0\\n", (long long)({cname}));')
+    d = tmp_path_factory.mktemp("header_probe")
+    (d / "probe.c").write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    cc = subprocess.run([_toolchain("clang"), "-x", "c", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                         str(d / "probe.c"), "-o", str(d / "probe")], capture_output=True, text=True, timeout=120)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(d / "probe")], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stderr
+    return {(a, b): (int(x), int(y)) for a, b, x, y in (ln.split() for ln in run.stdout.splitlines())}
+
+
+def test_struct_layout_matches_a_compiled_probe(header_probe):
+    """all eight structs: ctypes.sizeof and every field's offset and size of the derived classes equal the compiler's"""
+    from pde_policylearning_amd import _lib
+    hdr = _strip_comments(open(os.path.join(ROOT, "include", "fnoengine.h")).read())
+    names = re.findall(r"typedef\s+struct\s+(\w+)\s*\{", hdr)
+    assert names == list(_lib.ABI.structs) and len(names) == 8
+    for sname in names:
+        cls = getattr(_lib, sname)
+        assert cls is _lib.ABI.structs[sname] and cls.__name__ == sname
+        assert ctypes.sizeof(cls) == header_probe[("sizeof", sname)][0], sname
+        assert len(cls._fields_) == sum(1 for k in header_probe if k[0] == sname)
+        for fname, _ in cls._fields_:
+            f = getattr(cls, fname)
+            assert (f.offset, f.size) == header_probe[(sname, fname)], (sname, fname)
+    assert ctypes.sizeof(_lib.FnoModelParams) == ctypes.sizeof(_lib.FnoModelGrads) > 8 * 64
+
+
+def test_constants_are_the_headers(header_probe):
+    from pde_policylearning_amd import _lib, functional
+    const = {k[1]: v[0] for k, v in header_probe.items() if k[0] == "const"}
+    assert const == _lib.ABI.consts and len(const) >= 18
+    hdr = _strip_comments(open(os.path.join(ROOT, "include", "fnoengine.h")).read())
+    assert set(re.findall(r"#define[ \t]+(\w+)[ \t]+\S", hdr)) | set(re.findall(r"\b(FNO_\w+)\s*=", hdr)) == set(const)
+    assert _lib.FNO_MAX_LAYERS == const["FNO_MAX_LAYERS"] and _lib.FNO_CTRL_STATS_MAX == const["FNO_CTRL_STATS_MAX"]
+    assert functional.STATS_MAX_FIELDS == const["FNO_CTRL_STATS_MAX"]
+    assert functional._ACT_CODES == {"gelu": const["FNO_ACT_GELU"], "relu": const["FNO_ACT_RELU"]}
+    assert _lib.NORM_CODES == {"backward": const["FNO_NORM_BACKWARD"], None: const["FNO_NORM_BACKWARD"],
+                               "forward": const["FNO_NORM_FORWARD"], "ortho": const["FNO_NORM_ORTHO"]}
 
 
 def test_plan_rejects_bad_arguments_without_gpu(lib):

@@ -38,7 +38,6 @@ for _ in range(5):
 torch.cuda.synchronize()
 L.fno_profile_enable(0)
 launch_ms = {name: ms / max(cnt, 1) for name, ms, cnt in _lib.profile_summary()}
-L.fno_debug_clock_dump.argtypes = [C.c_void_p, C.c_size_t]
 N = 4 * 1024 * 8
 buf = (C.c_ulonglong * N)()
 assert L.fno_debug_clock_dump(buf, N) == 0

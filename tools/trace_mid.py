@@ -15,7 +15,6 @@ for _ in range(3):
 torch.cuda.synchronize()
 L = _lib.lib()
 buf = (C.c_ulonglong * (16 * 256))()
-L.fno_debug_trace_dump.argtypes = [C.c_void_p, C.c_size_t]
 assert L.fno_debug_trace_dump(buf, 16 * 256) == 0
 t0 = min(buf[w * 256] for w in range(8))
 for w in range(8):

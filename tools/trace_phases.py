@@ -22,7 +22,6 @@ for _ in range(3):
 torch.cuda.synchronize()
 L = _lib.lib()
 buf = (C.c_ulonglong * (16 * 256))()
-L.fno_debug_trace_dump.argtypes = [C.c_void_p, C.c_size_t]
 assert L.fno_debug_trace_dump(buf, 16 * 256) == 0
 for w in [int(v) for v in os.environ.get("WAVES", "0,3").split(",")]:
     row = [buf[w * 256 + i] for i in range(256)]
