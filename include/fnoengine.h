@@ -432,6 +432,25 @@ int fno_channel_mlp_backward(int batch, int channels, int hidden, size_t plane, 
                              float* db2, float* dgate, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Domain padding of the FNO family (neuralop/models/padding.py:35-95; tfno.py:195-211 pads the lifted field, runs the
+ * Fourier blocks on the extended grid and crops before the projection).  x (planes, dims[0..ndim)) fp32 with planes =
+ * batch * channels, y (planes, dims[d] + before[d] + after[d]); ndim 1, 2 or 3.  dims / before / after are HOST arrays of
+ * ndim ints, read before the call returns.
+ *   fno_domain_pad:  y = x with before[d] zeros in front of and after[d] zeros behind axis d.  Every element of y is written;
+ *     the margin is +0.0f, the interior is copied bit for bit (NaN payloads, infinities, -0.0).
+ *   fno_domain_crop: x = the interior of y.
+ * Each is the other's adjoint: the backward of a pad is the crop of the gradient and the reverse.  All pads zero is a plain
+ * copy.  One launch, no workspace, no atomics; stores are whole 16-byte vectors wherever the output's address allows it
+ * (tensors need 4-byte alignment only).  FNO_EINVAL: a null pointer, ndim outside 1..3, a dimension < 1, a negative pad;
+ * FNO_EUNSUPPORTED: more than 2^30 elements along a padded axis or more than 2^62 in the padded tensor.  The checks need
+ * no GPU.
+ * ---------------------------------------------------------------------- */
+int fno_domain_pad(int ndim, size_t planes, const int* dims, const int* before, const int* after, const float* x, float* y,
+                   void* stream);
+int fno_domain_crop(int ndim, size_t planes, const int* dims, const int* before, const int* after, const float* y, float* x,
+                    void* stream);
+
+/* ------------------------------------------------------------------------
  * Lifting layer on its own:  y = W x + b,  x (B, Cin <= 4, PW) -> y (B, C, PW), C in {32, 64}, PW % 128 == 0
  * (neuralop/models/tfno.py:11-20; also the `fc0` + Re-conditioning front of the PINO observers,
  * libs/models/pino_models/pinobserver.py:205-207, once its two linear maps are composed).  backward gives the

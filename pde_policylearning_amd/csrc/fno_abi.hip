@@ -30,6 +30,7 @@
 #include "k_projection2.h"
 #include "k_projection_h2.h"
 #include "k_channel_mlp.h"
+#include "k_domain_pad.h"
 #include "k_spectral_mid.h"
 #include "k_spec1d.h"
 #include "k_pino_loss.h"
@@ -3377,6 +3378,66 @@ extern "C" int fno_channel_mlp_backward(int B, int C, int hidden, size_t PW, con
   jobs.add(w.db2_part, db2, w.grid * 4, 1, C, C, C);
   if (gate) jobs.add(w.dg_part, dgate, w.grid, 1, C, C, C);
   return jobs.run(st);
+}
+
+// ===========================================================================
+// Domain padding (neuralop/models/padding.py:35-95; k_domain_pad.h): zero-pad a (planes, dims) tensor, or crop the interior
+// back out.  One launch either way, laid over the output in 16-byte quads.
+// ===========================================================================
+static constexpr int FNO_GRID_DOMPAD = 8;                     // workgroups of 256 threads a CU holds (four waves each, no LDS)
+static constexpr long long DOMPAD_MAX_EXTENT = 1ll << 30;      // per padded axis: coordinates and their sums stay in int
+static constexpr long long DOMPAD_MAX_ELEMS = 1ll << 62;       // in all: flat offsets stay in a signed 64-bit integer
+static int dompad_run(bool pad, const char* fn, int ndim, size_t planes, const int* dims, const int* before, const int* after,
+                      const float* src, float* dst, void* stream) {
+  if (!dims || !before || !after || !src || !dst) return fail(FNO_EINVAL, "%s: null argument", fn);
+  if (ndim < 1 || ndim > 3) return fail(FNO_EINVAL, "%s: ndim=%d (1, 2 or 3)", fn, ndim);
+  long long U[3] = {1, 1, 1}, P[3] = {1, 1, 1}, bf[3] = {0, 0, 0};      // unpadded, padded, leading zeros; right-aligned
+  for (int d = 0; d < ndim; ++d) {
+    const int k = 3 - ndim + d;
+    if (dims[d] < 1) return fail(FNO_EINVAL, "%s: dims[%d]=%d (at least 1)", fn, d, dims[d]);
+    if (before[d] < 0 || after[d] < 0) return fail(FNO_EINVAL, "%s: negative pad on axis %d (before %d, after %d)", fn, d, before[d], after[d]);
+    U[k] = dims[d];
+    bf[k] = before[d];
+    P[k] = (long long)dims[d] + before[d] + after[d];
+  }
+  long long total = (long long)std::min<size_t>(planes, (size_t)DOMPAD_MAX_ELEMS + 1);
+  bool fits = total <= DOMPAD_MAX_ELEMS;
+  for (int k = 0; k < 3; ++k) {
+    fits = fits && P[k] <= DOMPAD_MAX_EXTENT && (total == 0 || P[k] <= DOMPAD_MAX_ELEMS / total);
+    if (fits) total *= P[k];
+  }
+  if (!fits)
+    return fail(FNO_EUNSUPPORTED, "%s: at most 2^30 elements per padded axis and 2^62 in the padded tensor (got %zu planes of %lld x %lld x %lld)",
+                fn, planes, P[0], P[1], P[2]);
+  if ((((uintptr_t)src | (uintptr_t)dst) & 3)) return fail(FNO_EINVAL, "%s: tensor not aligned to 4 bytes", fn);
+  DomPadArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = (const unsigned*)src;
+  a.out = (unsigned*)dst;
+  for (int k = 0; k < 3; ++k) {
+    a.R[k] = (int)(pad ? P[k] : U[k]);
+    a.I[k] = (int)(pad ? U[k] : P[k]);
+    a.off[k] = (int)(pad ? -bf[k] : bf[k]);
+  }
+  a.n_out = (long long)planes * a.R[0] * a.R[1] * a.R[2];
+  if (a.n_out == 0) return FNO_OK;
+  a.head = (int)std::min<long long>(a.n_out, (4 - (long long)(((uintptr_t)dst >> 2) & 3)) & 3);
+  a.nq = (a.n_out - a.head) / 4;
+  const long long blocks = std::max<long long>(1, std::min<long long>((a.nq + 255) / 256, (long long)FNO_GRID_DOMPAD * dev_ncu()));
+  long long step = 4 * blocks * 256;
+  for (int k = 2; k >= 0; --k) { a.s[k] = (int)(step % a.R[k]); step /= a.R[k]; }
+  a.sp = step;
+  const int nq = (int)std::min<long long>(a.nq, 0x7fffffff);
+  if (pad) return LV("k_domain_pad", 0, nq), launch("k_domain_pad", k_domain_pad, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return LV("k_domain_crop", 0, nq), launch("k_domain_crop", k_domain_crop, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+}
+extern "C" int fno_domain_pad(int ndim, size_t planes, const int* dims, const int* before, const int* after, const float* x,
+                              float* y, void* stream) {
+  return dompad_run(true, "fno_domain_pad", ndim, planes, dims, before, after, x, y, stream);
+}
+extern "C" int fno_domain_crop(int ndim, size_t planes, const int* dims, const int* before, const int* after, const float* y,
+                               float* x, void* stream) {
+  return dompad_run(false, "fno_domain_crop", ndim, planes, dims, before, after, y, x, stream);
 }
 
 // ===========================================================================

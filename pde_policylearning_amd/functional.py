@@ -2282,3 +2282,88 @@ def channel_mlp(u, x, w1, b1, w2, b2, gate=None, gelu_out=False):
     input, w1 (H, C[, 1..]), w2 (C, H[, 1..]), gate (C) / (1, C, 1..) or None (identity skip); (C, H) in CHANNEL_MLP_WIDTHS.
     One kernel per direction; the backward recomputes the intermediates from u and x and skips dx when x needs no gradient."""
     return _ChannelMlpFn.apply(u, x, w1, b1, w2, b2, gate, gelu_out)
+
+
+# ----------------------------------------------------------------------------
+# domain padding: zero-pad the grid of a (B, C, d1[, d2[, d3]]) tensor, or crop the interior back out
+# ----------------------------------------------------------------------------
+def _domain_amounts(e, ndim, before, after):
+    """`before` / `after` as ndim-tuples of non-negative ints (an int stands for every axis)"""
+    out = []
+    for name, v in (("before", before), ("after", after)):
+        v = (int(v),) * ndim if isinstance(v, int) else tuple(int(p) for p in v)
+        if len(v) != ndim or min(v) < 0:
+            raise _refuse(e, name, f"be {ndim} non-negative amounts, one per grid axis", v)
+        out.append(v)
+    return out
+
+
+def _domain_move(e, fname, src, dims, before, after, out_dims):
+    """one fno_domain_pad / fno_domain_crop call on a checked, contiguous `src` (B, C, ...): -> (B, C) + out_dims"""
+    ndim = len(dims)
+    ints = C.c_int * ndim
+    dst = torch.empty(tuple(src.shape[:2]) + tuple(out_dims), dtype=torch.float32, device=src.device)
+    _call(e, src.device, fname, ndim, src.shape[0] * src.shape[1], ints(*dims), ints(*before), ints(*after), src, dst, STREAM)
+    return dst
+
+
+def _domain_operand(e, name, t):
+    _require_cuda(t, name)
+    if not 3 <= t.dim() <= 5:
+        raise _refuse(e, name, "be (B, C, d1[, d2[, d3]])", tuple(t.shape))
+    return t.contiguous()
+
+
+class _DomainPadFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, before, after):
+        e = "domain_pad"
+        x = _domain_operand(e, "x", x)
+        dims = tuple(x.shape[2:])
+        before, after = _domain_amounts(e, len(dims), before, after)
+        ctx.meta = (dims, before, after)
+        return _domain_move(e, "fno_domain_pad", x, dims, before, after, [d + b + a for d, b, a in zip(dims, before, after)])
+
+    @staticmethod
+    def backward(ctx, dy):
+        e = "domain_pad backward"
+        dims, before, after = ctx.meta
+        dy = _domain_operand(e, "dy", dy)
+        if tuple(dy.shape[2:]) != tuple(d + b + a for d, b, a in zip(dims, before, after)):
+            raise _refuse(e, "dy", "have the padded grid", tuple(dy.shape))
+        return _domain_move(e, "fno_domain_crop", dy, dims, before, after, dims), None, None
+
+
+class _DomainCropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, before, after):
+        e = "domain_crop"
+        y = _domain_operand(e, "y", y)
+        before, after = _domain_amounts(e, y.dim() - 2, before, after)
+        dims = tuple(p - b - a for p, b, a in zip(y.shape[2:], before, after))
+        if min(dims) < 1:
+            raise _refuse(e, "y", f"be larger than its pads {before} + {after} on every axis", tuple(y.shape))
+        ctx.meta = (dims, before, after)
+        return _domain_move(e, "fno_domain_crop", y, dims, before, after, dims)
+
+    @staticmethod
+    def backward(ctx, dx):
+        e = "domain_crop backward"
+        dims, before, after = ctx.meta
+        dx = _domain_operand(e, "dx", dx)
+        if tuple(dx.shape[2:]) != dims:
+            raise _refuse(e, "dx", "have the cropped grid", tuple(dx.shape))
+        return _domain_move(e, "fno_domain_pad", dx, dims, before, after, [d + b + a for d, b, a in zip(dims, before, after)]), None, None
+
+
+def domain_pad(x, before, after):
+    """Zero-pad the grid of x (B, C, d1[, d2[, d3]]): `before[d]` zeros in front of axis d and `after[d]` behind it (ints or one
+    int for every axis).  One kernel (k_domain_pad) writes the whole result - interior copied bit for bit, margin +0.0; the
+    backward is the crop of the gradient (k_domain_crop)."""
+    return _DomainPadFn.apply(x, before, after)
+
+
+def domain_crop(y, before, after):
+    """The interior of a padded y (B, C, p1[, p2[, p3]]): drops `before[d]` leading and `after[d]` trailing entries of axis d.
+    One kernel (k_domain_crop); the backward is the zero-pad of the gradient (k_domain_pad)."""
+    return _DomainCropFn.apply(y, before, after)

@@ -10,3 +10,4 @@ from .spectral_regressor import SpectralRegressor  # noqa: F401
 from .model_dispatcher import get_model, available_models  # noqa: F401
 from .spectral_convolution import SpectralConv, FactorizedSpectralConv  # noqa: F401
 from .fno_block import FNOBlocks  # noqa: F401
+from .padding import DomainPadding  # noqa: F401

@@ -8,6 +8,7 @@ from torch import nn
 
 from ... import functional as F
 from .fno_block import FNOBlocks
+from .padding import DomainPadding
 from .spectral_convolution import SpectralConv, _unsupported
 
 
@@ -36,6 +37,15 @@ class Projection(nn.Module):
 
 
 class FNO(nn.Module):
+    """neuralop.models.FNO (tfno.py:107-211).
+
+    `domain_padding=f` (with `domain_padding_mode` 'one-sided' or 'symmetric') zero-pads the lifted field by round(f * r)
+    entries per grid axis, runs the Fourier blocks on the extended grid and crops before the projection, as the reference
+    does on square and cubic grids.  On a grid whose axes get different amounts the reference's pad and unpad disagree
+    ((32, 64) at 0.25 -> (48, 72) -> (40, 56); (8, 8, 12) -> (11, 10, 14) -> (9, 8, 11); (2, 40) unpads to an empty tensor) and
+    its model returns the wrong shape; here every axis is padded and cropped by its own amount, so the output has the input's
+    grid (padding.DomainPadding).  Padding cannot be combined with `output_scaling_factor`."""
+
     def __init__(self, n_modes, hidden_channels, in_channels=3, out_channels=1, lifting_channels=256,
                  projection_channels=256, n_layers=4, output_scaling_factor=None,
                  incremental_n_modes=None, use_mlp=False, mlp_dropout=0, mlp_expansion=0.5,
@@ -45,8 +55,14 @@ class FNO(nn.Module):
                  decomposition_kwargs=dict(), domain_padding=None, domain_padding_mode='one-sided',
                  fft_norm='forward', SpectralConv=SpectralConv, **kwargs):
         super().__init__()
-        if domain_padding is not None and domain_padding > 0:
-            _unsupported("domain_padding")
+        if domain_padding is not None and domain_padding > 0:      # a scalar, as in the reference (tfno.py:158)
+            if output_scaling_factor is not None:
+                raise NotImplementedError("fnoengine FNO: domain_padding together with output_scaling_factor is not supported "
+                                          "(the resized blocks are torch compositions)")
+            self.domain_padding = DomainPadding(domain_padding=domain_padding, padding_mode=domain_padding_mode)
+        else:
+            self.domain_padding = None
+        self.domain_padding_mode = domain_padding_mode
         self.n_dim = len(n_modes)
         self.n_modes = tuple(n_modes)
         self.hidden_channels = hidden_channels
@@ -84,6 +100,8 @@ class FNO(nn.Module):
         <= 4 input / output channels, projection_channels 256, and either rows that tile the 128 / 256-pixel workgroup tile
         (last dim 32, 64, 128, 256) or "loose rows" (any last dim in 32..320 on planes that tile by 128 pixels: 96 x 96,
         160 x 160, 192 x 192 grids ...; split-precision GEMM mode)."""
+        if getattr(self, "domain_padding", None) is not None:
+            return False           # the whole-model plan knows no padding: lifting, pad, block stack, crop, projection (_forward_padded)
         if self.fno_blocks.convs.separable or self.fno_blocks.convs.output_scaling_factor is not None:
             return False           # torch compositions (SpectralConv._torch_composition): layer by layer
         if getattr(self.fno_blocks, "mlp", None) is not None:
@@ -112,6 +130,8 @@ class FNO(nn.Module):
             for p in self.parameters():
                 if p.grad is not None:
                     p.grad.zero_()
+        if getattr(self, "domain_padding", None) is not None:      # (modules pickled before the option existed have no such attribute)
+            return self._forward_padded(x)
         if getattr(self.fno_blocks, "mlp", None) is not None:
             return self._forward_mlp(x)
         x = self.lifting(x)
@@ -119,20 +139,45 @@ class FNO(nn.Module):
             x = self.fno_blocks(x, l)
         return self.projection(x)
 
-    def _forward_mlp(self, x):
-        """The layer loop of a model with channel MLPs: lifting and projection head on their engine kernels where those cover
-        the shape, the torch modules otherwise; every block is one fused Fourier layer + one channel-MLP kernel."""
-        F._require_cuda(x, "x")
+    def _lift(self, x):
         if F.lifting_supported(x, self.hidden_channels):
-            x = F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
-        else:
-            x = self.lifting(x)
-        for l in range(self.n_layers):
-            x = self.fno_blocks(x, l)
+            return F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
+        return self.lifting(x)
+
+    def _project(self, x):
         prj = self.projection
         if F.projection_supported(x, self.projection_channels, self.out_channels):
             return F.projection_head(x, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
         return prj(x)
+
+    def _forward_mlp(self, x):
+        """The layer loop of a model with channel MLPs: lifting and projection head on their engine kernels where those cover
+        the shape, the torch modules otherwise; every block is one fused Fourier layer + one channel-MLP kernel."""
+        F._require_cuda(x, "x")
+        x = self._lift(x)
+        for l in range(self.n_layers):
+            x = self.fno_blocks(x, l)
+        return self._project(x)
+
+    def _forward_padded(self, x):
+        """tfno.py:195-211 with domain padding: lifting, zero-pad (k_domain_pad), the blocks on the extended grid, crop
+        (k_domain_crop), projection.  The blocks are one fused engine stack where the block kernels cover the PADDED grid
+        (functional.blocks_supported), else the per-layer composition; with channel MLPs the layer loop of _forward_mlp.
+        Every gradient goes through autograd (forward() has cleared a direct-write bucket's gradients)."""
+        F._require_cuda(x, "x")
+        blk, convs = self.fno_blocks, self.fno_blocks.convs
+        x = self.domain_padding.pad(self._lift(x))
+        gelu_mask = F.default_gelu_mask(self.n_layers)
+        if (getattr(blk, "mlp", None) is None and convs.bias is not None and not convs.separable
+                and convs.output_scaling_factor is None
+                and F.blocks_supported(x, self.n_layers, convs.half_n_modes, self.fft_norm, gelu_mask)):
+            spec_ws = [w for l in range(self.n_layers) for w in convs.layer_weights(l)]
+            x = F.fno_blocks(x, [blk.fno_skips[l].weight for l in range(self.n_layers)], spec_ws,
+                             convs.bias.reshape(self.n_layers, -1), convs.half_n_modes, self.fft_norm, gelu_mask=gelu_mask)
+        else:
+            for l in range(self.n_layers):
+                x = blk(x, l)
+        return self._project(self.domain_padding.unpad(x))
 
 
 class FNO2d(FNO):
@@ -217,6 +262,11 @@ class FNO1d(FNO):
         """the whole-model plan (fno_model_plan_create) has no one-dimensional form: forward() below is the layer chain"""
         return False
 
+    def _hidden_length(self, n):
+        """the length the blocks run on: N, or N with its domain padding (what the 1-D kernels' shape rule applies to)"""
+        pad = getattr(self, "domain_padding", None)
+        return n if pad is None else pad.padded_resolution((n,))[0]
+
     def _covered(self, x, modes, gelu_in):
         """whether the 1-D kernels take this input; decided once per (shape, device, kept bins) - the probe needs a tensor of
         the hidden shape, which a forward pass should not allocate every time"""
@@ -225,7 +275,7 @@ class FNO1d(FNO):
         if key not in seen:
             ok = x.dim() == 3 and x.shape[1] == self.in_channels
             if ok:
-                u = x.new_empty((x.shape[0], self.hidden_channels, x.shape[2]))
+                u = x.new_empty((x.shape[0], self.hidden_channels, self._hidden_length(x.shape[2])))
                 ok = all(F.spectral_layer_supported(u, 1, modes, self.fft_norm, modes[0], g) for g in set(gelu_in))
             seen[key] = ok
         return seen[key]
@@ -235,9 +285,12 @@ class FNO1d(FNO):
         blk, convs, c = self.fno_blocks, self.fno_blocks.convs, self.hidden_channels
         modes = tuple(convs.half_n_modes)
         gelu_in = [l > 0 and blk.gelu_after(l - 1) for l in range(self.n_layers)]
+        pad = getattr(self, "domain_padding", None)      # (modules pickled before the option existed have no such attribute)
         if not self._covered(x, modes, gelu_in):
-            raise RuntimeError(f"fnoengine FNO1d: no one-dimensional kernel for input {tuple(x.shape)} with {modes[0]} kept bins "
-                               f"(needs (B, {self.in_channels}, N), N a multiple of 128 in [128, 8192], at most 64 kept bins)")
+            padded = "" if pad is None or x.dim() != 3 else f" padded to N = {self._hidden_length(x.shape[2])}"
+            raise RuntimeError(f"fnoengine FNO1d: no one-dimensional kernel for input {tuple(x.shape)}{padded} with {modes[0]} kept bins "
+                               f"(needs (B, {self.in_channels}, N), N a multiple of 128 in [128, 8192], at most 64 kept bins"
+                               f"{'; with domain padding the rule applies to the padded N' if pad is not None else ''})")
         if getattr(self, "_direct_grads", False) and torch.is_grad_enabled():
             # a direct-write bucket (trainer.FlatGradBucket(direct_module=...)) does not clear this model's gradients: it
             # expects the engine to overwrite them.  This forward hands every gradient to autograd, which accumulates into
@@ -249,11 +302,15 @@ class FNO1d(FNO):
             u = F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
         else:
             u = self.lifting(x)
+        if pad is not None:
+            u = pad.pad(u)
         for l in range(self.n_layers):
             u = F.spectral_pointwise_layer(u, convs.layer_weights(l), modes, self.fft_norm, blk.fno_skips[l].weight,
                                            convs.bias[l].reshape(-1), input_gelu=gelu_in[l])
         if blk.gelu_after(self.n_layers - 1):          # only a one-layer stack ends on an activation (fno_block.py:149)
             u = self.non_linearity(u)
+        if pad is not None:
+            u = pad.unpad(u)
         prj = self.projection
         if F.projection_supported(u, self.projection_channels, self.out_channels):
             return F.projection_head(u, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
