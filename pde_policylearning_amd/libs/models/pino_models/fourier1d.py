@@ -6,7 +6,7 @@ parts as torch modules."""
 import torch.nn.functional as TF
 from torch import nn
 
-from .... import functional as F
+from .... import layer_stack as LS
 from .basics import SpectralConv1d
 
 _ACTS = {"tanh": TF.tanh, "gelu": TF.gelu, "relu": TF.relu, "elu": TF.elu, "leaky_relu": TF.leaky_relu}     # utils.py:36-49
@@ -27,39 +27,29 @@ class FNO1d(nn.Module):
         self.fc2 = nn.Linear(fc_dim, out_dim)
         self.act_name, self.act = act, _ACTS[act]
 
-    def _engine_covers(self, x):
-        """the all-engine route: GELU, one width for every layer, and shapes the three kernel families take; decided once per
-        (shape, device) - the probes need tensors of the lifted shape, which a forward pass should not allocate every time"""
-        if self.act_name != "gelu" or not x.is_cuda or x.dim() != 3:
-            return False
-        key = (tuple(x.shape), x.device)
-        seen = self.__dict__.setdefault("_covered_shapes", {})
-        if key not in seen:
-            widths = {self.fc0.out_features} | {c.in_channels for c in self.sp_convs} | {c.out_channels for c in self.sp_convs}
-            ok = len(widths) == 1
-            if ok:
-                c = widths.pop()
-                xt = x.new_empty((x.shape[0], x.shape[2], x.shape[1]))       # (B, in_dim, N): shape only
-                u = x.new_empty((x.shape[0], c, x.shape[1]))
-                ok = (F.lifting_supported(xt, c) and F.projection_supported(u, self.fc1.out_features, self.fc2.out_features)
-                      and all(F.spectral_layer_supported(u, 1, (sp.modes1,), "backward", sp.modes1, i > 0)
-                              for i, sp in enumerate(self.sp_convs)))
-            seen[key] = ok
-        return seen[key]
+    ROUTES = (LS.CHAIN, LS.TORCH)
+
+    def stack(self):
+        uniform = self.act_name == "gelu" and len({w.in_channels for w in self.ws} | {w.out_channels for w in self.ws}) == 1
+        return LS.conv_stack(self.sp_convs, self.ws, self.act,
+                             [([sp.weights1], (sp.modes1,), sp.modes1) for sp in self.sp_convs] if uniform else None)
+
+    def route(self, x, stack=None):
+        """The rung the layers take for an input shaped like x (B, N, in_dim).  All of the engine or none of it: the chain
+        needs the lifting and the projection head on their kernels too."""
+        if not (x.is_cuda and x.dim() == 3):
+            return LS.TORCH
+        xt = x.permute(0, 2, 1)
+        u = LS.probe(xt, self.fc0.out_features)
+        ends = LS.lift_covered(xt, self.fc0) and LS.head_covered(u, self.fc1, self.fc2)
+        return LS.route(u, stack or self.stack(), self.ROUTES if ends else (LS.TORCH,))
 
     def forward(self, x):
-        if self._engine_covers(x):
-            u = F.lifting(x.permute(0, 2, 1), self.fc0.weight, self.fc0.bias)
-            for i, (sp, w) in enumerate(zip(self.sp_convs, self.ws)):
-                # the activation behind layer i - 1 (fourier1d.py:55-56) is applied while layer i loads its input
-                u = F.spectral_pointwise_layer(u, [sp.weights1], (sp.modes1,), "backward", w.weight, w.bias, input_gelu=i > 0,
-                                               direct_grads=getattr(sp, "_direct_grads", False))
-            y = F.projection_head(u, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-            return y.permute(0, 2, 1)
-        last = len(self.ws) - 1
-        x = self.fc0(x).permute(0, 2, 1)
-        for i, (sp, w) in enumerate(zip(self.sp_convs, self.ws)):
-            x = sp(x) + w(x)
-            if i != last:
-                x = self.act(x)
-        return self.fc2(self.act(self.fc1(x.permute(0, 2, 1))))
+        stack = self.stack()
+        rung = self.route(x, stack)
+        if rung == LS.TORCH:
+            u = LS.run(self.fc0(x).permute(0, 2, 1), stack, (rung,))
+            return self.fc2(self.act(self.fc1(u.permute(0, 2, 1))))
+        # chain: the activation behind layer i - 1 (fourier1d.py:55-56) is applied while layer i loads its input
+        u = LS.run(LS.lift(x.permute(0, 2, 1), self.fc0), stack, (rung,))
+        return LS.head(u, self.fc1, self.fc2).permute(0, 2, 1)

@@ -14,7 +14,7 @@ convolutions on the engine and the pointwise parts as torch modules.  There is n
 import torch.nn.functional as TF
 from torch import nn
 
-from .... import functional as F
+from .... import layer_stack as LS
 from .basics import SpectralConv2d
 from .fourier1d import _ACTS
 
@@ -58,25 +58,22 @@ class FNO2d(nn.Module):
             return [round(i * size_1) for i in self.pad_ratio], [round(i * size_2) for i in self.pad_ratio]
         return [0, 0], [0, 0]
 
-    def _engine_covers(self, x):
-        """the all-engine route up to the head: GELU, one width for every layer, and shapes the lifting and the layer kernels
-        take (the layers see the PADDED grid); decided once per (shape, device)"""
-        if self.act_name != "gelu" or not x.is_cuda or x.dim() != 4:
-            return False
-        key = (tuple(x.shape), x.device)
-        seen = self.__dict__.setdefault("_covered_shapes", {})
-        if key not in seen:
-            ok = len(set(self.layers)) == 1
-            if ok:
-                c = self.layers[0]
-                p1, p2 = self._pads(x.shape[1], x.shape[2])
-                xt = x.new_empty((x.shape[0], x.shape[3], x.shape[1], x.shape[2]))       # (B, in_dim, X, Y): shape only
-                u = x.new_empty((x.shape[0], c, x.shape[1] + sum(p1), x.shape[2] + sum(p2)))
-                ok = (F.lifting_supported(xt, c)
-                      and all(F.spectral_layer_supported(u, 2, (sp.modes1, sp.modes2), "backward", sp.modes2, i > 0)
-                              for i, sp in enumerate(self.sp_convs)))
-            seen[key] = ok
-        return seen[key]
+    ROUTES = (LS.CHAIN, LS.TORCH)
+
+    def stack(self):
+        uniform = self.act_name == "gelu" and len(set(self.layers)) == 1
+        return LS.conv_stack(self.sp_convs, self.ws, self.act, [([sp.weights1, sp.weights2], (sp.modes1, sp.modes2), sp.modes2)
+                                                                for sp in self.sp_convs] if uniform else None)
+
+    def route(self, x, stack=None):
+        """The rung the layers take for an input shaped like x (B, X, Y, in_dim); they see the PADDED grid.  All of the engine
+        up to the head or none of it: the chain needs the lifting on its kernels too."""
+        if not (x.is_cuda and x.dim() == 4):
+            return LS.TORCH
+        xt = x.permute(0, 3, 1, 2)
+        p1, p2 = self._pads(x.shape[1], x.shape[2])
+        u = LS.probe(xt, self.layers[0], (x.shape[1] + sum(p1), x.shape[2] + sum(p2)))
+        return LS.route(u, stack or self.stack(), self.ROUTES if LS.lift_covered(xt, self.fc0) else (LS.TORCH,))
 
     def _head(self, x):
         return self.fc3(self.act(self.fc2(self.act(self.fc1(x)))))
@@ -85,20 +82,10 @@ class FNO2d(nn.Module):
         if not x.is_cuda:
             raise RuntimeError(f"fnoengine FNO2d: the input must live on the GPU (got {x.device}); the engine has no CPU path")
         num_pad1, num_pad2 = self._pads(x.shape[1], x.shape[2])
-        if self._engine_covers(x):
-            u = F.lifting(x.permute(0, 3, 1, 2), self.fc0.weight, self.fc0.bias)
-            u = add_padding2(u, num_pad1, num_pad2)
-            for i, (sp, w) in enumerate(zip(self.sp_convs, self.ws)):
-                # the activation behind layer i - 1 (fourier2d.py:78-79) is applied while layer i loads its input
-                u = F.spectral_pointwise_layer(u, [sp.weights1, sp.weights2], (sp.modes1, sp.modes2), "backward", w.weight, w.bias,
-                                               input_gelu=i > 0, direct_grads=getattr(sp, "_direct_grads", False))
-            return self._head(remove_padding2(u, num_pad1, num_pad2).permute(0, 2, 3, 1))
-        last = len(self.ws) - 1
-        batchsize = x.shape[0]
-        x = add_padding2(self.fc0(x).permute(0, 3, 1, 2), num_pad1, num_pad2)
-        size_x, size_y = x.shape[-2], x.shape[-1]
-        for i, (sp, w) in enumerate(zip(self.sp_convs, self.ws)):
-            x = sp(x) + w(x.reshape(batchsize, self.layers[i], -1)).view(batchsize, self.layers[i + 1], size_x, size_y)
-            if i != last:
-                x = self.act(x)
-        return self._head(remove_padding2(x, num_pad1, num_pad2).permute(0, 2, 3, 1))
+        stack = self.stack()
+        rung = self.route(x, stack)
+        u = LS.lift(x.permute(0, 3, 1, 2), self.fc0) if rung == LS.CHAIN else self.fc0(x).permute(0, 3, 1, 2)
+        u = add_padding2(u, num_pad1, num_pad2)
+        # chain: the activation behind layer i - 1 (fourier2d.py:78-79) is applied while layer i loads its input
+        u = LS.run(u, stack, (rung,))
+        return self._head(remove_padding2(u, num_pad1, num_pad2).permute(0, 2, 3, 1))

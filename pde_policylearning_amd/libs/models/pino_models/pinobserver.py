@@ -11,6 +11,7 @@ from torch.nn import init
 
 from .basics import SpectralConv3d
 from .... import functional as F
+from .... import layer_stack as LS
 
 
 def _activation(name):
@@ -52,81 +53,54 @@ class MultiplicativeNet(nn.Module):
         return input1 @ self.B.t() + code + self.bias
 
 
-def _lift_front(fc0, mn, x, re, width):
+def _code(mn, re):
+    """the per-sample Re-conditioning code A re, (B, C)"""
+    return (re if re.dim() >= 2 else re.unsqueeze(-1)) @ mn.A.t()
+
+
+def _lift_front(fc0, mn, x, re):
     """multiplicative_net1(fc0(x), re) as a channels-first tensor (pinobserver.py:205-207, 356-358).  fc0 followed by the
     Re-conditioning affine is ONE linear map of the <= 4 input channels: when the shape allows it the two small matrices are
     composed (autograd differentiates the composition) and applied by the engine's lifting kernels; an input that asks for
     its gradient gets it from them too (functional.lifting)."""
     xc = x.permute(0, 4, 1, 2, 3)
-    if F.lifting_supported(xc, width):
-        w = mn.B @ fc0.weight                                             # (C, in_dim)
-        bias = mn.B @ fc0.bias + mn.bias
-        code = (re if re.dim() >= 2 else re.unsqueeze(-1)) @ mn.A.t()     # (B, C)
-        return F.lifting(xc.contiguous(), w, bias) + code[:, :, None, None, None]
+    if LS.lift_covered(xc, fc0):
+        return F.lifting(xc.contiguous(), mn.B @ fc0.weight, mn.B @ fc0.bias + mn.bias) + _code(mn, re)[:, :, None, None, None]
     return mn(fc0(x), re).permute(0, 4, 1, 2, 3)
+
+
+def _recondition_tail(x, re, mn, fc1, fc2, act, engine=True):
+    """fc2(act(fc1(multiplicative_net2(x, re)))) of the channels-first x, channels-last (pinobserver.py:228-233, 257-273).  On
+    the engine: the Re-conditioning affine as a pointwise mix with the per-sample code added, then fc1 -> GELU -> fc2 for all
+    planes in the projection kernels (hidden tensor never materialised)."""
+    if engine and act is TF.gelu and LS.head_covered(x, fc1, fc2):
+        h = F.pointwise_conv_add(x.contiguous(), mn.B, mn.bias, None) + _code(mn, re)[:, :, None, None, None]
+        return F.projection_head(h, fc1.weight, fc1.bias, fc2.weight, fc2.bias).permute(0, 2, 3, 4, 1)
+    return fc2(act(fc1(mn(x.permute(0, 2, 3, 4, 1), re))))
 
 
 class _SpectralStack(nn.Module):
     """layers of  x <- act(SpectralConv3d(x) + Conv1d_{k=1}(x)), no activation after the last."""
+
+    ROUTES = LS.RUNGS
 
     def _build_stack(self, layers, modes1, modes2, modes3):
         self.sp_convs = nn.ModuleList([SpectralConv3d(i, o, m1, m2, m3)
                                        for i, o, m1, m2, m3 in zip(layers, layers[1:], modes1, modes2, modes3)])
         self.ws = nn.ModuleList([nn.Conv1d(i, o, 1) for i, o in zip(layers, layers[1:])])
 
-    def _chain_supported(self, x):
-        if self.act is not TF.gelu or len(set(self.layers)) != 1:
-            return False
-        for i, conv in enumerate(self.sp_convs):
-            ws, modes, wle = conv.engine_call(x)
-            if not F.spectral_layer_supported(x, len(ws), modes, "backward", wle, i > 0):
-                return False
-        return True
-
-    def _fused_stack(self, x):
-        """The whole stack as ONE engine block stack (fno_model_* with Cin = Cout = 0: per layer one fused kernel each way that
-        applies the previous GELU on load, mixes the channels, adds the inverse last-dim transform of the spectral branch
-        as a K-extension of the same GEMM and the bias; no `SpectralConv(x)` tensor, no addend / gradient-addend passes)
-        when every layer has the same width and kept modes and the weights store exactly the live last-dim modes."""
-        if self.act is not TF.gelu or len(set(self.layers)) != 1:
-            return None
-        calls = [conv.engine_call(x) for conv in self.sp_convs]
-        modes = calls[0][1]
-        if any(c[1] != modes or c[2] != modes[-1] for c in calls):
-            return None
-        n = len(self.ws)
-        gelu_mask = (1 << (n - 1)) - 1                       # GELU after every layer but the last
-        if not F.blocks_supported(x, n, modes, "backward", gelu_mask):
-            return None
-        bias = torch.stack([w.bias for w in self.ws])
-        direct = all(getattr(conv, "_direct_grads", False) for conv in self.sp_convs)
-        return F.fno_blocks(x, [w.weight for w in self.ws], [t for c in calls for t in c[0]], bias, modes, "backward",
-                            gelu_mask=gelu_mask, direct_grads=direct)
+    def stack(self, x):
+        """the stack for an input shaped like x; engine_call announces the live last-dim slices before any weight is read"""
+        uniform = self.act is TF.gelu and len(set(self.layers)) == 1
+        return LS.conv_stack(self.sp_convs, self.ws, self.act, [conv.engine_call(x) for conv in self.sp_convs] if uniform else None)
 
     def _run_stack(self, x):
-        y = self._fused_stack(x)
-        if y is not None:
-            return y
-        if self._chain_supported(x):
-            # the stack chained on PRE-activation tensors: each layer applies the previous layer's GELU while it loads its
-            # input (spectral rows and channel mix alike) and its backward folds gelu' and the two-branch gradient sum in
-            for i, (conv, w) in enumerate(zip(self.sp_convs, self.ws)):
-                ws, modes, wle = conv.engine_call(x)
-                x = F.spectral_pointwise_layer(x, ws, modes, "backward", w.weight, w.bias, input_gelu=i > 0,
-                                               weight_last_extent=wle, direct_grads=getattr(conv, "_direct_grads", False))
-            return x
-        b = x.shape[0]
-        sx, sy, sz = x.shape[-3:]
-        last = len(self.ws) - 1
-        for i, (conv, w) in enumerate(zip(self.sp_convs, self.ws)):
-            if self.layers[i] == self.layers[i + 1] and F.pointwise_supported(x):
-                # Conv1d(k=1) + bias + the residual add in one engine kernel each way (fno_pointwise_*)
-                x = F.pointwise_conv_add(x, w.weight, w.bias, conv(x))
-            else:
-                x = conv(x) + w(x.reshape(b, self.layers[i], -1)).view(b, self.layers[i + 1], sx, sy, sz)
-            if i != last:
-                x = self.act(x)
-        return x
+        return LS.run(x, self.stack(x), self.ROUTES)
+
+
+def _num_pad(pad_ratio, size_z):
+    """zeros in front of / behind the last axis: round(size_z * r) of the extent the reference reads (dim -2, :353)"""
+    return [round(size_z * r) for r in pad_ratio] if max(pad_ratio) > 0 else [0, 0]
 
 
 def _pad_ratio(pad_ratio):
@@ -156,24 +130,13 @@ class PINObserver2d(_SpectralStack):
 
     def forward(self, x, re):
         re = re.float()
-        size_z = x.shape[-2]
-        num_pad = [round(size_z * r) for r in self.pad_ratio] if max(self.pad_ratio) > 0 else [0., 0.]
-        y = self._forward_padded(x, re, [int(p) for p in num_pad])
+        num_pad = _num_pad(self.pad_ratio, x.shape[-2])
+        y = self._forward_padded(x, re, num_pad)
         if y is not None:
             return y
-        x = _lift_front(self.fc0, self.multiplicative_net1, x, re, self.layers[0])
+        x = _lift_front(self.fc0, self.multiplicative_net1, x, re)
         x = _unpad_last(self._run_stack(_pad_last(x, num_pad).contiguous()), num_pad)
-        if (self.act is TF.gelu and self.layers[-1] in (32, 64)
-                and F.projection_supported(x, self.fc1.out_features, self.fc2.out_features)):
-            # channels-first tail on the engine: the Re-conditioning affine as a pointwise mix, then the projection kernels
-            mn = self.multiplicative_net2
-            code = (re if re.dim() >= 2 else re.unsqueeze(-1)) @ mn.A.t()                     # (B, C)
-            h = F.pointwise_conv_add(x.contiguous(), mn.B, mn.bias, None) + code[:, :, None, None, None]
-            y = F.projection_head(h, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-            return y.permute(0, 2, 3, 4, 1)
-        x = self.multiplicative_net2(x.permute(0, 2, 3, 4, 1), re)
-        return self.fc2(self.act(self.fc1(x)))
-
+        return _recondition_tail(x, re, self.multiplicative_net2, self.fc1, self.fc2, self.act)
 
     PER_SAMPLE_MAX = 16      # the per-sample-bias kernels are launched once per sample
 
@@ -191,17 +154,15 @@ class PINObserver2d(_SpectralStack):
         p0, p1 = num_pad
         xc = TF.pad(x.permute(0, 4, 1, 2, 3), (p0, p1)) if p0 + p1 > 0 else x.permute(0, 4, 1, 2, 3).contiguous()
         C = self.layers[0]
-        like = xc[:, :1].expand(-1, C, -1, -1, -1)          # a (B, C, X, Y, T') view for the shape predicates (no memory)
-        if not (F.lifting_supported(xc, C) and F.pointwise_supported(like)
-                and F.projection_supported(like, self.fc1.out_features, self.fc2.out_features)):
+        like = LS.probe(xc, C)                              # a (B, C, X, Y, T') view for the shape predicates (no memory)
+        if not (LS.lift_covered(xc, self.fc0) and F.pointwise_supported(like) and LS.head_covered(like, self.fc1, self.fc2)):
             return None
         fc0, mn1, mn2 = self.fc0, self.multiplicative_net1, self.multiplicative_net2
-        re2 = re if re.dim() >= 2 else re.unsqueeze(-1)
         w = mn1.B @ fc0.weight                                             # (C, in_dim): fc0 then the Re-conditioning mix
-        bias = (mn1.B @ fc0.bias + mn1.bias)[None, :] + re2 @ mn1.A.t()    # (B, C): + the per-sample code
+        bias = (mn1.B @ fc0.bias + mn1.bias)[None, :] + _code(mn1, re)     # (B, C): + the per-sample code
         h = F.zero_last_pads_(F.lifting_per_sample_bias(xc, w, bias), p0, p1)
         h = self._run_stack(h)
-        h = F.pointwise_conv_per_sample_bias(h, mn2.B, mn2.bias[None, :] + re2 @ mn2.A.t())
+        h = F.pointwise_conv_per_sample_bias(h, mn2.B, mn2.bias[None, :] + _code(mn2, re))
         y = F.projection_head(h, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
         if p0 + p1 > 0:
             y = y[..., p0:y.shape[-1] - p1]
@@ -219,18 +180,8 @@ class PlanePredHead(_SpectralStack):
 
     def forward(self, x, num_pad, re, multiplicative_net2):
         x = _unpad_last(self._run_stack(x), num_pad)
-        if (self.act is TF.gelu and self.layers[-1] in (32, 64) and not getattr(self, "no_engine_tail", False)
-                and F.projection_supported(x, self.fc1.out_features, self.fc2.out_features)):
-            # channels-first tail on the engine (as PINObserver2d's): the Re-conditioning affine as a pointwise mix with the
-            # per-sample code added, then fc1 -> GELU -> fc2 for all planes in the projection kernels (hidden tensor never
-            # materialised; pinobserver.py:257-273)
-            mn = multiplicative_net2
-            code = (re if re.dim() >= 2 else re.unsqueeze(-1)) @ mn.A.t()                     # (B, C)
-            h = F.pointwise_conv_add(x.contiguous(), mn.B, mn.bias, None) + code[:, :, None, None, None]
-            y = F.projection_head(h, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-            return y.permute(0, 2, 3, 4, 1)
-        x = multiplicative_net2(x.permute(0, 2, 3, 4, 1), re)
-        return self.fc2(self.act(self.fc1(x)))
+        return _recondition_tail(x, re, multiplicative_net2, self.fc1, self.fc2, self.act,
+                                 not getattr(self, "no_engine_tail", False))
 
 
 class PINObserverFullField(nn.Module):
@@ -251,9 +202,8 @@ class PINObserverFullField(nn.Module):
 
     def forward(self, x, re):
         re = re.float() / self.max_re
-        size_z = x.shape[-2]                  # the reference takes the pad size from dim -2 (:353)
-        num_pad = [round(size_z * r) for r in self.pad_ratio] if max(self.pad_ratio) > 0 else [0., 0.]
-        x = _lift_front(self.fc0, self.multiplicative_net1, x, re, self.layers[0])
+        num_pad = _num_pad(self.pad_ratio, x.shape[-2])
+        x = _lift_front(self.fc0, self.multiplicative_net1, x, re)
         pred = self.observer_head(_pad_last(x, num_pad).contiguous(), num_pad, re, self.multiplicative_net2)
         return pred.permute(0, 4, 1, 2, 3)     # (B, planes, X, Y, T)
 
@@ -290,7 +240,6 @@ class PolicyModel2D(nn.Module):
 
     def forward(self, x, re):
         re = re.float() / self.max_re
-        size_z = x.shape[-2]
-        num_pad = [round(size_z * r) for r in self.pad_ratio] if max(self.pad_ratio) > 0 else [0., 0.]
-        x = _lift_front(self.fc0, self.multiplicative_net1, x, re, self.layers[0])
+        num_pad = _num_pad(self.pad_ratio, x.shape[-2])
+        x = _lift_front(self.fc0, self.multiplicative_net1, x, re)
         return self.pred_net(_pad_last(x, num_pad).contiguous(), num_pad, re, self.multiplicative_net2)      # (B, X, Y, T, out_dim)

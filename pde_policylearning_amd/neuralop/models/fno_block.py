@@ -7,6 +7,7 @@ import torch.nn.functional as TF
 from torch import nn
 
 from ... import functional as F
+from ... import layer_stack as LS
 from .spectral_convolution import SpectralConv, _unsupported
 
 
@@ -128,6 +129,26 @@ class FNOBlocks(nn.Module):
     def gelu_after(self, index):
         return index < (self.n_layers - index)          # fno_block.py:149
 
+    def pre_activation(self, x, index=0):
+        """conv(x) + skip(x) of one block from this module's own parts (fno_block.py:123-147), before its activation"""
+        y = self.convs(x, index)       # (first: with a channel MLP x has a third use, and autograd sums its gradients in this order)
+        x_skip = self.fno_skips[index](x)
+        if self.convs.output_scaling_factor is not None:
+            x_skip = _resample(x_skip, self.output_scaling_factor[index])
+        return y + x_skip
+
+    ROUTES = (LS.FUSED, LS.TORCH)
+
+    def stack(self, index=None):
+        """the blocks without channel MLPs - or the Fourier part of block `index` alone - as layer_stack describes them"""
+        convs, ls = self.convs, range(self.n_layers) if index is None else (index,)
+        n, modes = len(ls), tuple(convs.half_n_modes)
+        return LS.Stack((self.in_channels,) + (self.out_channels,) * n, lambda x, l: self.pre_activation(x, ls[l]),
+                        F.default_gelu_mask(n) if index is None else 0, spec_ws=lambda l: convs.layer_weights(ls[l]),
+                        uniform=convs.bias is not None and not convs.separable and convs.output_scaling_factor is None,
+                        bias=convs.bias if index is None or convs.bias is None else convs.bias[index:index + 1], norm=self.fft_norm,
+                        skip_ws=[self.fno_skips[l].weight for l in ls], modes=(modes,) * n, wle=(modes[-1],) * n, direct=(False,) * n)
+
     def _forward_mlp(self, x, index):
         """fno_block.py:137-169 with an MLP: u = gelu(conv(x) + skip(x)) on EVERY layer (:147-150), then
         gelu(fcs.1(gelu(fcs.0(u)))) + mlp_skip(x) - the skip takes the block's INPUT (:137) - and a GELU unless this is the
@@ -138,15 +159,10 @@ class FNOBlocks(nn.Module):
         if not F.channel_mlp_supported(x, hidden):
             raise RuntimeError(f"fnoengine FNOBlocks(use_mlp=True): no channel-MLP kernel for input {tuple(x.shape)} {x.dtype} "
                                f"(float32, planes a multiple of 128 elements, (channels, hidden) in {F.CHANNEL_MLP_WIDTHS})")
-        convs = self.convs
-        if convs.bias is not None and not convs.separable and F.blocks_supported(x, 1, convs.half_n_modes, self.fft_norm, 0):
-            # one fused engine layer (spectral convolution + skip + bias, fixed-order weight-gradient reductions).  Its GELU is
-            # a torch operation: the engine's block stacks end without activation unless a projection follows
-            # (fno_model_plan_create), so `gelu_mask=1` on a one-layer stack is refused
-            pre = F.fno_blocks(x, [self.fno_skips[index].weight], convs.layer_weights(index),
-                               convs.bias[index:index + 1].reshape(1, -1), convs.half_n_modes, self.fft_norm, gelu_mask=0)
-        else:
-            pre = convs(x, index) + self.fno_skips[index](x)
+        # one fused engine layer (spectral convolution + skip + bias, fixed-order weight-gradient reductions) where the block
+        # kernels cover the shape.  Its GELU is a torch operation: the engine's block stacks end without activation unless a
+        # projection follows (fno_model_plan_create), so `gelu_mask=1` on a one-layer stack is refused
+        pre = LS.run(x, self.stack(index), self.ROUTES)
         u = self.non_linearity(pre)
         skip = self.mlp_skips[index]
         gate = skip.weight if isinstance(skip, SoftGating) else None
@@ -157,10 +173,7 @@ class FNOBlocks(nn.Module):
         """Unfused composition (one block on its own); FNO.forward uses the fused engine path."""
         if getattr(self, "mlp", None) is not None:      # (modules pickled before the channel MLP existed carry no `mlp`)
             return self._forward_mlp(x, index)
-        x_skip = self.fno_skips[index](x)
-        if self.convs.output_scaling_factor is not None:
-            x_skip = _resample(x_skip, self.output_scaling_factor[index])
-        x = self.convs(x, index) + x_skip
+        x = self.pre_activation(x, index)
         if self.gelu_after(index):
             x = self.non_linearity(x)
         return x

@@ -13,6 +13,7 @@ import torch.nn.functional as TF
 from torch import nn
 
 from ... import functional as F
+from ... import layer_stack as LS
 
 
 class SpectralConv2d(nn.Module):
@@ -79,8 +80,7 @@ class SpectralConvWithFC(nn.Module):
             return F.fno_block_tail(a.contiguous(), self.linear.weight, list(sc.fourier_weight), self.linear.bias.view(1, -1),
                                     (sc.modes1, sc.modes2), sc.norm, relu_out=relu, drop_p=p, seed=seed,
                                     direct_grads=getattr(sc, "_direct_grads", False))
-        s = self.spec_conv(self.dropout(a))
-        return self.activation(F.pointwise_conv_add(a, self.linear.weight, self.linear.bias, addend=s))
+        return self.activation(F.pointwise_conv_add(a, self.linear.weight, self.linear.bias, addend=self.spec_conv(self.dropout(a))))
 
 
 class SpectralRegressor(nn.Module):
@@ -111,14 +111,12 @@ class SpectralRegressor(nn.Module):
         fc1, fc2 = self.regressor[0], self.regressor[2]
         if (x.dim() == 4 and F.pointwise_supported(a)
                 and all(l.in_channels == l.out_channels for l in self.spectral_conv)
-                and isinstance(self.activation, nn.ReLU)
-                and F.projection_supported(a, fc1.out_features, fc2.out_features, "relu")):
-            # whole regressor channels-first on the engine: two pointwise launches + the fused ReLU head
+                and isinstance(self.activation, nn.ReLU) and LS.head_covered(a, fc1, fc2, "relu")):
+            # whole regressor channels-first on the engine (all of it or none): two pointwise launches + the fused ReLU head
             # (hidden (B, X, Y, 256) tensor never materialised; backward recomputes it)
             for layer in self.spectral_conv:
                 a = layer.forward_channels_first(a)
-            y = F.projection_head(a, fc1.weight, fc1.bias, fc2.weight, fc2.bias, act="relu")
-            return y.permute(0, 2, 3, 1)
+            return F.projection_head(a, fc1.weight, fc1.bias, fc2.weight, fc2.bias, act="relu").permute(0, 2, 3, 1)
         for layer in self.spectral_conv:
             x = layer(x)
         return self.regressor(x)
@@ -131,14 +129,13 @@ class FourierLayer2d(nn.Module):
         self.spec_conv = SpectralConv2d(width, width, modes1, modes2, norm='ortho')
         self.norm_conv1d = nn.Conv1d(width, width, 1)
 
+    ROUTES = (LS.FUSED, LS.TORCH)
+
     def forward(self, x):
-        b, c, n1, n2 = x.shape
-        if n1 == n2 and F.blocks_supported(x, 1, (self.spec_conv.modes1, self.spec_conv.modes2), self.spec_conv.norm):
-            # one fused engine layer: spectral conv + Conv1d(k=1) + bias (fno_model_* block stack, L = 1)
-            sc = self.spec_conv
-            return F.fno_blocks(x, [self.norm_conv1d.weight], list(sc.fourier_weight), self.norm_conv1d.bias.view(1, c),
-                                (sc.modes1, sc.modes2), sc.norm, direct_grads=getattr(sc, "_direct_grads", False))
-        return self.spec_conv(x) + self.norm_conv1d(x.reshape(b, c, n1 * n2)).view(b, self.width, n1, n2)
+        # one fused engine layer (fno_model_* block stack, L = 1) on square grids the block kernels cover, else spec_conv + Conv1d
+        sc = self.spec_conv
+        stack = LS.conv_stack([sc], [self.norm_conv1d], None, [(list(sc.fourier_weight), (sc.modes1, sc.modes2), sc.modes2)], sc.norm)
+        return LS.run(x, stack, self.ROUTES if x.shape[-2] == x.shape[-1] else (LS.TORCH,))
 
 
 class RNO_cell(nn.Module):
@@ -263,10 +260,8 @@ class RNO2d(nn.Module):
         b, t, n1, n2, _ = x.shape
         lin = self.input_projection_layer
         xc = x.reshape(b * t, 1, n1, n2)     # in_dim = 1: channels-last == channels-first
-        if not x.requires_grad and F.lifting_supported(xc, self.width):
-            x = F.lifting(xc, lin.weight, lin.bias).view(b, t, self.width, n1, n2)       # engine 1 -> C channel mix
-        else:
-            x = lin(x).permute(0, 1, 4, 2, 3)
+        # engine 1 -> C channel mix for an input that asks for no gradient
+        x = lin(x).permute(0, 1, 4, 2, 3) if x.requires_grad else LS.lift(xc, lin).view(b, t, self.width, n1, n2)
         x = self._pad(x)                     # (B, T, C, X, Y)
         finals = []
         for i, layer in enumerate(self.layers):

@@ -7,6 +7,7 @@ import torch.nn.functional as TF
 from torch import nn
 
 from ... import functional as F
+from ... import layer_stack as LS
 from .fno_block import FNOBlocks
 from .padding import DomainPadding
 from .spectral_convolution import SpectralConv, _unsupported
@@ -101,7 +102,7 @@ class FNO(nn.Module):
         (last dim 32, 64, 128, 256) or "loose rows" (any last dim in 32..320 on planes that tile by 128 pixels: 96 x 96,
         160 x 160, 192 x 192 grids ...; split-precision GEMM mode)."""
         if getattr(self, "domain_padding", None) is not None:
-            return False           # the whole-model plan knows no padding: lifting, pad, block stack, crop, projection (_forward_padded)
+            return False           # the whole-model plan knows no padding: lifting, pad, block stack, crop, projection (forward)
         if self.fno_blocks.convs.separable or self.fno_blocks.convs.output_scaling_factor is not None:
             return False           # torch compositions (SpectralConv._torch_composition): layer by layer
         if getattr(self.fno_blocks, "mlp", None) is not None:
@@ -124,60 +125,23 @@ class FNO(nn.Module):
             # under incremental_n_modes are copies, so that combination takes the composition below)
             return F.fno_model(x, direct_grads=getattr(self, "_direct_grads", False),
                                overlap=getattr(self, "_grad_overlap", None), **self.engine_args())
-        # other widths / grids: spectral convolutions on the engine, pointwise glue in torch
-        if getattr(self, "_direct_grads", False) and torch.is_grad_enabled():
-            # a direct-write bucket does not clear this model's gradients; autograd accumulates on this path, so clear them here
-            for p in self.parameters():
-                if p.grad is not None:
-                    p.grad.zero_()
-        if getattr(self, "domain_padding", None) is not None:      # (modules pickled before the option existed have no such attribute)
-            return self._forward_padded(x)
-        if getattr(self.fno_blocks, "mlp", None) is not None:
-            return self._forward_mlp(x)
-        x = self.lifting(x)
-        for l in range(self.n_layers):
-            x = self.fno_blocks(x, l)
-        return self.projection(x)
-
-    def _lift(self, x):
-        if F.lifting_supported(x, self.hidden_channels):
-            return F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
-        return self.lifting(x)
-
-    def _project(self, x):
-        prj = self.projection
-        if F.projection_supported(x, self.projection_channels, self.out_channels):
-            return F.projection_head(x, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
-        return prj(x)
-
-    def _forward_mlp(self, x):
-        """The layer loop of a model with channel MLPs: lifting and projection head on their engine kernels where those cover
-        the shape, the torch modules otherwise; every block is one fused Fourier layer + one channel-MLP kernel."""
-        F._require_cuda(x, "x")
-        x = self._lift(x)
-        for l in range(self.n_layers):
-            x = self.fno_blocks(x, l)
-        return self._project(x)
-
-    def _forward_padded(self, x):
-        """tfno.py:195-211 with domain padding: lifting, zero-pad (k_domain_pad), the blocks on the extended grid, crop
-        (k_domain_crop), projection.  The blocks are one fused engine stack where the block kernels cover the PADDED grid
-        (functional.blocks_supported), else the per-layer composition; with channel MLPs the layer loop of _forward_mlp.
-        Every gradient goes through autograd (forward() has cleared a direct-write bucket's gradients)."""
-        F._require_cuda(x, "x")
-        blk, convs = self.fno_blocks, self.fno_blocks.convs
-        x = self.domain_padding.pad(self._lift(x))
-        gelu_mask = F.default_gelu_mask(self.n_layers)
-        if (getattr(blk, "mlp", None) is None and convs.bias is not None and not convs.separable
-                and convs.output_scaling_factor is None
-                and F.blocks_supported(x, self.n_layers, convs.half_n_modes, self.fft_norm, gelu_mask)):
-            spec_ws = [w for l in range(self.n_layers) for w in convs.layer_weights(l)]
-            x = F.fno_blocks(x, [blk.fno_skips[l].weight for l in range(self.n_layers)], spec_ws,
-                             convs.bias.reshape(self.n_layers, -1), convs.half_n_modes, self.fft_norm, gelu_mask=gelu_mask)
-        else:
+        # other widths / grids, domain padding (tfno.py:195-211), channel MLPs: every gradient through autograd.  Without
+        # padding and MLPs lifting and projection are torch modules and the blocks take the last rung
+        LS.clear_direct_grads(self)
+        pad = getattr(self, "domain_padding", None)      # (modules pickled before the option existed have no such attribute)
+        mlp = getattr(self.fno_blocks, "mlp", None) is not None
+        engine = pad is not None or mlp
+        if engine:
+            F._require_cuda(x, "x")
+        x = LS.lift(x, self.lifting.fc) if engine else self.lifting(x)
+        x = x if pad is None else pad.pad(x)
+        if mlp:                                # blocks with a channel MLP route their own Fourier part (FNOBlocks._forward_mlp)
             for l in range(self.n_layers):
-                x = blk(x, l)
-        return self._project(self.domain_padding.unpad(x))
+                x = self.fno_blocks(x, l)
+        else:
+            x = LS.run(x, self.fno_blocks.stack(), self.fno_blocks.ROUTES if engine else (LS.TORCH,))
+        x = x if pad is None else pad.unpad(x)
+        return LS.head(x, self.projection.fc1, self.projection.fc2) if engine else self.projection(x)
 
 
 class FNO2d(FNO):
@@ -267,54 +231,23 @@ class FNO1d(FNO):
         pad = getattr(self, "domain_padding", None)
         return n if pad is None else pad.padded_resolution((n,))[0]
 
-    def _covered(self, x, modes, gelu_in):
-        """whether the 1-D kernels take this input; decided once per (shape, device, kept bins) - the probe needs a tensor of
-        the hidden shape, which a forward pass should not allocate every time"""
-        key = (tuple(x.shape), x.device, modes)
-        seen = self.__dict__.setdefault("_covered_shapes", {})
-        if key not in seen:
-            ok = x.dim() == 3 and x.shape[1] == self.in_channels
-            if ok:
-                u = x.new_empty((x.shape[0], self.hidden_channels, self._hidden_length(x.shape[2])))
-                ok = all(F.spectral_layer_supported(u, 1, modes, self.fft_norm, modes[0], g) for g in set(gelu_in))
-            seen[key] = ok
-        return seen[key]
+    ROUTES = (LS.CHAIN,)
 
     def forward(self, x):
         F._require_cuda(x, "x")
-        blk, convs, c = self.fno_blocks, self.fno_blocks.convs, self.hidden_channels
-        modes = tuple(convs.half_n_modes)
-        gelu_in = [l > 0 and blk.gelu_after(l - 1) for l in range(self.n_layers)]
+        stack = self.fno_blocks.stack()
         pad = getattr(self, "domain_padding", None)      # (modules pickled before the option existed have no such attribute)
-        if not self._covered(x, modes, gelu_in):
+        ok = x.dim() == 3 and x.shape[1] == self.in_channels
+        if not (ok and LS.route(LS.probe(x, self.hidden_channels, (self._hidden_length(x.shape[2]),)), stack, self.ROUTES)):
             padded = "" if pad is None or x.dim() != 3 else f" padded to N = {self._hidden_length(x.shape[2])}"
-            raise RuntimeError(f"fnoengine FNO1d: no one-dimensional kernel for input {tuple(x.shape)}{padded} with {modes[0]} kept bins "
+            raise RuntimeError(f"fnoengine FNO1d: no one-dimensional kernel for input {tuple(x.shape)}{padded} with {stack.modes[0][0]} kept bins "
                                f"(needs (B, {self.in_channels}, N), N a multiple of 128 in [128, 8192], at most 64 kept bins"
                                f"{'; with domain padding the rule applies to the padded N' if pad is not None else ''})")
-        if getattr(self, "_direct_grads", False) and torch.is_grad_enabled():
-            # a direct-write bucket (trainer.FlatGradBucket(direct_module=...)) does not clear this model's gradients: it
-            # expects the engine to overwrite them.  This forward hands every gradient to autograd, which accumulates into
-            # the bucket's views, so they are cleared here (as FNO.forward does on its layer-by-layer route)
-            for p in self.parameters():
-                if p.grad is not None:
-                    p.grad.zero_()
-        if F.lifting_supported(x, c):
-            u = F.lifting(x, self.lifting.fc.weight, self.lifting.fc.bias)
-        else:
-            u = self.lifting(x)
-        if pad is not None:
-            u = pad.pad(u)
-        for l in range(self.n_layers):
-            u = F.spectral_pointwise_layer(u, convs.layer_weights(l), modes, self.fft_norm, blk.fno_skips[l].weight,
-                                           convs.bias[l].reshape(-1), input_gelu=gelu_in[l])
-        if blk.gelu_after(self.n_layers - 1):          # only a one-layer stack ends on an activation (fno_block.py:149)
-            u = self.non_linearity(u)
-        if pad is not None:
-            u = pad.unpad(u)
-        prj = self.projection
-        if F.projection_supported(u, self.projection_channels, self.out_channels):
-            return F.projection_head(u, prj.fc1.weight, prj.fc1.bias, prj.fc2.weight, prj.fc2.bias)
-        return prj(u)
+        LS.clear_direct_grads(self)           # this forward hands every gradient to autograd (as FNO.forward's layer routes do)
+        u = LS.lift(x, self.lifting.fc)
+        u = LS.run(u if pad is None else pad.pad(u), stack, self.ROUTES)      # (only a one-layer stack ends on an activation)
+        u = u if pad is None else pad.unpad(u)
+        return LS.head(u, self.projection.fc1, self.projection.fc2)
 
 
 def _with_defaults(new_name, cls, **defaults):

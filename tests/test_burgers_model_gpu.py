@@ -68,9 +68,9 @@ def test_golden_models(dev, case):  # noqa: F811
     p, x = K.golden_params(GM), K.model_input("pino_fno2d_small")
     model = build(dev, p, pad_ratio=pad)
     got, records, calls = evaluate(model, x, dev)
-    assert_route(records, calls, engine=model._engine_covers(x.to(dev)))
+    assert_route(records, calls, engine=model.route(x.to(dev)) == "chain")
     if case == "pad0":
-        assert model._engine_covers(x.to(dev)), "the unpadded (12, 32) grid is covered by the lifting and layer kernels"
+        assert model.route(x.to(dev)) == "chain", "the unpadded (12, 32) grid is covered by the lifting and layer kernels"
     ref64 = K.model_reference(p, x, K.MODES1, K.MODES2, pad, "gelu", torch.float64)
     own32 = K.model_reference(p, x, K.MODES1, K.MODES2, pad, "gelu", torch.float32)
     # the yardstick is the reference's own float32 run; its spectral gradients are stored for the first GOLDEN_CIN input
@@ -101,7 +101,7 @@ def test_mixed_routes(dev, variant):  # noqa: F811
     model.load_state_dict(p)
     x = K.model_input("fno2d." + variant)
     got, records, calls = evaluate(model, x, dev)
-    assert not model._engine_covers(x.to(dev))
+    assert model.route(x.to(dev)) == "torch"
     assert_route(records, calls, engine=False)
     act = kw.get("act", "gelu")
     ref64 = K.model_reference(p, x, K.MODES1, K.MODES2, [0., 0.], act, torch.float64)

@@ -44,7 +44,7 @@ def test_fno2d_on_an_odd_grid(dev, case):  # noqa: F811
         names = [n for n, _ in model.named_parameters()]
         grads = torch.autograd.grad(y.square().sum(), [q for _, q in model.named_parameters()])
         torch.cuda.synchronize()
-    assert not model._engine_covers(x.to(dev))
+    assert model.route(x.to(dev)) == "torch"
     assert_mixed(log.records, case)
     got = {"y": y.detach().cpu(), **{"grad " + n: g.cpu() for n, g in zip(names, grads)}}
     ref64 = KB.model_reference(p, x, K.MODES, K.MODES, pad, "gelu", torch.float64)

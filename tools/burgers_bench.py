@@ -164,7 +164,7 @@ def bench_step(dev, blocks, iters, lines):
     torch.manual_seed(0)
     me = FNO2d(modes1=MODES, modes2=MODES, layers=LAYERS, fc_dim=128, in_dim=3).to(dev)
     mt = copy.deepcopy(me)
-    lines.append(f"  step: the engine covers lifting and layers at this shape: {me._engine_covers(x)}")
+    lines.append(f"  step: the engine covers lifting and layers at this shape: {me.route(x) == 'chain'}")
     with torch.no_grad():
         lines.append(f"  step: model output, engine vs torch composition on the same parameters: rel L2 {rel(me(x), torch_model(mt, x)):.3e}")
     oe, ot = torch.optim.Adam(me.parameters(), lr=1e-3), torch.optim.Adam(mt.parameters(), lr=1e-3)

@@ -3,6 +3,7 @@ GPU box: python tools/fuzz_fused.py [n_cases]"""
 import os, sys, random
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from pde_policylearning_amd import layer_stack as LS
 from pde_policylearning_amd.neuralop.models import FNO2d, FNO3d
 
 dev = torch.device("cuda", 0)
@@ -32,13 +33,9 @@ for case in range(n):
     dy = torch.randn((B, cout) + dims, device=dev)
     def run(fused):
         for p in model.parameters(): p.grad = None
-        if not fused:
-            orig = model.fused_supported
-            model.fused_supported = lambda *_: False
-        try:
-            y = model(x); y.backward(dy)
-        finally:
-            if not fused: model.fused_supported = orig
+        # unfused: the model's plain composition (torch lifting and projection, the blocks on layer_stack's last rung)
+        y = model(x) if fused else model.projection(LS.run(model.lifting(x), model.fno_blocks.stack(), (LS.TORCH,)))
+        y.backward(dy)
         return [y.detach().clone()] + [p.grad.clone() for p in model.parameters()]
     try:
         a, b = run(True), run(False)
