@@ -344,6 +344,33 @@ int fno_darcy_loss_backward(int batch, int S, const float* out, const float* mol
                             const float* g_data, const float* g_f, float* dout, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Sobolev (H1) and L2 training losses of neuralop: LpLoss (p = 2) and H1Loss, neuralop/training/losses.py:62-277.
+ *   x, y (planes, dims[0] .. dims[d-1]) fp32 contiguous, d = 1, 2 or 3 grid axes, a plane = one (batch, channel) index;
+ *   e = x - y;  D_k v[i] = (v[i+1] - v[i-1]) / (2 h_k) with indices mod dims[k] (torch.roll); where bit k of fix_mask is set
+ *   (fix_x_bnd is bit 0) rows 0 and dims[k]-1 are (v[1] - v[0]) / h_k and (v[n-1] - v[n-2]) / h_k instead;
+ *   num = sum e^2 + [order 1] sum_k sum (D_k e)^2,  den = the same of y, per plane, float64 in a fixed order;
+ *   value[plane] = relative ? sqrt(num / den) : sqrt(vol * num), vol = prod h_k  (order 0 is LpLoss, order 1 H1Loss).
+ * The host passes inv2h[k] = 1 / (2 h_k), invh[k] = 1 / h_k (HOST arrays of d doubles, like dims) and vol, all float64.
+ * batch_reduce 0: none.  1 / 2: the planes are a (planes / channels, channels) layout and reduced[c] is the sum / mean of
+ * value[b, c] over b in a fixed order (`reduced` (channels) is required then and `channels` must divide planes).
+ * forward leaves the per-workgroup partial sums and (num, den) per plane in `ws` (fno_sobolev_loss_workspace_bytes; float64
+ * data only); backward reads (num, den) and writes dx = s (e + sum_k D_k^T D_k e) into all of x's extent, s = g / sqrt(num den)
+ * or g sqrt(vol) / sqrt(num), g = grad[plane] without a batch reduction, grad[plane % channels] (times 1 / batch for the
+ * mean) with one.  A plane whose num is exactly zero gets a zero gradient (the reference's autograd gives NaN there); the
+ * forward value follows IEEE (den = 0: inf or NaN).  y is data and gets no gradient.
+ * FNO_EINVAL: d outside 1..3, an extent < 2, planes < 1, order / relative outside 0..1, fix_mask outside d bits, an unknown
+ * batch_reduce, channels not dividing planes, a null required pointer, a short workspace.  FNO_EUNSUPPORTED: a plane of 2^31
+ * elements or more.  All of it is decided before anything is launched and needs no GPU; workspace_bytes returns 0 there.
+ * ---------------------------------------------------------------------- */
+size_t fno_sobolev_loss_workspace_bytes(int planes, int d, const int* dims, int order);
+int fno_sobolev_loss_forward(int planes, int channels, int d, const int* dims, int order, int relative, int fix_mask,
+                             int batch_reduce, const double* inv2h, const double* invh, double vol, const float* x,
+                             const float* y, float* value, float* reduced, void* ws, size_t ws_bytes, void* stream);
+int fno_sobolev_loss_backward(int planes, int channels, int d, const int* dims, int order, int relative, int fix_mask,
+                              int batch_reduce, const double* inv2h, const double* invh, double vol, const float* x,
+                              const float* y, const float* grad, float* dx, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Gates of the recurrent neural operator cell, neuralop/models/rno.py:254-260 (all tensors (B, C, X, Y) fp32,
  * n elements, 16-byte aligned, n % 4 == 0; b* are the cell's SCALAR biases on the device):
  *   reset gate : r = sigmoid(a3 + a4 + b2), rh = r * h                                   (:256-257)

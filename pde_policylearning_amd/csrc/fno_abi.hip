@@ -37,6 +37,7 @@
 #include "k_pino_loss2.h"
 #include "k_burgers_loss.h"
 #include "k_darcy_loss.h"
+#include "k_sobolev_loss.h"
 #include "k_rno_gates.h"
 #include "k_train.h"
 
@@ -2461,6 +2462,129 @@ extern "C" int fno_darcy_loss_backward(int B, int S, const float* out, const flo
   DarcyArgs d = darcy_args(B, S, out, mol, a, y, w);
   d.g_data = g_data; d.g_f = g_f; d.dout = dout;
   return launch("k_darcy_bwd", k_darcy_bwd, dim3((unsigned)(B * d.tiles * d.tiles)), dim3(DARCY_NT), 0, (hipStream_t)stream, d);
+}
+
+// ===========================================================================
+// Sobolev (H1) and L2 training losses of neuralop (k_sobolev_loss.h): LpLoss (p = 2) and H1Loss, neuralop/training/losses.py:62-277
+// ===========================================================================
+struct SobGeom { int D, n[3], c[3], per, seg; size_t plane; };
+static int sob_check(int planes, int channels, int d, const int* dims, int order, int relative, int fix_mask, int batch_reduce,
+                     SobGeom* out) {
+  if (d < 1 || d > 3) return fail(FNO_EINVAL, "sobolev loss: d=%d (1, 2 or 3 grid axes)", d);
+  if (!dims) return fail(FNO_EINVAL, "sobolev loss: dims is null");
+  for (int k = 0; k < d; ++k)
+    if (dims[k] < 2) return fail(FNO_EINVAL, "sobolev loss: extent %d of grid axis %d (at least 2)", dims[k], k);
+  if (planes < 1) return fail(FNO_EINVAL, "sobolev loss: planes=%d (at least 1)", planes);
+  if (order != 0 && order != 1) return fail(FNO_EINVAL, "sobolev loss: order=%d (0: Lp, 1: H1)", order);
+  if (relative != 0 && relative != 1) return fail(FNO_EINVAL, "sobolev loss: relative=%d (0 or 1)", relative);
+  if (fix_mask < 0 || fix_mask >= (1 << d)) return fail(FNO_EINVAL, "sobolev loss: fix_mask=%d (one bit per grid axis, d=%d)", fix_mask, d);
+  if (batch_reduce != SOB_REDUCE_NONE && batch_reduce != SOB_REDUCE_SUM && batch_reduce != SOB_REDUCE_MEAN)
+    return fail(FNO_EINVAL, "sobolev loss: batch_reduce=%d (0 none, 1 sum, 2 mean)", batch_reduce);
+  if (batch_reduce != SOB_REDUCE_NONE && (channels < 1 || planes % channels != 0))
+    return fail(FNO_EINVAL, "sobolev loss: channels=%d does not divide planes=%d (the batch reduction takes a (B, C) layout)", channels,
+                planes);
+  SobGeom g;
+  g.plane = 1;
+  for (int k = 0; k < d; ++k) g.plane *= (size_t)dims[k];
+  if (g.plane >= 0x80000000ull)
+    return fail(FNO_EUNSUPPORTED, "sobolev loss: a plane of %zu elements (fewer than 2^31)", g.plane);
+  g.D = order ? d : 1;
+  for (int k = 0; k < 3; ++k) { g.n[k] = 1; g.c[k] = 1; }
+  if (order) {
+    for (int k = 0; k < d; ++k) g.n[3 - d + k] = dims[k];
+    const int t[3] = {d == 3 ? SOB_T3D_Z : 1, d == 3 ? SOB_T3D_Y : d == 2 ? SOB_T2D_Y : 1,
+                      d == 3 ? SOB_T3D_X : d == 2 ? SOB_T2D_X : SOB_T1D_X};
+    for (int k = 0; k < 3; ++k) g.c[k] = (g.n[k] + t[k] - 1) / t[k];
+  } else {
+    g.n[2] = (int)g.plane;
+    g.c[2] = (g.n[2] + SOB_T0 - 1) / SOB_T0;
+  }
+  const size_t per = (size_t)g.c[0] * g.c[1] * g.c[2];
+  if (per * (size_t)planes > 0x7fffffffull)
+    return fail(FNO_EUNSUPPORTED, "sobolev loss: planes=%d times %zu tiles exceeds the grid limit", planes, per);
+  g.per = (int)per;
+  g.seg = 1;
+  while (g.seg < g.per && g.seg < 64) g.seg <<= 1;
+  if (out) *out = g;
+  return FNO_OK;
+}
+struct SobWs { double *part, *stats; size_t total; bool ok; };
+static SobWs carve_sobolev(int planes, const SobGeom& g, void* ws, size_t ws_bytes) {
+  Carver c(ws, ws_bytes);
+  SobWs w;
+  w.part = c.take<double>((size_t)planes * g.per * 2);
+  w.stats = c.take<double>((size_t)planes * 2);
+  w.total = c.off;
+  w.ok = c.ok;
+  return w;
+}
+extern "C" size_t fno_sobolev_loss_workspace_bytes(int planes, int d, const int* dims, int order) {
+  SobGeom g;
+  if (sob_check(planes, 1, d, dims, order, 0, 0, SOB_REDUCE_NONE, &g) != FNO_OK) return 0;
+  return carve_sobolev(planes, g, nullptr, 0).total;
+}
+static SobolevArgs sobolev_args(const SobGeom& g, int planes, int channels, int d, int relative, int fix_mask, int batch_reduce,
+                                const double* inv2h, const double* invh, double vol, const float* x, const float* y,
+                                const SobWs& w) {
+  SobolevArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.part = w.part; a.stats = w.stats;
+  for (int k = 0; k < 3; ++k) { a.n[k] = g.n[k]; a.c[k] = g.c[k]; a.inv2h[k] = 0.f; a.invh[k] = 0.f; }
+  for (int k = 0; k < d; ++k) {
+    a.fix[3 - d + k] = (fix_mask >> k) & 1;
+    a.inv2h[3 - d + k] = (float)inv2h[k];
+    a.invh[3 - d + k] = (float)invh[k];
+  }
+  a.per = g.per;
+  a.relative = relative; a.reduce = batch_reduce;
+  a.channels = batch_reduce == SOB_REDUCE_NONE ? 1 : channels;
+  a.batch = batch_reduce == SOB_REDUCE_NONE ? 1 : planes / channels;
+  a.vol = vol;
+  return a;
+}
+extern "C" int fno_sobolev_loss_forward(int planes, int channels, int d, const int* dims, int order, int relative, int fix_mask,
+                                        int batch_reduce, const double* inv2h, const double* invh, double vol, const float* x,
+                                        const float* y, float* value, float* reduced, void* ws, size_t ws_bytes, void* stream) {
+  SobGeom g;
+  LAUNCHCHK(sob_check(planes, channels, d, dims, order, relative, fix_mask, batch_reduce, &g));
+  if (!x || !y || !value || !ws || !inv2h || !invh || (batch_reduce != SOB_REDUCE_NONE && !reduced))
+    return fail(FNO_EINVAL, "fno_sobolev_loss_forward: null argument");
+  SobWs w = carve_sobolev(planes, g, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_EINVAL, "fno_sobolev_loss_forward: workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  SobolevArgs a = sobolev_args(g, planes, channels, d, relative, fix_mask, batch_reduce, inv2h, invh, vol, x, y, w);
+  const dim3 grid((unsigned)((size_t)planes * g.per)), blk(SOB_NT);
+  if (!order) LAUNCHCHK(launch("k_sobolev_fwd", k_sobolev_fwd<1, 0>, grid, blk, 0, st, a));
+  else if (d == 1) LAUNCHCHK(launch("k_sobolev_fwd", k_sobolev_fwd<1, 1>, grid, blk, 0, st, a));
+  else if (d == 2) LAUNCHCHK(launch("k_sobolev_fwd", k_sobolev_fwd<2, 1>, grid, blk, 0, st, a));
+  else LAUNCHCHK(launch("k_sobolev_fwd", k_sobolev_fwd<3, 1>, grid, blk, 0, st, a));
+  SobolevFinish f;
+  memset(&f, 0, sizeof(f));
+  f.part = w.part; f.stats = w.stats; f.value = value; f.reduced = reduced;
+  f.planes = planes; f.per = g.per; f.seg = g.seg;
+  f.relative = relative; f.reduce = batch_reduce; f.batch = a.batch; f.vol = vol;
+  const int nseg = SOB_NT / g.seg;
+  unsigned groups;
+  if (batch_reduce == SOB_REDUCE_NONE) { f.cnt = nseg; f.gstride = nseg; f.jstride = 1; groups = (unsigned)((planes + nseg - 1) / nseg); }
+  else { f.cnt = a.batch; f.gstride = 1; f.jstride = channels; groups = (unsigned)channels; }
+  return launch("k_sobolev_finish", k_sobolev_finish, dim3(groups), blk, 0, st, f);
+}
+extern "C" int fno_sobolev_loss_backward(int planes, int channels, int d, const int* dims, int order, int relative, int fix_mask,
+                                         int batch_reduce, const double* inv2h, const double* invh, double vol, const float* x,
+                                         const float* y, const float* grad, float* dx, void* ws, size_t ws_bytes, void* stream) {
+  SobGeom g;
+  LAUNCHCHK(sob_check(planes, channels, d, dims, order, relative, fix_mask, batch_reduce, &g));
+  if (!x || !y || !grad || !dx || !ws || !inv2h || !invh) return fail(FNO_EINVAL, "fno_sobolev_loss_backward: null argument");
+  SobWs w = carve_sobolev(planes, g, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_EINVAL, "fno_sobolev_loss_backward: workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  SobolevArgs a = sobolev_args(g, planes, channels, d, relative, fix_mask, batch_reduce, inv2h, invh, vol, x, y, w);
+  a.grad = grad; a.dx = dx;
+  const dim3 grid((unsigned)((size_t)planes * g.per)), blk(SOB_NT);
+  if (!order) return launch("k_sobolev_bwd", k_sobolev_bwd<1, 0>, grid, blk, 0, st, a);
+  if (d == 1) return launch("k_sobolev_bwd", k_sobolev_bwd<1, 1>, grid, blk, 0, st, a);
+  if (d == 2) return launch("k_sobolev_bwd", k_sobolev_bwd<2, 1>, grid, blk, 0, st, a);
+  return launch("k_sobolev_bwd", k_sobolev_bwd<3, 1>, grid, blk, 0, st, a);
 }
 
 // ===========================================================================

@@ -12,6 +12,7 @@ Two helpers carry that ("The Python bridge"):
 Every forward / backward below reads: check operands, allocate, call.
 """
 import ctypes as C
+import functools
 import math
 import typing
 import weakref
@@ -1053,6 +1054,90 @@ def darcy_residual(u, a, mollifier=None):
     u_c, _, _, _, _, ws, _ = _darcy_forward("darcy_residual", u.detach(), a, None, mollifier)
     B, S, _ = u_c.shape
     return ws[:4 * B * (S - 4) * (S - 4)].view(torch.float32).reshape(B, S - 4, S - 4)
+
+
+# ----------------------------------------------------------------------------
+# Sobolev (H1) and L2 training losses of neuralop (LpLoss p = 2, H1Loss: neuralop/training/losses.py:62-277)
+# ----------------------------------------------------------------------------
+SOBOLEV_REDUCE = {None: 0, "sum": 1, "mean": 2}        # csrc/k_sobolev_loss.h SOB_REDUCE_*
+
+
+def sobolev_loss_supported(x, d):
+    """what k_sobolev_loss.h takes: float32 on the GPU, 1 <= d <= 3 trailing grid axes of extent >= 2 each, at least one
+    plane, a plane of fewer than 2^31 elements"""
+    return bool(isinstance(d, int) and 1 <= d <= 3 and x.is_cuda and x.dtype == torch.float32 and x.dim() >= d
+                and all(n >= 2 for n in x.shape[x.dim() - d:]) and math.prod(x.shape[:x.dim() - d]) >= 1
+                and math.prod(x.shape[x.dim() - d:]) < 2 ** 31)
+
+
+@functools.lru_cache(maxsize=256)
+def _sobolev_plan(shape, d, h, order, relative, fix, reduce, squeeze):
+    """The host's part of one configuration, worked out once: (the scalar arguments of both entry points, workspace bytes,
+    planes, channels, shape of the result).  The step factors are float64 here and rounded once by the library."""
+    e = "sobolev_loss"
+    if not isinstance(d, int) or not 1 <= d <= 3 or len(shape) < d:
+        raise _refuse(e, "d", "count 1, 2 or 3 trailing grid axes of `x`", f"d={d}, x of shape {tuple(shape)}")
+    if reduce not in SOBOLEV_REDUCE:
+        raise _refuse(e, "reduce", "be None, 'sum' or 'mean'", repr(reduce))
+    if len(h) != d or len(fix) != d:
+        raise _refuse(e, "h, fix", f"have one entry per grid axis (d={d})", f"h={list(h)}, fix={list(fix)}")
+    lead, grid = shape[:len(shape) - d], shape[len(shape) - d:]
+    if reduce is not None and len(lead) < 1:
+        raise _refuse(e, "reduce", "be None for an input without a leading axis", repr(reduce))
+    planes = math.prod(lead)
+    channels = planes // lead[0] if reduce is not None and lead[0] > 0 else 1
+    dims = (C.c_int * 3)(*grid)
+    hs = [float(v) for v in h]
+    inv2h, invh = (C.c_double * 3)(*[1.0 / (2.0 * v) for v in hs]), (C.c_double * 3)(*[1.0 / v for v in hs])
+    mask = sum(1 << k for k, f in enumerate(fix) if f)
+    scal = (planes, channels, d, dims, int(order), int(bool(relative)), mask, SOBOLEV_REDUCE[reduce], inv2h, invh,
+            float(math.prod(hs)))
+    nws = _lib.lib().fno_sobolev_loss_workspace_bytes(planes, d, dims, int(order))
+    result = tuple(lead if reduce is None else lead[1:])
+    if squeeze:
+        result = tuple(n for n in result if n != 1)
+    return scal, nws, planes, channels, result
+
+
+class _SobolevLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, d, h, order, relative, fix, reduce, squeeze):
+        _require_cuda(x, "x")
+        scal, nws, planes, channels, result = _sobolev_plan(tuple(x.shape), d, h, order, relative, fix, reduce, squeeze)
+        x_c = x.contiguous()
+        y_c = _operand("sobolev_loss", "y", y, x, shape=x.shape)
+        ws = _bytes(nws, x.device)
+        out = torch.empty(planes + channels, dtype=torch.float32, device=x.device)
+        value, reduced = out[:planes], out[planes:]
+        _call("sobolev_loss_forward", x.device, "fno_sobolev_loss_forward", *scal, x_c, y_c, value,
+              None if reduce is None else reduced, ws, nws, STREAM)
+        ctx.save_for_backward(x_c, y_c, ws)
+        ctx.meta = (scal, nws, x.shape, channels if reduce else planes)
+        return (value if reduce is None else reduced).view(result)
+
+    @staticmethod
+    def backward(ctx, g):
+        x_c, y_c, ws = ctx.saved_tensors
+        scal, nws, shape, ngrad = ctx.meta
+        grad = _operand("sobolev_loss backward", "grad", g.to(torch.float32), x_c, numel=ngrad)
+        dx = torch.empty_like(x_c)
+        _call("sobolev_loss_backward", dx.device, "fno_sobolev_loss_backward", *scal, x_c, y_c, grad, dx, ws, nws, STREAM)
+        return dx.view(shape), None, None, None, None, None, None, None, None
+
+
+def sobolev_loss(x, y, d, h, order=1, relative=True, fix=None, reduce=None, squeeze=False):
+    """LpLoss (order 0, p = 2) / H1Loss (order 1) of neuralop/training/losses.py in one fused forward (two launches) and one
+    backward launch.  x, y (*lead, n_1 .. n_d) float32 on the GPU, h the d step sizes, fix the d per-axis flags of a
+    non-periodic axis (fix_x_bnd first; default all periodic).  relative: sqrt(num / den), else sqrt(prod(h) num).
+    reduce None: the per-plane tensor `lead`; 'sum' / 'mean': reduced over the FIRST leading axis inside the engine, shape
+    lead[1:]; squeeze: without the result's singleton axes (the reference's `.squeeze()`).  Differentiable w.r.t. x
+    (non-contiguous inputs are copied); y is data.  A plane with x == y exactly gets a zero gradient (the reference's autograd
+    gives NaN there)."""
+    if y.requires_grad:
+        raise _refuse("sobolev_loss", "y", "be data (the loss is differentiated with respect to `x` only)", "requires_grad=True")
+    fix = (False,) * d if fix is None and isinstance(d, int) else fix
+    return _SobolevLossFn.apply(x, y, d, tuple(float(v) for v in h), int(order), bool(relative), tuple(bool(f) for f in fix),
+                                reduce, bool(squeeze))
 
 
 # ----------------------------------------------------------------------------
