@@ -371,6 +371,33 @@ int fno_sobolev_loss_backward(int planes, int channels, int d, const int* dims, 
                               const float* y, const float* grad, float* dx, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Spectral Sobolev loss of the original FNO code base: HsLoss, libs/utilities3.py:339-405.
+ *   x, y (batch, nx, ny, channels) fp32 contiguous, channels LAST; e = x - y, E = fft2(e), Y = fft2(y) per (sample, channel)
+ *   plane; r2 = kx^2 + ky^2 of the absolute wave numbers |k|, k = [0 .. n/2-1, -n/2 .. -1] (the Nyquist index carries n/2);
+ *   num_j = w2[j] sum_{kx,ky,c} r2^j |E|^2,  den_j = w2[j] sum r2^j |Y|^2,  j < terms (w2: a HOST array of `terms` doubles,
+ *   the squared coefficients 1, a[0]^2, a[1]^2 of |k|^0, |k|^2, |k|^4), float32 per bin, float64 sums in a fixed order;
+ *   group 0: value[b] = sqrt(sum_j num_j) / sqrt(sum_j den_j);  group 1: value[b] = (sum_j sqrt(num_j) / sqrt(den_j)) / divisor
+ *   (the reference divides by k + 1 whatever the number of terms; `divisor` is read with group 1 only).
+ * reduce 0: none.  1 / 2: reduced[0] is the sum / mean of value[b] over b in a fixed order (`reduced` is required then).
+ * forward leaves the per-workgroup sums and (num_j, den_j) per sample in `ws` (fno_hs_loss_workspace_bytes; float64 data only);
+ * backward reads them and writes dx = d(sum_b g_b value[b]) / dx into all of x's extent, g_b = grad[b] without a reduction,
+ * grad[0] (times 1 / batch for the mean) with one.  A term whose num_j is exactly zero (group 0: a sample whose sum is)
+ * contributes a zero gradient (the reference's autograd gives NaN there); the forward value follows IEEE (den = 0: inf or NaN).
+ * y is data and gets no gradient.
+ * FNO_EINVAL: nx != ny or outside {32, 64, 128}, batch or channels < 1, terms outside 1..3, group outside 0..1, a grouped
+ * divisor that is not positive, an unknown reduce, a null required pointer, a short workspace.  FNO_EUNSUPPORTED: batch times
+ * ceil(channels / 2) workgroups beyond the grid limit of 2^31 - 1.  All of it is decided before anything is launched and needs
+ * no GPU; workspace_bytes returns 0 for batch or channels < 1 and beyond that limit.
+ * ---------------------------------------------------------------------- */
+size_t fno_hs_loss_workspace_bytes(int batch, int channels);
+int fno_hs_loss_forward(int batch, int nx, int ny, int channels, int terms, const double* w2, int group, double divisor,
+                        int reduce, const float* x, const float* y, float* value, float* reduced, void* ws, size_t ws_bytes,
+                        void* stream);
+int fno_hs_loss_backward(int batch, int nx, int ny, int channels, int terms, const double* w2, int group, double divisor,
+                         int reduce, const float* x, const float* y, const float* grad, float* dx, void* ws, size_t ws_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------
  * Gates of the recurrent neural operator cell, neuralop/models/rno.py:254-260 (all tensors (B, C, X, Y) fp32,
  * n elements, 16-byte aligned, n % 4 == 0; b* are the cell's SCALAR biases on the device):
  *   reset gate : r = sigmoid(a3 + a4 + b2), rh = r * h                                   (:256-257)

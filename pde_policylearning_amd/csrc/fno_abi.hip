@@ -38,6 +38,7 @@
 #include "k_burgers_loss.h"
 #include "k_darcy_loss.h"
 #include "k_sobolev_loss.h"
+#include "k_hs_loss.h"
 #include "k_rno_gates.h"
 #include "k_train.h"
 
@@ -2585,6 +2586,91 @@ extern "C" int fno_sobolev_loss_backward(int planes, int channels, int d, const 
   if (d == 1) return launch("k_sobolev_bwd", k_sobolev_bwd<1, 1>, grid, blk, 0, st, a);
   if (d == 2) return launch("k_sobolev_bwd", k_sobolev_bwd<2, 1>, grid, blk, 0, st, a);
   return launch("k_sobolev_bwd", k_sobolev_bwd<3, 1>, grid, blk, 0, st, a);
+}
+
+// ===========================================================================
+// Spectral Sobolev loss of the original FNO code base (k_hs_loss.h): HsLoss, libs/utilities3.py:339-405
+// ===========================================================================
+static int hs_slots(int channels) { return (channels + 1) / 2; }      // a workgroup takes a pair of channels as one complex plane
+static int hs_check(int B, int nx, int ny, int C, int terms, const double* w2, int group, double divisor, int reduce) {
+  if (nx != ny) return fail(FNO_EINVAL, "hs loss: a %d x %d plane (square planes of 32, 64 or 128 points a side)", nx, ny);
+  if (nx != 32 && nx != 64 && nx != 128)
+    return fail(FNO_EINVAL, "hs loss: a %d x %d plane (square planes of 32, 64 or 128 points a side)", nx, ny);
+  if (B < 1) return fail(FNO_EINVAL, "hs loss: batch=%d (at least 1)", B);
+  if (C < 1) return fail(FNO_EINVAL, "hs loss: channels=%d (at least 1)", C);
+  if (terms < 1 || terms > HS_TERMS) return fail(FNO_EINVAL, "hs loss: terms=%d (1 to %d: |k|^0, |k|^2, |k|^4)", terms, HS_TERMS);
+  if (!w2) return fail(FNO_EINVAL, "hs loss: w2 is null");
+  if (group != 0 && group != 1) return fail(FNO_EINVAL, "hs loss: group=%d (0 or 1)", group);
+  if (group && !(divisor > 0.0)) return fail(FNO_EINVAL, "hs loss: divisor=%g of the grouped form (positive: k + 1)", divisor);
+  if (reduce != HS_REDUCE_NONE && reduce != HS_REDUCE_SUM && reduce != HS_REDUCE_MEAN)
+    return fail(FNO_EINVAL, "hs loss: reduce=%d (0 none, 1 sum, 2 mean)", reduce);
+  if ((size_t)B * (size_t)hs_slots(C) > 0x7fffffffull)
+    return fail(FNO_EUNSUPPORTED, "hs loss: batch=%d times %d channel pairs exceeds the grid limit", B, hs_slots(C));
+  return FNO_OK;
+}
+struct HsWs { double *part, *stats; size_t total; bool ok; };
+static HsWs carve_hs(int B, int C, void* ws, size_t ws_bytes) {
+  Carver c(ws, ws_bytes);
+  HsWs w;
+  w.part = c.take<double>((size_t)B * hs_slots(C) * 2 * HS_TERMS);
+  w.stats = c.take<double>((size_t)B * 2 * HS_TERMS);
+  w.total = c.off;
+  w.ok = c.ok;
+  return w;
+}
+extern "C" size_t fno_hs_loss_workspace_bytes(int batch, int channels) {
+  if (batch < 1 || channels < 1 || (size_t)batch * (size_t)hs_slots(channels) > 0x7fffffffull) return 0;
+  return carve_hs(batch, channels, nullptr, 0).total;
+}
+static HsArgs hs_args(int B, int C, int terms, const double* w2, int group, double divisor, int reduce, const float* x,
+                      const float* y, const HsWs& w) {
+  HsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.part = w.part; a.stats = w.stats;
+  a.C = C; a.slots = hs_slots(C); a.terms = terms; a.group = group; a.reduce = reduce; a.batch = B;
+  for (int j = 0; j < terms; ++j) a.w2[j] = w2[j];
+  a.divisor = group ? divisor : 1.0;
+  return a;
+}
+template <int N>
+static int hs_launch_planes(bool backward, hipStream_t st, const HsArgs& a) {
+  const size_t lds = ((size_t)N * (N + 1) + N / 2) * 8 + (size_t)(PinoCfg<N>::NT / 64) * HS_TERMS * 8;
+  const dim3 grid((unsigned)(a.batch * a.slots)), blk(PinoCfg<N>::NT);
+  if (backward) return launch("k_hs_plane_bwd", k_hs_plane_bwd<N>, grid, blk, lds, st, a);
+  return launch("k_hs_plane_fwd", k_hs_plane_fwd<N>, grid, blk, lds, st, a);
+}
+static int hs_planes(bool backward, int n, hipStream_t st, const HsArgs& a) {
+  if (n == 32) return hs_launch_planes<32>(backward, st, a);
+  if (n == 64) return hs_launch_planes<64>(backward, st, a);
+  return hs_launch_planes<128>(backward, st, a);
+}
+extern "C" int fno_hs_loss_forward(int B, int nx, int ny, int C, int terms, const double* w2, int group, double divisor, int reduce,
+                                   const float* x, const float* y, float* value, float* reduced, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  LAUNCHCHK(hs_check(B, nx, ny, C, terms, w2, group, divisor, reduce));
+  if (!x || !y || !value || !ws || (reduce != HS_REDUCE_NONE && !reduced)) return fail(FNO_EINVAL, "fno_hs_loss_forward: null argument");
+  HsWs w = carve_hs(B, C, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_EINVAL, "fno_hs_loss_forward: workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  HsArgs a = hs_args(B, C, terms, w2, group, divisor, reduce, x, y, w);
+  LAUNCHCHK(hs_planes(false, nx, st, a));
+  HsFinish f;
+  memset(&f, 0, sizeof(f));
+  f.part = w.part; f.stats = w.stats; f.value = value; f.reduced = reduced;
+  f.B = B; f.slots = a.slots; f.terms = terms; f.group = group; f.reduce = reduce; f.divisor = a.divisor;
+  for (int j = 0; j < terms; ++j) f.w2[j] = w2[j];
+  return launch("k_hs_finish", k_hs_finish, dim3(1), dim3(HS_FINISH_NT), 0, st, f);
+}
+extern "C" int fno_hs_loss_backward(int B, int nx, int ny, int C, int terms, const double* w2, int group, double divisor, int reduce,
+                                    const float* x, const float* y, const float* grad, float* dx, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  LAUNCHCHK(hs_check(B, nx, ny, C, terms, w2, group, divisor, reduce));
+  if (!x || !y || !grad || !dx || !ws) return fail(FNO_EINVAL, "fno_hs_loss_backward: null argument");
+  HsWs w = carve_hs(B, C, ws, ws_bytes);
+  if (!w.ok) return fail(FNO_EINVAL, "fno_hs_loss_backward: workspace too small: need %zu, have %zu", w.total, ws_bytes);
+  HsArgs a = hs_args(B, C, terms, w2, group, divisor, reduce, x, y, w);
+  a.grad = grad; a.dx = dx;
+  return hs_planes(true, nx, (hipStream_t)stream, a);
 }
 
 // ===========================================================================

@@ -1141,6 +1141,85 @@ def sobolev_loss(x, y, d, h, order=1, relative=True, fix=None, reduce=None, sque
 
 
 # ----------------------------------------------------------------------------
+# spectral Sobolev loss of the original FNO code base (HsLoss: libs/utilities3.py:339-405)
+# ----------------------------------------------------------------------------
+HS_REDUCE = {None: 0, "sum": 1, "mean": 2}        # csrc/k_hs_loss.h HS_REDUCE_*
+HS_GRIDS = (32, 64, 128)                          # square planes the in-LDS transforms of csrc/k_hs_loss.h cover
+HS_TERMS = 3                                      # |k|^0, |k|^2, |k|^4
+
+
+def hs_loss_supported(x):
+    """what k_hs_loss.h takes: float32 on the GPU, (B, N, N, *rest) with N = 32, 64 or 128, at least one sample and one
+    channel (the trailing dimensions fold into one channel axis)"""
+    return bool(x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and x.shape[1] == x.shape[2] and x.shape[1] in HS_GRIDS
+                and x.shape[0] >= 1 and math.prod(x.shape[3:]) >= 1)
+
+
+@functools.lru_cache(maxsize=256)
+def _hs_plan(shape, k, a, group, reduce):
+    """The host's part of one configuration, worked out once: (the scalar arguments of both entry points, workspace bytes,
+    batch).  The squared coefficients are float64 here."""
+    e = "hs_loss"
+    if len(shape) < 3 or shape[1] != shape[2] or shape[1] not in HS_GRIDS:
+        raise _refuse(e, "x", f"be (B, N, N, ...) with a square plane of N = {', '.join(map(str, HS_GRIDS))} points a side "
+                      "(the in-LDS transforms; there is no other path)", f"shape {tuple(shape)}")
+    B, channels = shape[0], math.prod(shape[3:])
+    if B < 1 or channels < 1:
+        raise _refuse(e, "x", "have at least one sample and one channel", f"shape {tuple(shape)}")
+    if not isinstance(k, int) or k < 0:
+        raise _refuse(e, "k", "be a non-negative integer", repr(k))
+    if reduce not in HS_REDUCE:
+        raise _refuse(e, "reduce", "be None, 'sum' or 'mean'", repr(reduce))
+    terms = min(k, HS_TERMS - 1) + 1
+    if len(a) < terms - 1:
+        raise _refuse(e, "a", f"have a coefficient for each of the orders 1 .. {terms - 1}", f"a={list(a)}, k={k}")
+    w2 = (C.c_double * HS_TERMS)(1.0, *[float(v) ** 2 for v in a[:terms - 1]])
+    scal = (B, shape[1], shape[2], channels, terms, w2, int(group), float(k + 1), HS_REDUCE[reduce])
+    return scal, _lib.lib().fno_hs_loss_workspace_bytes(B, channels), B
+
+
+class _HsLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, k, a, group, reduce):
+        scal, nws, B = _hs_plan(tuple(x.shape), k, a, group, reduce)
+        _require_cuda(x, "x")
+        x_c = x.contiguous()
+        y_c = _operand("hs_loss", "y", y, x, shape=x.shape)
+        ws = _bytes(nws, x.device)
+        out = torch.empty(B + 1, dtype=torch.float32, device=x.device)
+        value, reduced = out[:B], out[B:]
+        _call("hs_loss_forward", x.device, "fno_hs_loss_forward", *scal, x_c, y_c, value, None if reduce is None else reduced,
+              ws, nws, STREAM)
+        ctx.save_for_backward(x_c, y_c, ws)
+        ctx.meta = (scal, nws, x.shape, B if reduce is None else 1)
+        return value if reduce is None else reduced.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        x_c, y_c, ws = ctx.saved_tensors
+        scal, nws, shape, ngrad = ctx.meta
+        grad = _operand("hs_loss backward", "grad", g.to(torch.float32), x_c, numel=ngrad)
+        dx = torch.empty_like(x_c)
+        _call("hs_loss_backward", dx.device, "fno_hs_loss_backward", *scal, x_c, y_c, grad, dx, ws, nws, STREAM)
+        return dx.view(shape), None, None, None, None, None
+
+
+def hs_loss(x, y, k=1, a=None, group=False, reduce="mean"):
+    """HsLoss of libs/utilities3.py:339-405 in one fused forward (two launches) and one backward launch.  x, y (B, N, N, *rest)
+    float32 on the GPU, channels last, N = 32, 64 or 128; the loss compares them in Fourier space with the weights
+    1 + a[0]^2 |k|^2 + a[1]^2 |k|^4 (orders up to min(k, 2); a defaults to [1] * k); group: the mean of the per-order relative
+    norms over k + 1 instead of one weighted norm.  reduce 'mean' / 'sum': a 0-d tensor, reduced over the batch inside the engine;
+    None: the (B,) values.  Differentiable w.r.t. x (non-contiguous inputs are copied); y is data.  A sample with x == y exactly
+    gets a zero gradient (the reference's autograd gives NaN there).  Any other grid raises: there is no torch fallback."""
+    if y.requires_grad:
+        raise _refuse("hs_loss", "y", "be data (the loss is differentiated with respect to `x` only)", "requires_grad=True")
+    if not isinstance(k, int) or isinstance(k, bool) or k < 0:
+        raise _refuse("hs_loss", "k", "be a non-negative integer", repr(k))
+    a = (1.0,) * k if a is None else a
+    return _HsLossFn.apply(x, y, k, tuple(float(v) for v in a), bool(group), reduce)
+
+
+# ----------------------------------------------------------------------------
 # channel-flow RHS and the physics-informed loss (libs/envs/control_env.py:429-530, 627-633)
 # ----------------------------------------------------------------------------
 class ChannelGrid:
