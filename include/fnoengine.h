@@ -505,6 +505,30 @@ int fno_domain_crop(int ndim, size_t planes, const int* dims, const int* before,
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Device-resident training data (libs/pde_data_loader.py DeviceBatches): a batch assembled from raw snapshots that stay on the
+ * device.  src is a pool of n_src snapshots of snap_elems elements each, float32 (src_dtype 0) or float64 (1), the codes of
+ * fno_chanflow_rhs; idx (count) int64 on the device picks the entries.  For entry e, i < rows, j < cols:
+ *     x = src[idx[e] * snap_elems + offset + i * row_stride + j * col_stride]
+ *     out[e * out_stride + i * cols + j] = (float)((x - mean[i][j]) / (std_[i][j] + eps))
+ * mean, std_ (rows, cols) contiguous of stat_dtype (same codes).  The arithmetic type is the host's promotion of
+ * NormalizerGivenMeanStd.encode: float64 if either dtype is float64, float32 if both are float32; std_ + eps is formed in the
+ * statistics' type (eps rounded to float32 first there, as tensor + python_float does); every operation is rounded once with
+ * a true division, and one last rounding gives the float32.  mean and std_ both NULL: out = (float)x, a gather and cast
+ * (stat_dtype is not read).  The one view covers downsample + crop (row_stride = d * C0, col_stride = d), a plane V[:, p, :]
+ * (offset = p * Nz, row_stride = Ny * Nz), a whole field as a 2-D array, and one plane of a (T, P, X, Z) target (out advanced by
+ * p * X * Z, out_stride = P * X * Z).
+ * Every index is compared unsigned against n_src before it becomes an address: an entry whose index is out of range reads
+ * nothing and its rows * cols outputs are NaN.  One launch, no workspace, no atomics, 64-bit addressing; stores are whole
+ * 16-byte vectors wherever the output's address allows it (tensors need the alignment of their element only).
+ * FNO_EINVAL: a null src / idx / out, exactly one of mean / std_, an unknown dtype, rows or cols < 1, out_stride < rows * cols,
+ * offset + (rows - 1) * row_stride + (cols - 1) * col_stride >= snap_elems, a misaligned tensor; FNO_EUNSUPPORTED: a pool
+ * beyond 2^62 bytes or an output beyond 2^60 floats.  count == 0 succeeds without a launch.  The checks need no GPU.
+ * ---------------------------------------------------------------------- */
+int fno_data_gather(int src_dtype, int stat_dtype, const void* src, size_t n_src, size_t snap_elems, size_t offset,
+                    size_t row_stride, size_t col_stride, int rows, int cols, const long long* idx, size_t count,
+                    const void* mean, const void* std_, double eps, float* out, size_t out_stride, void* stream);
+
+/* ------------------------------------------------------------------------
  * Lifting layer on its own:  y = W x + b,  x (B, Cin <= 4, PW) -> y (B, C, PW), C in {32, 64}, PW % 128 == 0
  * (neuralop/models/tfno.py:11-20; also the `fc0` + Re-conditioning front of the PINO observers,
  * libs/models/pino_models/pinobserver.py:205-207, once its two linear maps are composed).  backward gives the

@@ -31,6 +31,7 @@
 #include "k_projection_h2.h"
 #include "k_channel_mlp.h"
 #include "k_domain_pad.h"
+#include "k_data_gather.h"
 #include "k_spectral_mid.h"
 #include "k_spec1d.h"
 #include "k_pino_loss.h"
@@ -3648,6 +3649,54 @@ extern "C" int fno_domain_pad(int ndim, size_t planes, const int* dims, const in
 extern "C" int fno_domain_crop(int ndim, size_t planes, const int* dims, const int* before, const int* after, const float* y,
                                float* x, void* stream) {
   return dompad_run(false, "fno_domain_crop", ndim, planes, dims, before, after, y, x, stream);
+}
+
+// ===========================================================================
+// Device-resident training data (k_data_gather.h): one strided (rows, cols) view of `count` snapshots picked by index from a
+// pool, normalised (or only cast) and written as float32 planes `out_stride` floats apart.  One launch.
+// ===========================================================================
+template <typename S, bool NORM>
+static int data_gather_launch(const char* tag, int stat_dtype, dim3 grid, hipStream_t st, const DataGatherArgs& a) {
+  LV(tag, 0, (int)std::min<unsigned long long>(a.count, 0x7fffffffull));
+  if constexpr (NORM) {      // (the cast-only kernels read no statistics: one instantiation per snapshot type)
+    if (stat_dtype == 1) return launch("k_data_gather", k_data_gather<S, double, true>, grid, dim3(256), 0, st, a);
+  }
+  return launch("k_data_gather", k_data_gather<S, float, NORM>, grid, dim3(256), 0, st, a);
+}
+extern "C" int fno_data_gather(int src_dtype, int stat_dtype, const void* src, size_t n_src, size_t snap_elems, size_t offset,
+                               size_t row_stride, size_t col_stride, int rows, int cols, const long long* idx, size_t count,
+                               const void* mean, const void* std_, double eps, float* out, size_t out_stride, void* stream) {
+  const char* fn = "fno_data_gather";
+  if (!src || !idx || !out) return fail(FNO_EINVAL, "%s: null argument", fn);
+  if (!mean != !std_) return fail(FNO_EINVAL, "%s: mean and std_ are given together or both NULL", fn);
+  const bool norm = mean != nullptr;
+  if (src_dtype < 0 || src_dtype > 1) return fail(FNO_EINVAL, "%s: src_dtype=%d (0 = float32, 1 = float64)", fn, src_dtype);
+  if (norm && (stat_dtype < 0 || stat_dtype > 1)) return fail(FNO_EINVAL, "%s: stat_dtype=%d (0 = float32, 1 = float64)", fn, stat_dtype);
+  if (rows < 1 || cols < 1) return fail(FNO_EINVAL, "%s: a view of %d x %d elements (at least 1 x 1)", fn, rows, cols);
+  const unsigned long long n = (unsigned long long)rows * (unsigned long long)cols;
+  if (out_stride < n) return fail(FNO_EINVAL, "%s: out_stride %zu is shorter than the %d x %d plane", fn, out_stride, rows, cols);
+  const unsigned __int128 last = (unsigned __int128)offset + (unsigned __int128)(rows - 1) * row_stride + (unsigned __int128)(cols - 1) * col_stride;
+  if (last >= snap_elems)
+    return fail(FNO_EINVAL, "%s: the view (offset %zu, %d rows %zu apart, %d columns %zu apart) leaves a snapshot of %zu elements", fn, offset,
+                rows, row_stride, cols, col_stride, snap_elems);
+  const size_t ssz = src_dtype ? 8 : 4, msz = stat_dtype ? 8 : 4;
+  if ((unsigned __int128)n_src * snap_elems * ssz > ((unsigned __int128)1 << 62) || (unsigned __int128)count * out_stride > ((unsigned __int128)1 << 60))
+    return fail(FNO_EUNSUPPORTED, "%s: at most 2^62 bytes in the pool and 2^60 floats in the output", fn);
+  if (((uintptr_t)src & (ssz - 1)) || ((uintptr_t)idx & 7) || ((uintptr_t)out & 3) || (norm && (((uintptr_t)mean | (uintptr_t)std_) & (msz - 1))))
+    return fail(FNO_EINVAL, "%s: tensor not aligned to its element size", fn);
+  if (count == 0) return FNO_OK;
+  DataGatherArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src; a.idx = idx; a.mean = mean; a.sd = std_; a.out = out;
+  a.n_src = n_src; a.snap_elems = snap_elems; a.offset = offset; a.row_stride = row_stride; a.col_stride = col_stride;
+  a.out_stride = out_stride; a.count = count; a.n = (long long)n; a.cols = cols; a.eps = eps;
+  const dim3 grid((unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((n / 4 + 255) / 256, 1024)),
+                  (unsigned)std::min<size_t>(count, 65535));
+  hipStream_t st = (hipStream_t)stream;
+  if (src_dtype == 1) return norm ? data_gather_launch<double, true>("k_data_gather<f64, norm>", stat_dtype, grid, st, a)
+                                  : data_gather_launch<double, false>("k_data_gather<f64, cast>", 0, grid, st, a);
+  return norm ? data_gather_launch<float, true>("k_data_gather<f32, norm>", stat_dtype, grid, st, a)
+              : data_gather_launch<float, false>("k_data_gather<f32, cast>", 0, grid, st, a);
 }
 
 // ===========================================================================

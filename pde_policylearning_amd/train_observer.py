@@ -31,7 +31,7 @@ from torch.utils.data import DataLoader
 
 from .libs.models.fno_models import FNO2dObserver
 from .libs.models.rno_models import RNO2dObserver
-from .libs.pde_data_loader import FullFieldNSDataset, PDEDataset, SequentialPDEDataset
+from .libs.pde_data_loader import DeviceBatches, FullFieldNSDataset, PDEDataset, SequentialPDEDataset
 from .trainer import (enable_dp_exchange, DevicePrefetcher, FlatGradBucket, FullFieldObjective, FusedAdam, FusedLpLoss, MeanStdDecoder,
                       broadcast_parameters, shard_batch, train_step)
 
@@ -71,6 +71,11 @@ def build_parser():
     ap.add_argument("--graph", action="store_true", help="PINObserverFullField on one GPU: capture the training step of a full "
                     "batch into a hipGraph and replay it (the step is launch-bound: 1.9 vs 2.4 ms at the YAML's sizes); a "
                     "smaller last batch runs eagerly")
+    ap.add_argument("--device-data", dest="device_data", action="store_true", help="keep the folder's raw files on the GPU and "
+                    "assemble every batch there (libs.pde_data_loader.DeviceBatches: the host loader's batches bit for bit, "
+                    "without its per-item work); YAML key device_data; off: DataLoader + DevicePrefetcher as before")
+    ap.add_argument("--device-data-max-gb", dest="device_data_max_gb", type=float, default=8.0,
+                    help="budget of the device-resident pool in GiB; a larger folder raises and the host loader remains the path")
     ap.add_argument("--save-path", default=None, help="whole-module checkpoint written whenever the test rel-L2 improves "
                     "(run_pde_observers.py:307-315: torch.save(observer_model, './outputs/<path>_<exp>.pth'))")
     return ap
@@ -175,6 +180,22 @@ def make_train_loader(train_ds, args, world):
     return loader
 
 
+def make_batch_sources(train_ds, test_ds, train_loader, test_loader, args, dev, rank, world):
+    """(train batches, test batches, whether the train batches still need shard_batch).  Default: DevicePrefetcher over the two
+    host loaders.  device_data: DeviceBatches over one shared pool, in the order of make_train_loader's loader (same shuffle,
+    generator and drop_last; that loader itself is not iterated, so the generator is drawn from once per epoch as before) and
+    already cut to this rank's slice."""
+    if not bool(getattr(args, "device_data", False)):
+        return DevicePrefetcher(train_loader, dev), DevicePrefetcher(test_loader, dev), world > 1
+    from torch.utils.data import RandomSampler
+    max_bytes = int(float(getattr(args, "device_data_max_gb", 8.0) or 8.0) * (1 << 30))
+    train = DeviceBatches(train_ds, args.batch_size, dev, shuffle=isinstance(train_loader.sampler, RandomSampler),
+                          generator=train_loader.generator, drop_last=train_loader.drop_last, rank=rank, world=world,
+                          max_bytes=max_bytes)
+    test = DeviceBatches(test_ds, args.batch_size, dev, shuffle=False, generator=None, max_bytes=max_bytes)
+    return train, test, False
+
+
 def run(args, log=print):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -216,6 +237,7 @@ def run(args, log=print):
     train_ds, test_ds = mk(idx[:args.ntrain].tolist()), mk(idx[-args.ntest:].tolist())
     train_loader = make_train_loader(train_ds, args, world)
     test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, drop_last=False)
+    train_batches, test_batches, shard = make_batch_sources(train_ds, test_ds, train_loader, test_loader, args, dev, rank, world)
     if args.model == "FNO2dObserver":
         model = FNO2dObserver(args.modes, args.modes, args.width, use_v_plane=bool(getattr(args, "use_v_plane", False))).to(dev)
         forward = lambda p: model(p, None)
@@ -243,8 +265,8 @@ def run(args, log=print):
         t0 = time.perf_counter()
         tot = torch.zeros((), device=dev)
         cnt = 0
-        for p_plane, v_plane in DevicePrefetcher(train_loader, dev):
-            if world > 1:
+        for p_plane, v_plane in train_batches:
+            if shard:
                 p_plane, v_plane = shard_batch(p_plane, rank, world), shard_batch(v_plane, rank, world)
             p_plane, tgt = make_batch(p_plane, v_plane)
             tot += train_step(forward, bucket, opt, (p_plane,), tgt, loss_fn)     # :185-193
@@ -255,7 +277,7 @@ def run(args, log=print):
         model.eval()
         test_tot, test_cnt = torch.zeros((), device=dev), 0
         with torch.no_grad():
-            for p_plane, v_plane in DevicePrefetcher(test_loader, dev):
+            for p_plane, v_plane in test_batches:
                 p_plane, tgt = make_batch(p_plane, v_plane)
                 test_tot += loss_fn(forward(p_plane).reshape(tgt.shape), tgt)
                 test_cnt += tgt.shape[0]
@@ -280,6 +302,7 @@ def run_full_field(args, idx, dev, rank, world, log):
     train_ds, test_ds = mk(idx[:args.ntrain]), mk(idx[-args.ntest:])
     train_loader = make_train_loader(train_ds, args, world)
     test_loader = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, drop_last=False)
+    train_batches, test_batches, shard = make_batch_sources(train_ds, test_ds, train_loader, test_loader, args, dev, rank, world)
     P, L = len(args.plane_indexs), 4
     model = PINObserverFullField(plane_num=P, modes1=[args.modes] * L, modes2=[args.modes] * L, modes3=[args.modes] * L,
                                  fc_dim=128, layers=[getattr(args, "fullfield_width", None) or args.width] * (L + 1), in_dim=1, out_dim=1, act="gelu",
@@ -311,8 +334,8 @@ def run_full_field(args, idx, dev, rank, world, log):
         model.train()
         t0 = time.perf_counter()
         tot, cnt = torch.zeros((), device=dev), 0
-        for batch in DevicePrefetcher(train_loader, dev):
-            if world > 1:
+        for batch in train_batches:
+            if shard:
                 batch = [shard_batch(t, rank, world) for t in batch]
             v_plane, v_field, U, V, W, re, _dpdx = [t.float() for t in batch]
             if use_graph and graphed is None and v_plane.shape[0] == args.batch_size:
@@ -330,7 +353,7 @@ def run_full_field(args, idx, dev, rank, world, log):
         model.eval()
         test_tot, test_cnt = torch.zeros((), device=dev), 0
         with torch.no_grad():
-            for batch in DevicePrefetcher(test_loader, dev):
+            for batch in test_batches:
                 v_plane, v_field, U, V, W, re, _dpdx = [t.float() for t in batch]
                 objective(forward(v_plane, re), (v_field, U, V, W))
                 test_tot += objective.last_terms[0]                                  # test metric: the data term
