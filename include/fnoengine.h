@@ -529,6 +529,34 @@ int fno_data_gather(int src_dtype, int stat_dtype, const void* src, size_t n_src
                     const void* mean, const void* std_, double eps, float* out, size_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Device-resident PINO training data (libs/pino_utils/datasets.py DevicePinoBatches): a batch (u, a_in) of a
+ * MultipleReynoldsKFaDataset from tensors that stay on the device, one launch each.  idx (count) int64 on the device picks the
+ * entries.  Both kernels move 32-bit words, never floats: NaN payloads, infinities, -0.0 and denormals arrive unchanged.
+ *
+ * fno_data_transpose_gather: src is a pool of n_src entries of (rows, cols) float32; for entry e, r < rows, c < cols
+ *     out[e * out_stride + c * rows + r] = src[idx[e] * rows * cols + r * cols + c]
+ * (the dataset: rows = T frames of a window, cols = S * S; every entry a (T, S*S) -> (S*S, T) transpose).  The source is read in
+ * whole runs along c (16-byte loads where the address allows), the layout turns in LDS, the destination is written in whole
+ * 16-byte vectors along r laid over the output's address, so `out` needs the alignment of a float only and rows may be odd; rows
+ * is not bounded (frame chunks), rows == 1 is a gather-copy.
+ * FNO_EINVAL: a null src / idx / out, rows or cols < 1, out_stride < rows * cols, a tensor not aligned to its element size;
+ * FNO_EUNSUPPORTED: a pool beyond 2^62 bytes or an output beyond 2^60 floats.
+ *
+ * fno_pino_input: a0 is a pool of n_src planes (s1, s2) float32, gx (s1), gy (s2), gt (t) the axis vectors of the grid;
+ *     out[e, x, y, k, :] = (gx[x], gy[y], gt[k], a0[idx[e], x, y])          channels-last (count, s1, s2, t, 4)
+ * one 16-byte store per grid point, a0 read once per (x, y).  FNO_EINVAL: a null a0 / idx / gx / gy / gt / out, s1, s2 or t < 1,
+ * a tensor not aligned to its element size, out not aligned to 16 bytes; FNO_EUNSUPPORTED: the same two size limits.
+ *
+ * Both: every index is compared unsigned against n_src before it becomes an address; an entry whose index is out of range reads
+ * nothing and all its outputs are NaN.  One launch, no workspace, no atomics, 64-bit addressing, capturable.  count == 0
+ * succeeds without a launch.  The checks need no GPU.
+ * ---------------------------------------------------------------------- */
+int fno_data_transpose_gather(const float* src, size_t n_src, int rows, int cols, const long long* idx, size_t count, float* out,
+                              size_t out_stride, void* stream);
+int fno_pino_input(const float* a0, size_t n_src, const long long* idx, size_t count, const float* gx, const float* gy,
+                   const float* gt, int s1, int s2, int t, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Lifting layer on its own:  y = W x + b,  x (B, Cin <= 4, PW) -> y (B, C, PW), C in {32, 64}, PW % 128 == 0
  * (neuralop/models/tfno.py:11-20; also the `fc0` + Re-conditioning front of the PINO observers,
  * libs/models/pino_models/pinobserver.py:205-207, once its two linear maps are composed).  backward gives the

@@ -32,6 +32,7 @@
 #include "k_channel_mlp.h"
 #include "k_domain_pad.h"
 #include "k_data_gather.h"
+#include "k_pino_batch.h"
 #include "k_spectral_mid.h"
 #include "k_spec1d.h"
 #include "k_pino_loss.h"
@@ -3697,6 +3698,52 @@ extern "C" int fno_data_gather(int src_dtype, int stat_dtype, const void* src, s
                                   : data_gather_launch<double, false>("k_data_gather<f64, cast>", 0, grid, st, a);
   return norm ? data_gather_launch<float, true>("k_data_gather<f32, norm>", stat_dtype, grid, st, a)
               : data_gather_launch<float, false>("k_data_gather<f32, cast>", 0, grid, st, a);
+}
+
+// ===========================================================================
+// Device-resident PINO training data (k_pino_batch.h): a batch of a MultipleReynoldsKFaDataset from its resident tensors, one
+// launch per tensor: u as a transposing gather, a_in = (x, y, t, u0) written in place.
+// ===========================================================================
+extern "C" int fno_data_transpose_gather(const float* src, size_t n_src, int rows, int cols, const long long* idx, size_t count,
+                                         float* out, size_t out_stride, void* stream) {
+  const char* fn = "fno_data_transpose_gather";
+  if (!src || !idx || !out) return fail(FNO_EINVAL, "%s: null argument", fn);
+  if (rows < 1 || cols < 1) return fail(FNO_EINVAL, "%s: entries of %d x %d elements (at least 1 x 1)", fn, rows, cols);
+  const unsigned long long n = (unsigned long long)rows * (unsigned long long)cols;
+  if (out_stride < n) return fail(FNO_EINVAL, "%s: out_stride %zu is shorter than the %d x %d entry", fn, out_stride, rows, cols);
+  if ((unsigned __int128)n_src * n * 4 > ((unsigned __int128)1 << 62) || (unsigned __int128)count * out_stride > ((unsigned __int128)1 << 60))
+    return fail(FNO_EUNSUPPORTED, "%s: at most 2^62 bytes in the pool and 2^60 floats in the output", fn);
+  if (((uintptr_t)src & 3) || ((uintptr_t)idx & 7) || ((uintptr_t)out & 3)) return fail(FNO_EINVAL, "%s: tensor not aligned to its element size", fn);
+  if (count == 0) return FNO_OK;
+  TransposeGatherArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = reinterpret_cast<const unsigned*>(src); a.idx = idx; a.out = reinterpret_cast<unsigned*>(out);
+  a.n_src = n_src; a.out_stride = out_stride; a.count = count; a.rows = rows; a.cols = cols;
+  const dim3 grid((unsigned)((cols + TG_COLS - 1) / TG_COLS), (unsigned)std::min<size_t>(count, 65535));
+  LV(rows > TG_ROWS ? "k_data_transpose_gather<chunked>" : "k_data_transpose_gather<one tile>", 0, (int)std::min<size_t>(count, 0x7fffffff));
+  return launch("k_data_transpose_gather", k_data_transpose_gather, grid, dim3(256), 0, (hipStream_t)stream, a);
+}
+
+extern "C" int fno_pino_input(const float* a0, size_t n_src, const long long* idx, size_t count, const float* gx, const float* gy,
+                              const float* gt, int s1, int s2, int t, float* out, void* stream) {
+  const char* fn = "fno_pino_input";
+  if (!a0 || !idx || !gx || !gy || !gt || !out) return fail(FNO_EINVAL, "%s: null argument", fn);
+  if (s1 < 1 || s2 < 1 || t < 1) return fail(FNO_EINVAL, "%s: a grid of %d x %d x %d points (at least 1 x 1 x 1)", fn, s1, s2, t);
+  const unsigned long long npts = (unsigned long long)s1 * (unsigned long long)s2;
+  if ((unsigned __int128)n_src * npts * 4 > ((unsigned __int128)1 << 62) || (unsigned __int128)count * npts * t * 4 > ((unsigned __int128)1 << 60))
+    return fail(FNO_EUNSUPPORTED, "%s: at most 2^62 bytes in the pool and 2^60 floats in the output", fn);
+  if (((uintptr_t)a0 & 3) || ((uintptr_t)idx & 7) || (((uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gt) & 3))
+    return fail(FNO_EINVAL, "%s: tensor not aligned to its element size", fn);
+  if ((uintptr_t)out & 15) return fail(FNO_EINVAL, "%s: out must be aligned to 16 bytes (one store per grid point)", fn);
+  if (count == 0) return FNO_OK;
+  PinoInputArgs a;
+  memset(&a, 0, sizeof(a));
+  a.a0 = reinterpret_cast<const unsigned*>(a0); a.idx = idx; a.out = reinterpret_cast<unsigned*>(out);
+  a.gx = reinterpret_cast<const unsigned*>(gx); a.gy = reinterpret_cast<const unsigned*>(gy); a.gt = reinterpret_cast<const unsigned*>(gt);
+  a.n_src = n_src; a.count = count; a.npts = npts; a.s2 = s2; a.t = t;
+  const dim3 grid((unsigned)std::min<unsigned long long>((npts + PIN_POINTS - 1) / PIN_POINTS, 1u << 20), (unsigned)std::min<size_t>(count, 65535));
+  LV("k_pino_input", 0, (int)std::min<size_t>(count, 0x7fffffff));
+  return launch("k_pino_input", k_pino_input, grid, dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // ===========================================================================

@@ -2593,3 +2593,66 @@ def data_gather(pool, idx, view, mean=None, std=None, eps=1e-5, out=None, out_st
     _call(e, pool.device, "fno_data_gather", _DATA_DTYPES[pool.dtype], stat, pool, n_src, snap, offset, row_stride, col_stride,
           rows, cols, idx_dev, count, mean, std, float(eps), out, stride, STREAM)
     return out
+
+
+# ----------------------------------------------------------------------------
+# device-resident PINO training data: a batch (u, a_in) of a MultipleReynoldsKFaDataset from its resident tensors
+# ----------------------------------------------------------------------------
+def _data_out(e, out, anchor, shape, align=4):
+    """a gather's output: new, or the caller's dense float32 buffer of exactly that many elements (e.g. a static input of a
+    captured step) whose first element is aligned to `align` bytes; returned in `shape`"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=anchor.device)
+    if not torch.is_tensor(out):
+        raise _refuse(e, "out", "be a tensor", type(out).__name__)
+    out = _operand(e, "out", out, anchor, dtype=torch.float32, numel=math.prod(shape), layout="dense")
+    if out.data_ptr() % align:
+        raise _refuse(e, "out", f"start on a {align}-byte boundary", f"address {out.data_ptr():#x}")
+    return out.view(shape)
+
+
+def data_transpose_gather(pool, idx, out=None):
+    """out[e] = pool[idx[e]].transpose(0, 1) as words: pool (n_src, rows, cols) dense float32 on the GPU -> (len(idx), cols, rows),
+    every bit pattern unchanged.  idx: a CPU int64 vector, checked against 0 <= idx < n_src here, before anything is launched, and
+    uploaded afterwards.  `out`: a dense float32 tensor of len(idx) * rows * cols elements that is written in place (any 4-byte
+    alignment) and returned in the result's shape; None: a new tensor.  One launch (k_data_transpose_gather)."""
+    e = "data_transpose_gather"
+    _gpu_anchor(e, "pool", pool)
+    if pool.dim() != 3 or pool.numel() == 0:
+        raise _refuse(e, "pool", "be (n_src, rows, cols) with at least one element", tuple(pool.shape))
+    pool = _operand(e, "pool", pool, pool, layout="dense")
+    n_src, rows, cols = pool.shape
+    count = _data_indices(e, idx, n_src)
+    out = _data_out(e, out, pool, (count, cols, rows))
+    if count == 0:
+        return out
+    idx_dev = idx.to(pool.device)        # (never through torch.empty / _bytes: an index buffer is not poisoned, tests/hygiene.py)
+    _call(e, pool.device, "fno_data_transpose_gather", pool, n_src, rows, cols, idx_dev, count, out, rows * cols, STREAM)
+    return out
+
+
+def pino_input(a0, idx, gx, gy, gt, out=None):
+    """out[e, x, y, k] = (gx[x], gy[y], gt[k], a0[idx[e], x, y]): the (x, y, t, u0) input of the PINO observers, channels-last
+    (len(idx), s1, s2, t, 4), from a0 (n_src, s1, s2) and the axis vectors gx (s1), gy (s2), gt (t) - dense float32 on the GPU,
+    moved as words.  idx: a CPU int64 vector, checked against 0 <= idx < n_src here, before anything is launched, and uploaded
+    afterwards.  `out`: a dense float32 tensor of that many elements on a 16-byte boundary, written in place and returned in the
+    result's shape; None: a new tensor.  One launch (k_pino_input)."""
+    e = "pino_input"
+    _gpu_anchor(e, "a0", a0)
+    if a0.dim() != 3 or a0.numel() == 0:
+        raise _refuse(e, "a0", "be (n_src, s1, s2) with at least one element", tuple(a0.shape))
+    a0 = _operand(e, "a0", a0, a0, layout="dense")
+    n_src, s1, s2 = a0.shape
+    axes = []
+    for name, g, n in (("gx", gx, s1), ("gy", gy, s2), ("gt", gt, None)):
+        if not torch.is_tensor(g) or g.dim() != 1 or g.numel() == 0:
+            raise _refuse(e, name, "be a vector with at least one element", tuple(g.shape) if torch.is_tensor(g) else type(g).__name__)
+        axes.append(_operand(e, name, g, a0, numel=n))
+    t = axes[2].numel()
+    count = _data_indices(e, idx, n_src)
+    out = _data_out(e, out, a0, (count, s1, s2, t, 4), align=16)
+    if count == 0:
+        return out
+    idx_dev = idx.to(a0.device)          # (as above)
+    _call(e, a0.device, "fno_pino_input", a0, n_src, idx_dev, count, *axes, s1, s2, t, out, STREAM)
+    return out

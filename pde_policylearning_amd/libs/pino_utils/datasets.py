@@ -80,6 +80,89 @@ class MultipleReynoldsKFaDataset(Dataset):
         return self.data.shape[0]
 
 
+class DevicePinoBatches(object):
+    """Batches of a MultipleReynoldsKFaDataset assembled on the GPU from the dataset's own tensors, uploaded once: iterating
+    yields the `(u (B, S, S, T), a_in (B, S, S, T, 4), re (B,))` float32 device tensors that
+    `DevicePrefetcher(DataLoader(dataset, batch_size * world, shuffle, drop_last, generator))` followed by `shard_batch` yields,
+    bit for bit, without per-item host work: no `torch.cat` of a grid that is the same for every item, no strided collate of
+    the permuted `u`, no pinned copy of the whole batch.
+
+    Pool: `dataset.data` in the (N, T, S, S) storage it is a permuted view of, `dataset.a_data` as (N, S, S) and `dataset.re`.
+    Subsampling, windowing by `t_duration`, `offset`, `total_samples` and the Reynolds bookkeeping stay the host class's, done
+    once at load.  u is one functional.data_transpose_gather launch, a_in one functional.pino_input launch from the three axis
+    vectors of `dataset.grid` (checked here to reproduce the grid exactly), re a gather on the host of `batch` floats.
+    Order: the index batches come from a DataLoader with the same arguments over an index-only dataset of the same length, so
+    order, generator consumption, ragged tail and drop_last are the host loader's by construction.  Data parallelism: a rank
+    gathers only its slice of the global batch.  A pool beyond `max_bytes` raises and the host loader remains the path."""
+
+    def __init__(self, dataset, batch_size, device, shuffle, generator=None, drop_last=False, rank=0, world=1, max_bytes=8 << 30):
+        from torch.utils.data import DataLoader
+        from ..pde_data_loader import _ItemIndex
+        if not isinstance(dataset, MultipleReynoldsKFaDataset):
+            raise NotImplementedError(f"DevicePinoBatches: {type(dataset).__name__} (MultipleReynoldsKFaDataset)")
+        self.dataset, self.device = dataset, torch.device(device)
+        self.batch_size, self.rank, self.world = int(batch_size), int(rank), int(world)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"DevicePinoBatches: rank {rank} outside a world of {world}")
+        data, a = dataset.data, dataset.a_data
+        grid = dataset.grid
+        N = data.shape[0]
+        if data.dim() != 4 or data.dtype != torch.float32 or a.dtype != torch.float32 or a.dim() != 5 or grid.dim() != 4 \
+                or tuple(a.shape) != (N,) + tuple(grid.shape[:2]) + (1, 1) or grid.shape[3] != 3 or grid.dtype != torch.float32 \
+                or len(dataset.re) < N:
+            raise ValueError(f"DevicePinoBatches: data {tuple(data.shape)} {data.dtype}, a_data {tuple(a.shape)} {a.dtype}, grid "
+                             f"{tuple(grid.shape)} {grid.dtype}, {len(dataset.re)} Reynolds numbers (float32 (N, S, S, T), "
+                             "(N, S', S', 1, 1), (S', S', T', 3) and at least N expected)")
+        need = 4 * (data.numel() + a.numel() + N)
+        if need > max_bytes:
+            raise MemoryError(f"device-resident data of {dataset.paths[0]}: the pool would hold {need} bytes, the budget is "
+                              f"{int(max_bytes)} bytes (max_bytes; the host loader remains the path for such a dataset)")
+        S1, S2, T = grid.shape[:3]
+        self._axes = (grid[:, 0, 0, 0].clone(), grid[0, :, 0, 1].clone(), grid[0, 0, :, 2].clone())
+        gx, gy, gt = self._axes
+        again = torch.stack((gx[:, None, None].expand(S1, S2, T), gy[None, :, None].expand(S1, S2, T),
+                             gt[None, None, :].expand(S1, S2, T)), dim=-1)
+        if not torch.equal(again, grid):
+            raise ValueError("DevicePinoBatches: dataset.grid is not the product of its three axis vectors (x along axis 0, y "
+                             "along axis 1, t along axis 2); the host loader remains the path")
+        self.shape = tuple(data.shape[1:])          # u: (S, S, T); a_in: the grid's (S', S', T', 4)
+        self.loader = DataLoader(_ItemIndex(N), batch_size=self.batch_size * self.world, shuffle=shuffle, drop_last=drop_last,
+                                 generator=generator)
+        self._re = torch.as_tensor(np.asarray(dataset.re)).float()      # the cast DevicePrefetcher makes on the device: one rounding
+        self._pool = None
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _resident(self):
+        """(u pool (N, T, S * S), a0 pool (N, S, S), gx, gy, gt) on the device, uploaded at the first batch"""
+        if self._pool is None:
+            ds = self.dataset
+            N, (S1, S2, T) = len(ds), self.shape
+            frames = ds.data.permute(0, 3, 1, 2)      # the storage's own order: contiguous without a copy wherever load() made it
+            self._pool = (frames.contiguous().view(N, T, S1 * S2).to(self.device),
+                          ds.a_data.reshape((N,) + tuple(ds.grid.shape[:2])).to(self.device), *(g.to(self.device) for g in self._axes))
+        return self._pool
+
+    def index_batches(self):
+        """this rank's item indices of every batch of one epoch (CPU int64), in the host loader's order"""
+        for items in self.loader:
+            if self.world > 1:
+                n = items.shape[0]
+                assert n % self.world == 0, f"global batch {n} not divisible by world size {self.world}"
+                per = n // self.world
+                items = items[self.rank * per:(self.rank + 1) * per]
+            yield items
+
+    def __iter__(self):
+        from ... import functional as F
+        S1, S2, T = self.shape
+        for items in self.index_batches():
+            frames, a0, gx, gy, gt = self._resident()
+            u = F.data_transpose_gather(frames, items).view(items.shape[0], S1, S2, T)
+            yield u, F.pino_input(a0, items, gx, gy, gt), self._re[items].to(self.device)
+
+
 def _darcy_arrays(datapath):
     """`coeff` and `sol` of a MATLAB file (scipy.io is needed for that alone), or of a mapping that holds both arrays"""
     if hasattr(datapath, 'keys'):

@@ -16,11 +16,17 @@ import yaml
 from torch.utils.data import DataLoader
 
 from .libs.models.pino_models import PINObserver2d
-from .libs.pino_utils.datasets import MultipleReynoldsKFaDataset, sample_data
+from .libs.pino_utils.datasets import DevicePinoBatches, MultipleReynoldsKFaDataset, sample_data
 from .libs.pino_utils.losses import get_forcing
 from .libs.pino_utils.utils import count_params, dict2str, save_ckpt
 from .trainer import (enable_dp_exchange, DevicePrefetcher, FlatGradBucket, FusedAdam, FusedLpLoss, MultiStepLR, PinoObjective, broadcast_parameters,
                       shard_batch, train_step)
+
+
+def _device_batches(loader, device):
+    """what a loop iterates: a DevicePinoBatches as it is (its batches are on the device and cut to this rank's slice), a host
+    loader behind the asynchronous staging"""
+    return loader if isinstance(loader, DevicePinoBatches) else DevicePrefetcher(loader, device)
 
 
 @torch.no_grad()
@@ -28,7 +34,7 @@ def eval_ns(model, val_loader, criterion, device):
     """mean and standard error of the per-batch relative L2 error (train_pino.py:24-38)."""
     model.eval()
     errs = []
-    for u, a, re in DevicePrefetcher(val_loader, device):
+    for u, a, re in _device_batches(val_loader, device):
         errs.append(float(criterion(model(a, re).reshape(u.shape), u)))
     model.train()
     n = len(errs)
@@ -48,12 +54,13 @@ def train_ns(model, train_u_loader, val_loader, optimizer, scheduler, device, co
                               tcfg['xy_loss'], scale=1.0 / world)       # mean-reduced losses: ranks average
     lploss = FusedLpLoss(size_average=True)
     bucket = optimizer.bucket
-    batches = sample_data(DevicePrefetcher(train_u_loader, device))
+    batches = sample_data(_device_batches(train_u_loader, device))
+    shard = world > 1 and not isinstance(train_u_loader, DevicePinoBatches)
     log_every = max(1, int(getattr(args, "log_every", 100)))
     history = []
     for e in range(tcfg['start_iter'], tcfg['num_iter']):
         u, a_in, re = next(batches)
-        if world > 1:
+        if shard:
             u, a_in, re = (shard_batch(t, rank, world) for t in (u, a_in, re))
         loss = train_step(model, bucket, optimizer, (a_in, re), (u, a_in, re), objective)
         scheduler.step()
@@ -84,8 +91,24 @@ def _dataset(config, paths, res, n_samples, offset):
                                       offset=offset, t_duration=d['t_duration'])
 
 
+def device_data_plan(config, args):
+    """(on, budget in bytes) of the device-resident data: --device-data or YAML `data: device_data: true`; the budget from
+    --device-data-max-gb (8 GiB)"""
+    on = bool(getattr(args, "device_data", False) or config.get('data', {}).get('device_data', False))
+    return on, int(float(getattr(args, "device_data_max_gb", 8.0) or 8.0) * (1 << 30))
+
+
+def _loader(dataset, batch_size, device, plan, shuffle=False, drop_last=False, rank=0, world=1):
+    """the batches of `dataset`: a host DataLoader of the global batch (default), or DevicePinoBatches in the same order"""
+    on, max_bytes = plan
+    if on:
+        return DevicePinoBatches(dataset, batch_size, device, shuffle, drop_last=drop_last, rank=rank, world=world, max_bytes=max_bytes)
+    return DataLoader(dataset, batch_size=batch_size * world, shuffle=shuffle, drop_last=drop_last)
+
+
 def run(config, args, log=print):
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
@@ -101,15 +124,16 @@ def run(config, args, log=print):
     if ckpt:
         model.load_state_dict(ckpt['model'])
     d, t = config['data'], config['train']
+    plan = device_data_plan(config, args)
     if args.test:
         testset = _dataset(config, d.get('paths', d['test_paths']), config['test']['data_res'], d['n_test_samples'], d['testoffset'])
-        err, std = eval_ns(model, DataLoader(testset, batch_size=config['test']['batchsize']), FusedLpLoss(size_average=True), device)
+        err, std = eval_ns(model, _loader(testset, config['test']['batchsize'], device, plan), FusedLpLoss(size_average=True), device)
         log(f'Averaged test relative L2 error: {err}; Standard error: {std}')
         return err, std
     u_set = _dataset(config, d['train_paths'], d['data_res'], d['n_data_samples'], d['offset'])
     valset = _dataset(config, d['test_paths'], config['test']['data_res'], d['n_test_samples'], d['testoffset'])
-    u_loader = DataLoader(u_set, batch_size=t['batchsize'] * world, shuffle=True, drop_last=world > 1)
-    val_loader = DataLoader(valset, batch_size=t['batchsize'])
+    u_loader = _loader(u_set, t['batchsize'], device, plan, shuffle=True, drop_last=world > 1, rank=rank, world=world)
+    val_loader = _loader(valset, t['batchsize'], device, plan)
     broadcast_parameters(model)
     bucket = FlatGradBucket(model.parameters(), direct_module=model)
     if world > 1:      # 268 MB (modes 8) / 4.2 GB (modes 20) of spectral weights: per-layer segments overlap the backward pass
@@ -131,6 +155,12 @@ def build_parser():
     ap.add_argument('--ckpt', type=str, default=None)
     ap.add_argument('--test', action='store_true')
     ap.add_argument('--log-every', type=int, default=100)
+    ap.add_argument('--device-data', dest='device_data', action='store_true', help="keep the datasets' tensors on the GPU and "
+                    "assemble every training and validation batch there (libs.pino_utils.datasets.DevicePinoBatches: the host "
+                    "loader's batches bit for bit, two launches each); YAML key data: device_data; off: DataLoader + "
+                    "DevicePrefetcher as before")
+    ap.add_argument('--device-data-max-gb', dest='device_data_max_gb', type=float, default=8.0,
+                    help="budget of the device-resident pool in GiB; a larger dataset raises and the host loader remains the path")
     return ap
 
 
