@@ -165,6 +165,32 @@ class _ItemIndex(Dataset):
         return i
 
 
+class _RankIndexBatches(object):
+    """The index loader of a device-resident batch source and this rank's slice of its batches: a DataLoader with the host
+    loader's arguments over an index-only dataset of `n` items, so order, draws from the generator, ragged tail and drop_last
+    are the host loader's; of every global batch of batch_size * world items a rank keeps its own batch_size."""
+
+    def _index_loader(self, n, batch_size, shuffle, generator, drop_last, rank, world):
+        self.batch_size, self.rank, self.world = int(batch_size), int(rank), int(world)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"{type(self).__name__}: rank {rank} outside a world of {world}")
+        self.loader = DataLoader(_ItemIndex(n), batch_size=self.batch_size * self.world, shuffle=shuffle, drop_last=drop_last,
+                                 generator=generator)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def index_batches(self):
+        """this rank's item indices of every batch of one epoch (CPU int64), in the host loader's order"""
+        for items in self.loader:
+            if self.world > 1:
+                n = items.shape[0]
+                assert n % self.world == 0, f"global batch {n} not divisible by world size {self.world}"
+                per = n // self.world
+                items = items[self.rank * per:(self.rank + 1) * per]
+            yield items
+
+
 _TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
 _STAGE_BYTES = 64 << 20
 _POOLS = weakref.WeakValueDictionary()      # (folder, device) -> _FolderPool: datasets over one folder share one pool
@@ -257,7 +283,7 @@ def _folder_pool(folder, device):
     return pool
 
 
-class DeviceBatches(object):
+class DeviceBatches(_RankIndexBatches):
     """Batches of a PDEDataset, SequentialPDEDataset or FullFieldNSDataset assembled on the GPU from a device-resident pool of
     the folder's raw files: iterating yields the tuples of float32 device tensors that
     `DevicePrefetcher(DataLoader(dataset, batch_size * world, shuffle, drop_last, generator))` followed by `shard_batch` yields,
@@ -276,11 +302,7 @@ class DeviceBatches(object):
         if not isinstance(dataset, (PDEDataset, SequentialPDEDataset, FullFieldNSDataset)):
             raise NotImplementedError(f"DeviceBatches: {type(dataset).__name__} (PDEDataset, SequentialPDEDataset, FullFieldNSDataset)")
         self.dataset, self.device = dataset, torch.device(device)
-        self.batch_size, self.rank, self.world = int(batch_size), int(rank), int(world)
-        if not 0 <= self.rank < self.world:
-            raise ValueError(f"DeviceBatches: rank {rank} outside a world of {world}")
-        self.loader = DataLoader(_ItemIndex(len(dataset)), batch_size=self.batch_size * self.world, shuffle=shuffle,
-                                 drop_last=drop_last, generator=generator)
+        self._index_loader(len(dataset), batch_size, shuffle, generator, drop_last, rank, world)
         self.T = 1 if isinstance(dataset, PDEDataset) else int(dataset.timestep)
         index = [int(i) for i in dataset.data_index][:len(dataset) * self.T]
         self.file_index = torch.tensor(index, dtype=torch.int64).reshape(len(dataset), self.T)      # file of (item, time step)
@@ -296,9 +318,6 @@ class DeviceBatches(object):
             slots = self.pool.plan(tag, [files[i] for i in index], max_bytes)
             self._slots[tag] = torch.tensor(slots, dtype=torch.int64).reshape(len(dataset), self.T)
         self._plan_views()
-
-    def __len__(self):
-        return len(self.loader)
 
     @staticmethod
     def _crop_extent(n, d, limit):
@@ -347,16 +366,6 @@ class DeviceBatches(object):
                 self._re_row = torch.tensor([ds.re for _ in range(self.T)]).to(self.device).float()
                 self._dpdx = torch.tensor([ds.dpdx_all[i] for i in files]).reshape(self.file_index.shape).to(self.device).float()
         return {tag: self.pool.tensor(tag) for tag in self._slots}
-
-    def index_batches(self):
-        """this rank's item indices of every batch of one epoch (CPU int64), in the host loader's order"""
-        for items in self.loader:
-            if self.world > 1:
-                n = items.shape[0]
-                assert n % self.world == 0, f"global batch {n} not divisible by world size {self.world}"
-                per = n // self.world
-                items = items[self.rank * per:(self.rank + 1) * per]
-            yield items
 
     def __iter__(self):
         from .. import functional as F

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from ..pde_data_loader import _RankIndexBatches
 from .utils import get_grid3d, torch2dgrid
 
 
@@ -80,7 +81,7 @@ class MultipleReynoldsKFaDataset(Dataset):
         return self.data.shape[0]
 
 
-class DevicePinoBatches(object):
+class DevicePinoBatches(_RankIndexBatches):
     """Batches of a MultipleReynoldsKFaDataset assembled on the GPU from the dataset's own tensors, uploaded once: iterating
     yields the `(u (B, S, S, T), a_in (B, S, S, T, 4), re (B,))` float32 device tensors that
     `DevicePrefetcher(DataLoader(dataset, batch_size * world, shuffle, drop_last, generator))` followed by `shard_batch` yields,
@@ -96,17 +97,13 @@ class DevicePinoBatches(object):
     gathers only its slice of the global batch.  A pool beyond `max_bytes` raises and the host loader remains the path."""
 
     def __init__(self, dataset, batch_size, device, shuffle, generator=None, drop_last=False, rank=0, world=1, max_bytes=8 << 30):
-        from torch.utils.data import DataLoader
-        from ..pde_data_loader import _ItemIndex
         if not isinstance(dataset, MultipleReynoldsKFaDataset):
             raise NotImplementedError(f"DevicePinoBatches: {type(dataset).__name__} (MultipleReynoldsKFaDataset)")
         self.dataset, self.device = dataset, torch.device(device)
-        self.batch_size, self.rank, self.world = int(batch_size), int(rank), int(world)
-        if not 0 <= self.rank < self.world:
-            raise ValueError(f"DevicePinoBatches: rank {rank} outside a world of {world}")
         data, a = dataset.data, dataset.a_data
         grid = dataset.grid
         N = data.shape[0]
+        self._index_loader(N, batch_size, shuffle, generator, drop_last, rank, world)
         if data.dim() != 4 or data.dtype != torch.float32 or a.dtype != torch.float32 or a.dim() != 5 or grid.dim() != 4 \
                 or tuple(a.shape) != (N,) + tuple(grid.shape[:2]) + (1, 1) or grid.shape[3] != 3 or grid.dtype != torch.float32 \
                 or len(dataset.re) < N:
@@ -126,13 +123,8 @@ class DevicePinoBatches(object):
             raise ValueError("DevicePinoBatches: dataset.grid is not the product of its three axis vectors (x along axis 0, y "
                              "along axis 1, t along axis 2); the host loader remains the path")
         self.shape = tuple(data.shape[1:])          # u: (S, S, T); a_in: the grid's (S', S', T', 4)
-        self.loader = DataLoader(_ItemIndex(N), batch_size=self.batch_size * self.world, shuffle=shuffle, drop_last=drop_last,
-                                 generator=generator)
         self._re = torch.as_tensor(np.asarray(dataset.re)).float()      # the cast DevicePrefetcher makes on the device: one rounding
         self._pool = None
-
-    def __len__(self):
-        return len(self.loader)
 
     def _resident(self):
         """(u pool (N, T, S * S), a0 pool (N, S, S), gx, gy, gt) on the device, uploaded at the first batch"""
@@ -143,16 +135,6 @@ class DevicePinoBatches(object):
             self._pool = (frames.contiguous().view(N, T, S1 * S2).to(self.device),
                           ds.a_data.reshape((N,) + tuple(ds.grid.shape[:2])).to(self.device), *(g.to(self.device) for g in self._axes))
         return self._pool
-
-    def index_batches(self):
-        """this rank's item indices of every batch of one epoch (CPU int64), in the host loader's order"""
-        for items in self.loader:
-            if self.world > 1:
-                n = items.shape[0]
-                assert n % self.world == 0, f"global batch {n} not divisible by world size {self.world}"
-                per = n // self.world
-                items = items[self.rank * per:(self.rank + 1) * per]
-            yield items
 
     def __iter__(self):
         from ... import functional as F

@@ -1,13 +1,13 @@
 """Memory-hygiene harness for the engine wrappers (a helper module, not a conftest).
 
-Every buffer the engine writes comes from an uninitialised allocation in pde_policylearning_amd/functional.py (`_bytes` for
-`saved`, `xhat` and every workspace; torch.empty / torch.empty_like for outputs and gradients) or in trainer.py (the dead
-Adam moments of FusedAdam.sync_dead_slices).  Under torch's caching allocator such a block usually holds what the same
-computation left there the last time, so a kernel that skips part of its output, reads a slab nobody wrote or stores one
-tile past the end passes every value test.  This module takes the allocator out of the picture:
+Every buffer the engine writes comes from an uninitialised allocation in a module of the pde_policylearning_amd/functional/
+package (`_bytes` of functional/_core.py for `saved`, `xhat` and every workspace; torch.empty / torch.empty_like for outputs and
+gradients) or in trainer.py (the dead Adam moments of FusedAdam.sync_dead_slices).  Under torch's caching allocator such a
+block usually holds what the same computation left there the last time, so a kernel that skips part of its output, reads a
+slab nobody wrote or stores one tile past the end passes every value test.  This module takes the allocator out of the picture:
 
-  poisoned(pattern)   while active, every allocation those two modules make through `torch.empty`, `torch.empty_like` and
-                      `functional._bytes` is numel + 2 G elements filled with the pattern byte, and the caller gets the
+  poisoned(pattern)   while active, every allocation those modules make through `torch.empty`, `torch.empty_like` and
+                      their `_bytes` name is numel + 2 G elements filled with the pattern byte, and the caller gets the
                       contiguous middle.  G * itemsize = GUARD_BYTES (256 KB: more than one 128-pixel x 64-channel fp32 tile,
                       a multiple of 256 bytes, so the middle keeps the alignment a fresh allocation has).  `torch` itself is
                       not patched: the modules' `torch` name is swapped for a proxy that overrides the two allocators and
@@ -145,14 +145,20 @@ class _TorchProxy(object):
 
 
 def _engine_modules():
+    """every module found in the functional package (one added later is covered without an edit here), the package itself
+    (callers allocate through F.torch / F._bytes too) and trainer"""
+    import importlib
+    import pkgutil
     from pde_policylearning_amd import functional, trainer
-    return [functional, trainer]
+    subs = [importlib.import_module(f"{functional.__name__}.{m.name}") for m in pkgutil.iter_modules(functional.__path__)]
+    return subs + [functional, trainer]
 
 
 @contextlib.contextmanager
 def poisoned(pattern, modules=None):
-    """Replace the allocations of the engine wrappers (functional.py and trainer.py, or `modules`) by poisoned, guarded
-    buffers.  `pattern`: a key of PATTERNS or a byte value.  Yields the Poison registry; the patches are undone on exit."""
+    """Replace the allocations of the engine wrappers (the modules of functional/ and trainer.py, or `modules`) by poisoned,
+    guarded buffers.  Each module's own `torch` and `_bytes` names are swapped, whichever of the two it has.  `pattern`: a key
+    of PATTERNS or a byte value.  Yields the Poison registry; the patches are undone on exit."""
     byte = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
     poison = Poison(byte)
     mods = list(modules) if modules is not None else _engine_modules()
@@ -162,11 +168,10 @@ def poisoned(pattern, modules=None):
         return poison.alloc((max(int(n), 256),), torch.uint8, device, _caller_label(1) + " _bytes")
     saved = []
     for m in mods:
-        saved.append((m, "torch", m.__dict__["torch"]))
-        m.torch = proxy
-        if "_bytes" in m.__dict__:
-            saved.append((m, "_bytes", m.__dict__["_bytes"]))
-            m._bytes = _bytes
+        for name, stand_in in (("torch", proxy), ("_bytes", _bytes)):
+            if name in m.__dict__:
+                saved.append((m, name, m.__dict__[name]))
+                setattr(m, name, stand_in)
     _active.append(poison)
     try:
         yield poison

@@ -488,7 +488,7 @@ def test_control_refusals_launch_nothing(dev):
             F.ctrl_encode(p.cpu(), m, s)
         with pytest.raises(RuntimeError, match=r"running_stats_update: `means\[0\]` must live on"):
             F.running_stats_update(nine[:1], [nine[1].cpu()], nine[2:3], 1)
-        # the library refuses on its own too (a caller that goes around functional.py)
+        # the library refuses on its own too (a caller that goes around functional/ctrl.py)
         rc = lib.fno_chanflow_diagnostics2(C_byref(grid), 1, 1, grid.metrics(dev).data_ptr(), poisson.table(dev).data_ptr(),
                                            poisson.table(dev).numel() * 8, U.data_ptr(), V.data_ptr(), W.data_ptr(), None, dp.data_ptr(),
                                            torch.zeros(13, dtype=torch.float64, device=dev).data_ptr(), 13, ws3.data_ptr(), ws3.numel(), None)

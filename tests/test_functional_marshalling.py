@@ -1,4 +1,4 @@
-"""functional.py's operand check and shape rules, driven on the CPU (no engine call is made here).
+"""functional/_core.py's operand check and shape rules, driven on the CPU (no engine call is made here).
 
 _operand is the one check between a tensor and its address; it reads only the anchor's device, so CPU tensors (and `meta`
 tensors as "another device") exercise every refusal.  The tiling table and the GELU masks below are written out by hand from

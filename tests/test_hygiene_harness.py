@@ -112,3 +112,32 @@ def test_patterns_and_guard_report():
     with H.poisoned("nan"):
         e = F.torch.empty_like(pm)
     assert e.stride() == pm.stride() and e.shape == pm.shape
+
+
+def _package_modules():
+    """every module of the functional package, found the way an import would find it (not through the harness's own list)"""
+    import importlib
+    import pkgutil
+    found = [importlib.import_module(f"{F.__name__}.{m.name}") for m in pkgutil.iter_modules(F.__path__)]
+    assert len(found) >= 10 and F._bytes.__module__ in [m.__name__ for m in found]
+    return found + [F]
+
+
+def test_every_module_of_the_package_is_poisoned():
+    """The wrappers live in one module per family: inside poisoned() each of them must see the proxy under its own `torch`
+    name and the poisoning allocator under its own `_bytes` name (a module left out would allocate unpoisoned while every
+    hygiene test stayed green), and both names come back on exit."""
+    mods = _package_modules()
+    before = {m.__name__: (m.__dict__.get("torch"), m.__dict__.get("_bytes")) for m in mods}
+    assert sum(t is torch for t, _ in before.values()) >= 10 and sum(b is F._bytes for _, b in before.values()) >= 5
+    with H.poisoned("nan") as p:
+        for m in mods:
+            if "torch" in m.__dict__:
+                assert m.torch is not torch and isinstance(m.torch, H._TorchProxy), m.__name__
+            if "_bytes" in m.__dict__:
+                assert m._bytes is F._bytes and m._bytes is not before[m.__name__][1], m.__name__
+                n0 = len(p.bufs)
+                b = m._bytes(10, torch.device("cpu"))
+                assert len(p.bufs) == n0 + 1 and b.numel() == 256 and bool((b == 0xFF).all()), m.__name__
+    for m in mods:
+        assert (m.__dict__.get("torch"), m.__dict__.get("_bytes")) == before[m.__name__], m.__name__

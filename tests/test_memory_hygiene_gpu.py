@@ -1,7 +1,7 @@
 """Poisoned buffers and guard bands on every engine entry point (harness: tests/hygiene.py).
 
 Each case runs four times: once with torch's own allocations, then under each fill pattern (0x00, 0xFF = NaN, 0x7F = 3.4e38)
-of every buffer functional.py / trainer.py hand to the engine, with 256 KB guard bands around each and the inputs copied into
+of every buffer functional/ and trainer.py hand to the engine, with 256 KB guard bands around each and the inputs copied into
 NaN-framed buffers.  Every output, gradient and loss (for the optimiser: parameters and moments) must be bitwise equal across
 the four runs and finite, the guard bands intact and the inputs bitwise unchanged after the forward and after the backward.
 The engine has no float atomics, so a run-to-run difference means a result read memory nobody wrote for it.  Model cases
